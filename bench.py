@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the HeatAlertEnv hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload configs2] [--num-envs M]
+    python bench.py --gpus N --steps K --warmup W [--workload configs2] [--num-envs M] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps, writes DIR/*.npy with --dump-outputs and prints its line; every
+other measurement or check below (parity, calibration, counter passes, extras, CPU baseline, the multi-GPU self-judging
+runs) runs with --full only.
 
 A "step" is one vector-env step(): every env of the batch advances one day (budget gate,
 feature-row gather, two 28-term logits against its posterior draw, reward, next observation),
@@ -71,24 +75,26 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=153, help="untimed steps (default: 1 episode)")
     p.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                    help="default: configs2 per GPU for every N (the config the >= 10 M target is quoted on: one workload for "
-                        "the whole 1/2/4/8-GPU curve); with N > 1 the line also carries BASELINE configs[4] "
+                        "the whole 1/2/4/8-GPU curve); with N > 1 and --full the line also carries BASELINE configs[4] "
                         "(nn_full_medicare_all shape, 1 048 576 envs per GPU) measured in the same job: `configs4_sharded`")
     p.add_argument("--num-envs", type=int, default=None, help="envs per GPU (overrides the workload's)")
     p.add_argument("--no-obs", action="store_true", help="reward-only step variant")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the reported extras (always-alert policy, sorted episode order, posterior-mean reward)")
+                   help="--full without the reported extras (always-alert policy, sorted episode order, posterior-mean "
+                        "reward)")
     p.add_argument("--no-parity", action="store_true",
-                   help="skip the oracle replay of a strided sample of the timed batch that follows the timed region")
+                   help="--full without the oracle replay of a strided sample of the timed batch that follows the timed "
+                        "region")
     p.add_argument("--only-extras", default=None, metavar="NAME[,NAME...]",
-                   help="single-GPU run: of the reported extras only these (always_alert, sorted, posterior_mean, rollout, "
-                        "configs4, configs1)")
+                   help="single-GPU --full run: of the reported extras only these (always_alert, sorted, posterior_mean, "
+                        "rollout, configs4, configs1)")
     p.add_argument("--no-live-traffic", action="store_true",
-                   help="do not start the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE on tools/pmc_probe.py) that "
-                        "measure roofline.traffic in this very run; the figure is then replayed from profiles/traffic_latest.json "
-                        "when the kernel sources still hash to the recorded value")
+                   help="--full without the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE on tools/pmc_probe.py) "
+                        "that measure roofline.traffic in this very run; the figure is then replayed from "
+                        "profiles/traffic_latest.json when the kernel sources still hash to the recorded value")
     p.add_argument("--no-calibration", action="store_true",
-                   help="skip the in-process copy-rate / access-pattern probe that follows the timed region")
+                   help="--full without the in-process copy-rate / access-pattern probe that follows the timed region")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                    help="weak: the workload's env count per GPU (default); strong: that count split over the GPUs")
@@ -110,12 +116,28 @@ def parse(argv=None):
                    help="scaling sweep in one command, e.g. --sweep 1,2,4,8: this process (which never touches a GPU) runs "
                         "`bench.py --gpus N` for every N in turn, each as a fresh group of child processes, and prints ONE "
                         "JSON line per N (value, per-GPU value, the job's own single-GPU reference, efficiency, what the "
-                        "collective costs, ranks seen) plus a closing summary line. Every job runs the default workload (configs2 "
-                        "per GPU, + configs4_sharded for N > 1) unless --workload says otherwise; --scaling weak (default) or strong")
+                        "collective costs, ranks seen; the per-job self-judging figures need --full) plus a closing summary "
+                        "line. Every job runs the default workload (configs2 per GPU, + configs4 with --full) unless --workload "
+                        "says otherwise; --scaling weak (default) or strong")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="gloo = rehearsal of the multi-rank path (ranks share the GPUs there are; with the "
                         "launcher_stub workload it needs no GPU at all)")
+    p.add_argument("--full", action="store_true",
+                   help="everything besides the headline: the oracle parity replay of the timed batch, the in-process "
+                        "calibration probe, the live rocprofv3 counter passes, a separate back-to-back kernel timing where "
+                        "the timed region has no whole episode, the extras, the CPU baseline and, on N > 1 GPUs, the "
+                        "single-GPU and no-collective runs and configs4_sharded. Without it a run sets up, warms up, times "
+                        "--steps steps, writes --dump-outputs and prints the line; the --no-* options narrow --full")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the caller of step() holds after the last one (obs, reward, "
+                        "terminated, truncated and the numeric entries of info; rank 0's shard) as DIR/<name>.npy in "
+                        "float32 / float64, at most 64 MB in all: above that a fixed, seeded sample of the envs, whose "
+                        "indices are in DIR/env_index.npy")
     a = p.parse_args(argv)
+    if not a.full:
+        if a.tamper or a.only_extras:
+            p.error("--tamper and --only-extras act on legs that only --full runs")
+        a.no_cpu_baseline = a.no_extras = a.no_parity = a.no_live_traffic = a.no_calibration = True
     if a.sweep is not None:
         try:
             a.sweep = [int(x) for x in a.sweep.split(",") if x.strip()]
@@ -219,7 +241,9 @@ def run_sweep(args) -> int:
     for n in args.sweep:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--workload", args.workload, "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--scaling", args.scaling, "--backend", args.backend, "--seed", str(args.seed),
-               "--launch-timeout", str(args.launch_timeout), "--no-cpu-baseline"] + ([] if n > 1 else ["--only-extras", "configs4"])
+               "--launch-timeout", str(args.launch_timeout), "--no-cpu-baseline"]
+        if args.full:
+            cmd += ["--full"] + ([] if n > 1 else ["--only-extras", "configs4"])
         if args.num_envs:
             cmd += ["--num-envs", str(args.num_envs)]
         if args.no_obs:
@@ -450,7 +474,7 @@ def run_stub(args, rank, world):
         return time.perf_counter() - t0
 
     single = None
-    if world > 1:  # rank 0 alone, the others idle at the barrier (the real workload's `single_gpu_value`)
+    if world > 1 and args.full:  # rank 0 alone, the others idle at the barrier (the real workload's `single_gpu_value`)
         wdist.barrier()
         if rank == 0:
             single = float(n) * args.steps / max(loop(False), 1e-9)
@@ -460,7 +484,7 @@ def run_stub(args, rank, world):
     wdist.barrier()
     wall = wdist.max_over_ranks(wall, device)
     no_coll = None
-    if world > 1:
+    if world > 1 and args.full:
         wdist.barrier()
         w2 = loop(False)
         wdist.barrier()
@@ -796,6 +820,40 @@ def timed_steps(env, pool, steps, torch):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1), time.perf_counter() - t0
+
+
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: everything it writes, .npy headers included
+INFO_ARRAYS = ("remaining_budget", "at_budget", "location_index", "county_w", "year", "final_return", "t")
+
+
+def dump_outputs(env, out_dir, torch, np):
+    """--dump-outputs: what a caller of step() holds after the last timed step. step() returns the env's own buffers, so
+    they are read here: obs (when the run writes observations), reward, terminated, truncated, and the numeric entries of
+    the info mapping as info_<key>. Floating-point tensors are written as float32, booleans as 0 / 1 float32, integers as
+    float64 (exact). When every env would not fit in DUMP_MAX_BYTES, every array holds the same fixed, seeded sample of
+    env rows (a power of two of them, ascending); env_index.npy holds their indices either way."""
+    info = env._info()
+    arrays = {"obs": env._obs} if env.write_obs else {}
+    arrays.update(reward=env._reward, terminated=env._done_bool, truncated=env._truncated)
+    arrays.update((f"info_{k}", info[k]) for k in INFO_ARRAYS)
+
+    def host_dtype(t):
+        return np.float32 if (t.is_floating_point() or t.dtype == torch.bool) else np.float64
+
+    n = env.num_envs
+    row_bytes = 8 + sum(np.dtype(host_dtype(t)).itemsize * (t.numel() // n) for t in arrays.values())
+    budget = DUMP_MAX_BYTES - 1024 * (len(arrays) + 1)  # room for the headers
+    if n * row_bytes <= budget:
+        index, idx = np.arange(n), None
+    else:
+        k = 1 << (budget // row_bytes).bit_length() - 1
+        index = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        idx = torch.as_tensor(index, device=env.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "env_index.npy"), index.astype(np.float64))
+    for name, t in arrays.items():
+        t = t if idx is None else t.index_select(0, idx)
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy().astype(host_dtype(t)))
 
 
 def extras(out, args, torch, HeatAlertVecEnv, synth, tables, dt, ct, device, n, augment, pool, cb, T, wname_main=None):
@@ -1241,7 +1299,7 @@ def main():
     # ---- multi-GPU: the same workload on ONE GPU of this very job, before the headline (the other ranks wait idle at a
     # barrier, so rank 0 has its GPU, its PCIe link and the host to itself): the denominator of `weak_efficiency`
     single = None
-    if world > 1 and graph is None:
+    if world > 1 and graph is None and args.full:
         wdist.barrier()
         if rank == 0:
             use_gather = False
@@ -1269,9 +1327,11 @@ def main():
     # the form of the per-env state the step kernel streamed in the measured launches (read NOW: later read-backs of
     # the state bring the canonical words up to date)
     packed = all(packed_seen) if packed_seen else env.packed_state
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs, torch, np)
     # ---- multi-GPU: the same K steps once more WITHOUT the return all-gather: what the collective costs end to end
     no_coll = None
-    if world > 1:
+    if world > 1 and args.full:
         use_gather = False
         w2, _, _ = timed_region(segments=False)
         no_coll = wdist.max_over_ranks(w2, device)
@@ -1304,6 +1364,9 @@ def main():
             kernel_us = dev_ms * 1e3 / args.steps
             kernel_timing = (f"HIP events on the launch stream around the {args.steps} back-to-back step launches of the timed "
                              "region itself (no reset kernel, no collective inside)")
+    elif graph is None and not args.full:
+        kernel_timing = (f"HIP events around the whole timed region / {args.steps} steps (reset kernels and collectives "
+                         "included; --full times back-to-back step launches separately)")
     elif graph is None:
         k_steps = min(T - 2, 140)
         if env._host_auto and T - env._steps_in_episode <= k_steps:

@@ -96,19 +96,25 @@ def test_bench_launches_itself_for_several_ranks():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--workload", "launcher_stub", "--steps", "306", "--warmup", "0"],
-                       capture_output=True, text=True, env=env, timeout=170)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "launcher_stub",
+           "--steps", "306", "--warmup", "0"]
+    r = subprocess.run(cmd + ["--full"], capture_output=True, text=True, env=env, timeout=170)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["rccl_ranks_seen"] == 2 and out["gather_ok"] and out["stub"]
     assert out["steps"] == 306 and out["collective_ms"] is not None and out["scaling"] == "weak"
-    # a multi-rank line judges itself: the same workload on rank 0 alone, the same steps without the collective
-    for k in ("single_gpu_value", "weak_efficiency", "efficiency_vs_rank0_alone", "no_collective_value", "collective_overhead_frac"):
+    # with --full a multi-rank line judges itself: the same workload on rank 0 alone, the same steps without the collective
+    judge = ("single_gpu_value", "weak_efficiency", "efficiency_vs_rank0_alone", "no_collective_value", "collective_overhead_frac")
+    for k in judge:
         assert out[k] is not None, k
     assert out["single_gpu_value"] > 0 and out["weak_efficiency"] > 0 and out["collective_overhead_frac"] < 1
+    # a plain run times the headline only
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=170)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    plain = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert plain["gather_ok"] and plain["steps"] == 306 and all(plain[k] is None for k in judge)
     # a mismatching launcher environment is refused, not silently benchmarked on one rank
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "launcher_stub",
                           "--backend", "gloo"], capture_output=True, text=True, env=dict(env, WORLD_SIZE="1", RANK="0"),
@@ -128,7 +134,7 @@ def test_bench_launcher_eight_ranks_and_a_rank_that_dies_at_startup():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--workload",
-            "launcher_stub", "--steps", "306", "--warmup", "0", "--num-envs", "1024"]
+            "launcher_stub", "--steps", "306", "--warmup", "0", "--full", "--num-envs", "1024"]
     r = subprocess.run(base, capture_output=True, text=True, env=env, timeout=280)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -168,7 +174,7 @@ def test_bench_sweep_runs_every_gpu_count_as_its_own_job():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     base = [sys.executable, os.path.join(root, "bench.py"), "--backend", "gloo", "--workload", "launcher_stub", "--steps", "306",
-            "--warmup", "0", "--num-envs", "1024"]
+            "--warmup", "0", "--full", "--num-envs", "1024"]
     r = subprocess.run(base + ["--sweep", "1,2,4"], capture_output=True, text=True, env=env, timeout=200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -238,3 +244,40 @@ def test_rccl_first_contact_children_on_cpu(tmp_path):
     if not torch.cuda.is_available():
         assert r.returncode != 0 and "needs a ROCm GPU" in r.stderr
 
+
+
+def test_bench_dump_outputs_fits_its_budget(tmp_path):
+    """bench.py --dump-outputs on a stand-in for the env (its output buffers and info mapping on the CPU): every env while
+    they fit, above that the same fixed, seeded power-of-two sample of rows in every array, 64 MB in all at most."""
+    import importlib.util
+    import types
+
+    import numpy as np
+    import torch
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+
+    def fake_env(n):
+        g = torch.Generator().manual_seed(n)
+        info = {k: torch.randint(0, 3000, (n,), dtype=torch.int32, generator=g) for k in b.INFO_ARRAYS}
+        info["at_budget"], info["final_return"] = info["at_budget"] > 1500, torch.rand(n, generator=g)
+        return types.SimpleNamespace(num_envs=n, device=torch.device("cpu"), write_obs=True, _info=lambda: info,
+                                     _obs=torch.rand((n, 29), generator=g), _reward=torch.rand(n, generator=g),
+                                     _done_bool=torch.rand(n, generator=g) < 0.5, _truncated=torch.zeros(n, dtype=torch.bool))
+
+    for n in (1000, 1048576):
+        env, dirs = fake_env(n), [tmp_path / f"{n}_{i}" for i in range(2)]
+        for d in dirs:
+            b.dump_outputs(env, str(d), torch, np)
+        files = sorted(os.listdir(dirs[0]))
+        assert sum(os.path.getsize(dirs[0] / f) for f in files) <= 64_000_000 and len(files) == 12
+        a = {f: np.load(dirs[0] / f) for f in files}
+        assert all(np.array_equal(a[f], np.load(dirs[1] / f)) for f in files)  # the sample is fixed
+        idx = a["env_index.npy"].astype(np.int64)
+        assert len(idx) == (n if n == 1000 else 262144) and np.all(np.diff(idx) > 0) and idx[-1] < n
+        assert np.array_equal(a["obs.npy"], env._obs.numpy()[idx]) and a["obs.npy"].dtype == np.float32
+        assert np.array_equal(a["terminated.npy"], env._done_bool.numpy()[idx].astype(np.float32))
+        assert np.array_equal(a["info_t.npy"], env._info()["t"].numpy()[idx]) and a["info_t.npy"].dtype == np.float64

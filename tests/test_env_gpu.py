@@ -2422,14 +2422,15 @@ def test_randomised_parity_sweep(dev):
 
 
 def test_bench_json_contract_on_the_gpu(dev):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's invocation, here without the extras and the CPU
-    baseline leg): one JSON line with the contract's keys, the roofline object and physically possible numbers."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the driver's invocation with every check, here without the
+    extras and the CPU baseline leg): one JSON line with the contract's keys, the roofline object and physically possible
+    numbers."""
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -2465,8 +2466,8 @@ def test_bench_json_contract_on_the_gpu(dev):
     assert d["single_gpu_value"] is None and d["collective_overhead_frac"] is None  # multi-GPU self-judging keys: N > 1 only
     # ... and an rc of 0 means something: with one finished episode's return off by 0.01 (--tamper, a test hook) the line is
     # still printed, says parity_ok false where the driver's record keeps it, and the process exits 5
-    small = ["--num-envs", "262144", "--steps", "160", "--warmup", "5", "--no-extras", "--no-cpu-baseline", "--no-calibration",
-             "--no-live-traffic"]
+    small = ["--num-envs", "262144", "--steps", "160", "--warmup", "5", "--full", "--no-extras", "--no-cpu-baseline",
+             "--no-calibration", "--no-live-traffic"]
     for tamper, want_rc in (("return", 5), (None, 0)):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *small,
                             *(["--tamper", tamper] if tamper else [])], capture_output=True, text=True, timeout=600, cwd=root)
@@ -2474,3 +2475,51 @@ def test_bench_json_contract_on_the_gpu(dev):
         assert r.returncode == want_rc, (tamper, r.returncode, r.stderr[-1500:])
         assert d2["roofline"]["parity_ok"] is (tamper is None) and d2["config"]["parity_ok"] is (tamper is None)
         assert ("PARITY FAILED" in r.stderr) == (tamper is not None)
+
+
+def test_bench_plain_run_and_dump_outputs(dev, tmp_path):
+    """A plain `bench.py --gpus 1 --steps 20 --warmup 5` does nothing but the headline (no parity, calibration, counter
+    passes, extras or CPU baseline) and, with --dump-outputs, writes what step() returned after its last timed step: the
+    same bytes from two runs with the same arguments, at most 64 MB, a seeded sample of the envs at 1 048 576 of them and
+    every env of a small batch."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--dump-outputs", str(out), *extra], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    def load(out):
+        files = sorted(os.listdir(out))
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64_000_000
+        arrs = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        return arrs
+
+    d = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["metric"] == "env_steps_per_sec" and d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True
+    n = d["config"]["num_envs_total"]
+    assert n == 1048576 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["parity"] is None and "cpu_baseline" not in d and "always_alert_policy" not in d and d["status_bits"] == 0
+    assert d["roofline"]["copy_gbs_this_box"] is None and d["roofline"]["traffic_live"] is False
+    run(tmp_path / "b")
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert set(a) == {"env_index", "obs", "reward", "terminated", "truncated", "info_remaining_budget", "info_at_budget",
+                      "info_location_index", "info_county_w", "info_year", "info_final_return", "info_t"}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["env_index"]
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0) and idx[-1] < n and a["obs"].shape == (len(idx), 29)
+    assert all(len(v) == len(idx) for v in a.values()) and np.isfinite(a["obs"]).all() and np.isfinite(a["reward"]).all()
+    assert not a["terminated"].any() and not a["truncated"].any()  # day 25 of a 153-day episode
+    s = run(tmp_path / "s", "--num-envs", "4096")
+    c = load(tmp_path / "s")
+    assert s["config"]["num_envs_total"] == 4096 and np.array_equal(c["env_index"], np.arange(4096))
+    assert c["obs"].shape == (4096, 29) and c["info_year"].min() >= 2006

@@ -6,7 +6,7 @@ GPUs, and skip cleanly on the one-GPU pool. The pytest process -- which has init
     dist.ReturnGatherer(async_op=True) over backend nccl = RCCL; rank 0 saves the gathered returns of every episode
   * tools/rccl_first_contact.py --single 2          ONE process, the same 131 072 global ids
   -> the two files must be equal bit for bit (shard invariance through the real collective) and the group must have had 2 ranks
-  * bench.py --gpus 2 --steps 20 --warmup 5         a line with n_gpus 2, rccl_ranks_seen 2 and weak_efficiency
+  * bench.py --gpus 2 --steps 20 --warmup 5 --full  a line with n_gpus 2, rccl_ranks_seen 2 and weak_efficiency
 
 The same children run on ONE GPU with --backend gloo (both ranks share the card, the collective is staged through the host):
 that rehearsal is part of the suite on every box; without any GPU (--stub) it is tests/test_dist_cpu.py. The reference has
@@ -62,8 +62,8 @@ def test_two_rccl_ranks_equal_one_process(tmp_path):
 def test_bench_on_two_gpus_reports_weak_efficiency():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-extras",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1100, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full",
+                        "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1100, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["rccl_ranks_seen"] == 2 and d["config"]["num_envs_total"] == 2 * 1048576

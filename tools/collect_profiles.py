@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Copy the judged rocprof evidence from gpurun_out/ (scratch) into profiles/<round>/ (tracked):
+"""Copy the judged rocprof evidence from tools/gpu_session.sh's output folder (scratch: $W2A_SESSION_OUT, default
+session_out/) into profiles/<round>/ (tracked):
 trimmed kernel-stats CSV of `rocprofv3 --kernel-trace --stats -- python3 bench.py ...`, per-kernel PMC means of the
 tools/pmc_probe.py passes, the in-process calibration of FETCH_SIZE / WRITE_SIZE on kernels of known byte counts, and
 profiles/traffic_latest.json, which bench.py reports as roofline.traffic when the kernel sources still hash to the
@@ -16,7 +17,7 @@ import shutil
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GO = os.path.join(ROOT, "gpurun_out")
+GO = os.path.join(ROOT, os.environ.get("W2A_SESSION_OUT", "session_out"))  # where tools/gpu_session.sh wrote
 GIB = float(1 << 30)
 KEEP = ("k_step", "k_reset", "k_posterior", "k_pm_", "k_rollout", "k_group", "copyBuffer", "FillFunctor")
 
@@ -44,7 +45,7 @@ def collect(tag, out, rnd):
     # 2. PMC passes (tools/pmc_probe.py): per-kernel means
     # Every pass records the hash of the kernel sources it ran on (<pass>_<tag>.probe.json, written next to its
     # summary by tools/gpu_session.sh). Passes are merged only when they ran on the SAME sources as the newest one:
-    # a summary left in gpurun_out/ by an older build would otherwise smuggle kernels that no longer exist into
+    # a summary left in the session folder by an older build would otherwise smuggle kernels that no longer exist into
     # pmc_<tag>.json.
     probe = {}
     pj = os.path.join(GO, f"pmc_probe_{tag}.json")
@@ -116,7 +117,7 @@ def main():
     logs = ["toolchain.txt", "pm_i8_variants.log", "bench.log", "pytest_gpu.log", "smoke.log", "exp_step_kernels.log", "ab_step64.log", "ab2.log", "nsweep.log",
             "bench_rollout.log", "bench_configs1.log", "bench_configs3.log", "bench_gloo2.log", "pm_trace.log",
             "pm_variants.log", "pm_tests_matrix.log", "pm_rollout.log", "mfma_overlap_probe.log"]
-    # gpurun_out/ is scratch that survives rounds: only logs written after the newest file of the other rounds'
+    # the session folder is scratch that survives rounds: only logs written after the newest file of the other rounds'
     # directories belong to this one
     older = [os.path.getmtime(f) for d in glob.glob(os.path.join(ROOT, "profiles", "r*")) if os.path.abspath(d) != os.path.abspath(out)
              for f in glob.glob(os.path.join(d, "*"))]

@@ -55,11 +55,12 @@ import json  # noqa: E402
 
 from weather2alert_amd import build as wbuild  # noqa: E402
 
-os.makedirs("gpurun_out", exist_ok=True)
+out_dir = os.environ.get("W2A_SESSION_OUT", "session_out")  # tools/gpu_session.sh's output folder
+os.makedirs(out_dir, exist_ok=True)
 tag = (a.workload + ("_noobs" if a.no_obs else "") + ("_sorted" if a.episode_order == "sorted" else "")
        + (("_pm_" + a.pm_kernel) if a.reward_mode == "posterior_mean" else ""))
 json.dump({"workload": tag, "src_sha": wbuild.source_sha(), "num_envs": n, "steps": a.steps,
            "step_kernel": env_kernel},
-          open(f"gpurun_out/pmc_probe_{tag}.json", "w"))
+          open(os.path.join(out_dir, f"pmc_probe_{tag}.json"), "w"))
 print("probe done", desc, "steps", a.steps)
 env.close()
