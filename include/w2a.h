@@ -314,6 +314,36 @@ typedef struct w2a_policy {
 int w2a_rollout(w2a_env *env, const w2a_policy *policy, int32_t n_steps, float *ret_out, int32_t *alerts_out,
                 int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words,
                 float *last_return, float *ret_snapshot, void *stream);
+/* w2a_rollout with a linear-logistic policy that has one parameter row per group of envs (policy search: many candidate
+ * parameter vectors, each scored on the envs of its group). Env i acts on
+ *     logit = weight[g] . obs_i + bias[g],   g = group[i],
+ * where obs_i is exactly the row w2a_step would have returned to the agent before that decision: the lagging
+ * observation with the faithful run-time columns (alert_lag1, the pre-update alert_streak,
+ * remaining_budget, alert_2wks). The logit is accumulated in fp64 over the f32 inputs and parameters: bias first, then
+ * the observation columns in slot order. sample = 0: alert iff logit > 0; sample = 1: alert iff u < sigmoid(logit),
+ * u the BERNOULLI policy's uniform of (seed, global env id, episode number, day). require_budget as in w2a_policy.
+ *   weight  device f32 [n_groups][32], 16-B aligned, in SLOT order: observation column j's coefficient at
+ *           slot obs_slot[j] of w2a_tables; the other slots are ignored
+ *   bias    device f32 [n_groups]
+ *   group   device i32 [num_envs] in [0, n_groups) (NULL = group 0 for every env); the caller checks the range --
+ *           the kernel clamps ids into it and never reads outside weight / bias
+ * obs (device f32 [num_envs][n_obs], in/out) is the observation buffer of w2a_reset / w2a_step: on entry it must hold
+ * the row every env's agent holds (the first day's input -- the state alone cannot rebuild it); on return it holds the
+ * row each env holds after this call (a terminal day leaves the previous row, like w2a_step), so calls chain with each
+ * other and with w2a_step. n_steps, outputs and lock-step bookkeeping are those of w2a_rollout (no in-call autoreset).
+ * Refused (W2A_ERR_ARG) on a handle with corrected-semantics flags (they change what the observation is). */
+typedef struct w2a_linear_policy {
+  const float *weight;
+  const float *bias;
+  const int32_t *group;
+  int32_t n_groups;
+  int32_t sample;         /* 0 or 1 */
+  int32_t require_budget; /* 0 or 1 */
+  uint64_t seed;          /* sample = 1 only */
+} w2a_linear_policy;
+int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an
@@ -370,7 +400,8 @@ int w2a_get_state(w2a_env *env, const w2a_state_view *view, void *stream);
 enum { W2A_Q_LOCKSTEP = 6,           /* 1: every env is known to be on the same day of an episode of the one length there is */
        W2A_Q_LOCKSTEP_DAY = 0, W2A_Q_PACKED_ELIGIBLE = 1, W2A_Q_PACKED_CURRENT = 2, W2A_Q_CANONICAL_CURRENT = 3,
        W2A_Q_LAST_ROLLOUT_KERNEL = 4 /* what the last w2a_rollout launched: -1 none yet, 0 k_rollout (4 lanes per env),
-                                        1 k_rollout64 (lane = env), 2 k_rollout_mfma (int8 matrix cores) */,
+                                        1 k_rollout64 (lane = env), 2 k_rollout_mfma (int8 matrix cores); 3 after
+                                        w2a_rollout_linear: k_rollout_linear (lane = env) */,
        W2A_Q_LAST_STEP_KERNEL = 5    /* what the last w2a_step launched: -1 none yet, 0 k_step (4 lanes per env),
                                         1 k_step64 on the canonical state words, 2 k_step64 on the lock-step mirror */ };
 int w2a_query(w2a_env *env, int what);

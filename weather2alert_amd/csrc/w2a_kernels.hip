@@ -43,6 +43,7 @@
 #include "w2a_posterior_i8.hip.h"
 #include "w2a_reset.hip.h"
 #include "w2a_rollout.hip.h"
+#include "w2a_rollout_linear.hip.h"
 #include "w2a_rollout_i8.hip.h"
 #include "w2a_rollout_mfma.hip.h"
 #include "w2a_sort.hip.h"
@@ -808,6 +809,77 @@ int w2a_rollout(w2a_env *env, const w2a_policy *policy, int32_t n_steps, float *
     return W2A_OK;
   }
   launch_rollout(policy->kind, alert_mask || attempt_mask || ret_snapshot, env->tb.fixes != 0, grid_for(env->n), s, a);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// what W2A_Q_LAST_ROLLOUT_KERNEL reports after w2a_rollout_linear (the built-in kernels' values come from
+// w2a_bookkeeping.h: bk_rollout_kernel)
+#define W2A_ROLLOUT_KERNEL_LINEAR 3
+
+int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine)
+  if (!policy) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL policy");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_linear: n_steps must be positive");
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL weight or bias");
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_linear: n_groups must be positive");
+  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "w2a_rollout_linear: sample must be 0 or 1");
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "w2a_rollout_linear: require_budget must be 0 or 1");
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "w2a_rollout_linear: weight must be 16-B aligned");
+  if (!obs) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL obs (the rows the agent holds are the first day's input)");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL handle");
+  if ((alert_mask || attempt_mask) && mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_rollout_linear: alert_mask / attempt_mask need ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_rollout_linear: not available with corrected-semantics flags (they change what the "
+                             "observation is)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_rollout_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  REFUSE_WHILE_CAPTURING("w2a_rollout_linear", stream);
+  LinearRolloutArgs la;
+  memset(&la, 0, sizeof(la));
+  // every observation column must sit on a slot the day loop multiplies (0..RO64_SLOTS-1): then slot 31, which carries
+  // the bias, is provably none of them
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_rollout_linear: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    la.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = la.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.pol.seed = policy->seed;
+  a.n_steps = n_steps; a.ret_out = ret_out; a.alerts_out = alerts_out; a.attempts_over_budget = attempts_over_budget;
+  a.alert_mask = alert_mask; a.attempt_mask = attempt_mask; a.mask_words = mask_words; a.last_return = last_return;
+  a.ret_snapshot = ret_snapshot;
+  a.order = env->order;
+  la.weight = reinterpret_cast<const float4 *>(policy->weight);
+  la.bias = policy->bias;
+  la.group = policy->group;
+  la.n_groups = policy->n_groups;
+  la.n_obs = env->tb.n_obs;
+  la.obs_mask = obs_mask;
+  la.obs = obs;
+  hipStream_t s = (hipStream_t)stream;
+  HipDev dv{env, s};
+  (void)bk_rollout_begin(env->bk, dv, n_steps);  // same lock-step bookkeeping as w2a_rollout
+  env->bk.last_rollout_kernel = W2A_ROLLOUT_KERNEL_LINEAR;
+  if (alert_mask) HIP_TRY(hipMemsetAsync(alert_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
+  if (attempt_mask) HIP_TRY(hipMemsetAsync(attempt_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  const bool masks = alert_mask || attempt_mask || ret_snapshot;
+  if (masks && policy->sample) hipLaunchKernelGGL((k_rollout_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, la);
+  else if (masks) hipLaunchKernelGGL((k_rollout_linear<true, false>), dim3(g64), dim3(BLOCK), 0, s, la);
+  else if (policy->sample) hipLaunchKernelGGL((k_rollout_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, la);
+  else hipLaunchKernelGGL((k_rollout_linear<false, false>), dim3(g64), dim3(BLOCK), 0, s, la);
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;

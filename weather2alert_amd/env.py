@@ -17,7 +17,7 @@ from typing import Literal
 import numpy as np
 import torch
 
-from . import _ffi, stats as _stats
+from . import _ffi, policy as _policy, stats as _stats
 from .info import _LazyInfo
 from .options import KernelOptions
 from .rng import numpy_parity_episode
@@ -272,6 +272,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         self._sticky = [budget] * n  # host mirror of self.budget per env (numpy_parity mode, Q9)
         self._needs_reset = True
+        # the observation buffer holds the row every env's agent holds (rollout(kind="linear") reads it on its first day):
+        # after reset(), step() and linear rollouts that wrote it; not after built-in rollouts (they write no rows)
+        self._obs_current = False
         self._last_opts: dict = {}
         self._np_random = None
         self._np_random_seed = None
@@ -352,9 +355,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
     @property
     def last_rollout_kernel(self) -> str | None:
         """Which kernel the last sampled-reward rollout() launched: "k_rollout_mfma" (int8 matrix cores), "k_rollout64"
-        (lane = env, vector ALU), "k_rollout" (4 lanes per env) or None before the first one."""
-        return {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma"}.get(
-            self._lib.w2a_query(self._h, _ffi.Q_LAST_ROLLOUT_KERNEL))
+        (lane = env, vector ALU), "k_rollout" (4 lanes per env), "k_rollout_linear" (kind="linear") or None before the
+        first one."""
+        return _ffi.ROLLOUT_KERNELS.get(self._lib.w2a_query(self._h, _ffi.Q_LAST_ROLLOUT_KERNEL))
 
     def _stream(self):
         if self._raw_stream is not None:
@@ -460,6 +463,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                  f"{self.num_envs} envs: not a checkpoint of this env batch")
             self._state[:canon].copy_(src[:canon])
         self._state[:256].copy_(hdr)
+        self._obs_current = False  # which row each agent held is not part of the checkpoint's guarantees
         # the state buffer changed behind the library: it forgets what it derived and scans the restored buffer for its
         # largest budget, sticky ones included (waits for this stream -- the one the copy above ran on -- and no other)
         with torch.cuda.device(self.device):
@@ -521,6 +525,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         else:
             self._reset_device(seed, options, mask_t, obs_ptr)
         self._needs_reset = False
+        if mask is None:  # a masked reset leaves the other envs' rows as they were
+            self._obs_current = self.write_obs
         return self._obs, self._info()
 
     def _reset_tuples(self, ep: dict, mask_t, obs_ptr):
@@ -656,6 +662,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
                     _ffi.check(lib.w2a_observe(self._h, obs_ptr, st), "w2a_observe")
         self._steps_in_episode = 0
         self._pending_reset = False
+        if mask_t is None:
+            self._obs_current = obs_ptr is not None
         self._regroup()
 
     def _regroup(self):
@@ -738,6 +746,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if rc != 0:
             _ffi.check(rc, "w2a_step")
         self._keep_act = actions
+        self._obs_current = self.write_obs
         done = self._done_bool
         if self._host_auto:  # lock step: the host counts days and launches the reset after the terminal step
             self._steps_in_episode += 1
@@ -775,8 +784,19 @@ class HeatAlertVecEnv(_VectorEnvBase):
         policy: {"kind": "never" | "always"} |
                 {"kind": "bernoulli", "p": 0.1, "seed": 0} |
                 {"kind": "threshold", "feature": "heat_qi", "threshold": 0.9, "lag": 1} |
-                {"kind": "table", "table": uint8 [T, R]}   (action = table[day][min(remaining_budget, R-1)])
+                {"kind": "table", "table": uint8 [T, R]}   (action = table[day][min(remaining_budget, R-1)]) |
+                {"kind": "linear", "weight": f32 [G, n_obs], "bias": f32 [G], "group": int [num_envs] (may be
+                 omitted when G == 1), "sample": False, "seed": 0}   (weather2alert_amd/policy.py)
                 plus optional "require_budget": True (never attempt an alert with no budget left).
+        The linear policy acts on logit = weight[g] . obs + bias[g] (fp64 over the f32 values) for the env's group g,
+        where obs is exactly the row step() would have returned before that decision -- so rollout(linear, k) is
+        indistinguishable from k iterations of `a = policy(obs); obs = env.step(a)`, observation buffer included.
+        sample=False alerts iff logit > 0, sample=True iff u < sigmoid(logit) with the bernoulli policy's uniform u.
+        It reads the observation buffer on its first day and writes the final rows back (k_rollout_linear), so it needs
+        that buffer current: after reset(), step() or a linear rollout with write_obs=True -- not after a built-in
+        rollout that did not end in a whole-batch reset, nor after load_state_dict (RuntimeError). Faithful semantics
+        only (fixes other than "budget" change what the observation is) and reward_mode="sampled" (ValueError). Its
+        result also holds "group_mean_return" f32 [G]: the mean "return" of each group's envs.
         The threshold policy sees the lagging observation the reference's agent would see (Q6; lag=0 reads
         today's row instead). Returns device tensors: "return" (rewards summed over the days run), "alerts",
         "attempts_over_budget", "final_return" (episode return of envs that finished), "done", and with
@@ -784,12 +804,26 @@ class HeatAlertVecEnv(_VectorEnvBase):
         reset, so consecutive calls evaluate consecutive episodes."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
-        if self._pending_reset:  # next_step autoreset in lock step: the finished batch restarts before anything runs
-            self._launch_device_reset(None, self._obs_ptr)
         ct = self.ct
         kind = policy.get("kind")
-        if kind not in _ffi.POLICY_KINDS:
+        lin = None
+        if kind == "linear":  # every argument is checked before anything runs
+            if self._pm:
+                raise ValueError("rollout(kind='linear') needs reward_mode='sampled'")
+            if self.fixes - {"budget"}:
+                raise ValueError(f"rollout(kind='linear') needs faithful observations; fixes {sorted(self.fixes - {'budget'})} "
+                                 "change what the observation is")
+            lin = _policy.check_linear_policy(policy, ct.n_obs, self.num_envs, ct.obs_slot, self.device)
+        elif kind not in _ffi.POLICY_KINDS:
             raise ValueError(f"policy kind {kind!r}")
+        if self._pending_reset:  # next_step autoreset in lock step: the finished batch restarts before anything runs
+            self._launch_device_reset(None, self._obs_ptr)
+        if lin is not None and not self._obs_current:
+            raise RuntimeError("rollout(kind='linear') reads the observation buffer, which does not hold the agents' "
+                               "current rows (write_obs=False, a built-in rollout or load_state_dict since the last "
+                               "step()/reset()): call step() or reset() first")
+        if lin is not None:
+            return self._rollout_linear(lin, n_steps, alert_mask)
         p = _ffi.Policy()
         p.kind = _ffi.POLICY_KINDS[kind]
         p.p = float(policy.get("p", 0.0))
@@ -807,6 +841,22 @@ class HeatAlertVecEnv(_VectorEnvBase):
             if keep.dim() != 2 or keep.shape[0] < ct.T:
                 raise ValueError(f"policy table must be [T >= {ct.T}, R]")
             p.table, p.table_R = keep.data_ptr(), int(keep.shape[1])
+        return self._rollout_run(p, None, n_steps, alert_mask, keep)
+
+    def _rollout_linear(self, lin, n_steps, alert_mask) -> dict:
+        """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
+        lp = _ffi.LinearPolicy()
+        lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
+        lp.group = None if lin.group is None else lin.group.data_ptr()
+        lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
+        out = self._rollout_run(None, lp, n_steps, alert_mask, lin)
+        out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
+        return out
+
+    def _rollout_run(self, p, lp, n_steps, alert_mask, keep) -> dict:
+        """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
+        linear (lp, w2a_rollout_linear)."""
+        ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
         out = {"return": torch.empty(n, dtype=torch.float32, device=dev),
@@ -834,7 +884,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
                             n, ct.S_w * ct.Y, ct.S, ct.n_samples), dtype=torch.uint8, device=dev)
                     _ffi.check(self._lib.w2a_rollout_mfma_prepare(self._h, self._mfma_ws.data_ptr(), self._mfma_ws.numel(),
                                                                   self._stream()), "w2a_rollout_mfma_prepare")
-            if self._pm:
+            if lp is not None:
+                _ffi.check(self._lib.w2a_rollout_linear(self._h, C.byref(lp), steps, self._obs.data_ptr(),
+                                                        out["return"].data_ptr(), out["alerts"].data_ptr(),
+                                                        out["attempts_over_budget"].data_ptr(),
+                                                        None if mask is None else mask.data_ptr(),
+                                                        None if amask is None else amask.data_ptr(), words, self._fr_ptr,
+                                                        None if snap is None else snap.data_ptr(), self._stream()),
+                           "w2a_rollout_linear")
+            elif self._pm:
                 steps = self._rollout_posterior_mean(p, steps, out, mask, amask, words, snap, st0)
             else:
                 _ffi.check(self._lib.w2a_rollout(self._h, C.byref(p), steps, out["return"].data_ptr(),
@@ -843,6 +901,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                  None if amask is None else amask.data_ptr(), words, self._fr_ptr,
                                                  None if snap is None else snap.data_ptr(), self._stream()), "w2a_rollout")
         self._keep_pol = keep
+        self._obs_current = lp is not None  # built-in policies write no observation rows (a reset below may)
         # only what this call returns is decoded (sixteen arrays of N int32 otherwise: 64 MB of writes at 1 M envs)
         st = self.state() if mask is not None else self._state_packed(("finished",))[1]
         out["done"] = st["finished"].bool()  # the terminal step has run (t stops at n_days-1 before AND after it)
