@@ -344,6 +344,48 @@ typedef struct w2a_linear_policy {
 int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                        int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                        int32_t mask_words, float *last_return, float *ret_snapshot, void *stream);
+/* w2a_rollout_linear with a small multilayer perceptron instead of the linear logit, one parameter block per group:
+ *     h1 = act(W1 . obs_i + b1),  [h2 = act(W2 . h1 + b2),]  logit = w_out . h_last + b_out,   g = group[i],
+ * on the same faithful observation row obs_i, with the same decisions (sample = 0: alert iff logit > 0; sample = 1:
+ * alert iff u < sigmoid(logit), the same uniform u), require_budget, obs buffer, outputs and bookkeeping.
+ * Numerics: parameters and activations are f32; every layer's pre-activation is an f32 sum of f32 products, bias
+ * first; tanh (within ~2e-7 absolute of the exact value over all f32) and ReLU in f32; the logit is f32. A decision
+ * can therefore differ from an fp64 evaluation of the same network only at a near-tie: |logit| <= 1e-4 (|b_out| +
+ * sum_h |w_out,h h_h|), or with sample = 1, |sigmoid(logit) - u| <= 1e-5. An env's result does not depend on which
+ * other envs share its wave, on the group layout or on the visiting order (bit for bit).
+ *   params  device f32, 16-B aligned: n_groups blocks of W2A_MLP_STRIDE(width, n_layers) floats, each
+ *             W1[32][width]     row obs_slot[j] (w2a_tables) holds observation column j; rows of other slots are zero
+ *             b1[width]
+ *             W2[width][width]  b2[width]   (n_layers == 2 only; W2[k][u]: input unit k, output unit u)
+ *             w_out[width]
+ *             b_out, 0, 0, 0
+ *           every part zero-padded to width (units past a layer's real width have zero weights and bias); a two-row
+ *           output (SB3's two action values) is folded by the caller into w_out = row1 - row0, b_out = b1 - b0
+ *   group   device i32 [num_envs] in [0, n_groups) (NULL = group 0 for every env); the kernel clamps, never reads
+ *           outside params
+ *   order   device i32 [num_envs], a permutation of the env ids: the visiting order (NULL = the handle's rollout
+ *           order, or identity). Speed only: a stable sort by group puts each group's envs in whole waves.
+ *   width   padded hidden width of every hidden layer: 16, 32 or 64;  n_layers: 1 or 2 hidden layers
+ *   activation  W2A_MLP_TANH or W2A_MLP_RELU, after every hidden layer (none after the output)
+ * Refused (W2A_ERR_ARG) where w2a_rollout_linear is, and for a bad width, n_layers, activation, sample or alignment. */
+enum { W2A_MLP_TANH = 0, W2A_MLP_RELU = 1 };
+#define W2A_MLP_STRIDE(width, n_layers) \
+  (W2A_ROW_FLOATS * (width) + (width) + ((n_layers) == 2 ? (width) * (width) + (width) : 0) + (width) + 4)
+typedef struct w2a_mlp_policy {
+  const float *params;
+  const int32_t *group;
+  const int32_t *order;
+  int32_t n_groups;
+  int32_t n_layers;       /* 1 or 2 */
+  int32_t width;          /* 16, 32 or 64 */
+  int32_t activation;     /* W2A_MLP_TANH 0 or W2A_MLP_RELU 1 */
+  int32_t sample;         /* 0 or 1 */
+  int32_t require_budget; /* 0 or 1 */
+  uint64_t seed;          /* sample = 1 only */
+} w2a_mlp_policy;
+int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                    int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                    int32_t mask_words, float *last_return, float *ret_snapshot, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an
@@ -401,7 +443,8 @@ enum { W2A_Q_LOCKSTEP = 6,           /* 1: every env is known to be on the same 
        W2A_Q_LOCKSTEP_DAY = 0, W2A_Q_PACKED_ELIGIBLE = 1, W2A_Q_PACKED_CURRENT = 2, W2A_Q_CANONICAL_CURRENT = 3,
        W2A_Q_LAST_ROLLOUT_KERNEL = 4 /* what the last w2a_rollout launched: -1 none yet, 0 k_rollout (4 lanes per env),
                                         1 k_rollout64 (lane = env), 2 k_rollout_mfma (int8 matrix cores); 3 after
-                                        w2a_rollout_linear: k_rollout_linear (lane = env) */,
+                                        w2a_rollout_linear: k_rollout_linear (lane = env); 4 after
+                                        w2a_rollout_mlp: k_rollout_mlp (lane = env, f32 matrix cores) */,
        W2A_Q_LAST_STEP_KERNEL = 5    /* what the last w2a_step launched: -1 none yet, 0 k_step (4 lanes per env),
                                         1 k_step64 on the canonical state words, 2 k_step64 on the lock-step mirror */ };
 int w2a_query(w2a_env *env, int what);

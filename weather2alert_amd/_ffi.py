@@ -23,10 +23,10 @@ SYMBOLS = [
     "w2a_reset_device_rng", "w2a_set_autoreset", "w2a_step", "w2a_get_state", "w2a_read_status",
     "w2a_sort_workspace_bytes", "w2a_sort_episodes", "w2a_reset_device_rng_sorted", "w2a_observe", "w2a_rollout", "w2a_rollout_order_workspace_bytes", "w2a_rollout_order_attach", "w2a_rollout_order", "w2a_rollout_posterior_mean", "w2a_policy_actions", "w2a_set_semantics",
     "w2a_group_workspace_bytes", "w2a_group_by_column", "w2a_posterior_mean_reward", "w2a_set_posterior_kernel", "w2a_invalidate", "w2a_query", "w2a_rollout_mfma_workspace_bytes", "w2a_rollout_mfma_prepare",
-    "w2a_rollout_linear",
+    "w2a_rollout_linear", "w2a_rollout_mlp",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
-ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear"}  # W2A_Q_LAST_ROLLOUT_KERNEL
+ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
 PM_KERNELS = {"vector": 0, "matrix": 1, "matrix_i8": 2}  # W2A_PM_VECTOR, W2A_PM_MATRIX_F64, W2A_PM_MATRIX_I8
 POLICY_KINDS = {"never": 0, "always": 1, "bernoulli": 2, "threshold": 3, "table": 4}
 
@@ -40,6 +40,15 @@ class Policy(C.Structure):
 class LinearPolicy(C.Structure):
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("group", C.c_void_p), ("n_groups", C.c_int32),
                 ("sample", C.c_int32), ("require_budget", C.c_int32), ("seed", C.c_uint64)]
+
+
+class MlpPolicy(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("group", C.c_void_p), ("order", C.c_void_p), ("n_groups", C.c_int32),
+                ("n_layers", C.c_int32), ("width", C.c_int32), ("activation", C.c_int32), ("sample", C.c_int32),
+                ("require_budget", C.c_int32), ("seed", C.c_uint64)]
+
+
+MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}  # W2A_MLP_TANH, W2A_MLP_RELU
 
 
 class Tables(C.Structure):
@@ -151,6 +160,8 @@ def load(build_if_missing: bool = True):
     lib.w2a_rollout_posterior_mean.argtypes = [vp, C.POINTER(Policy), i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.w2a_rollout_linear.restype = C.c_int
     lib.w2a_rollout_linear.argtypes = [vp, C.POINTER(LinearPolicy), i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.w2a_rollout_mlp.restype = C.c_int
+    lib.w2a_rollout_mlp.argtypes = [vp, C.POINTER(MlpPolicy), i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     if lib.w2a_abi_version() != ABI_VERSION:

@@ -44,6 +44,7 @@
 #include "w2a_reset.hip.h"
 #include "w2a_rollout.hip.h"
 #include "w2a_rollout_linear.hip.h"
+#include "w2a_rollout_mlp.hip.h"
 #include "w2a_rollout_i8.hip.h"
 #include "w2a_rollout_mfma.hip.h"
 #include "w2a_sort.hip.h"
@@ -880,6 +881,88 @@ int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_
   else if (masks) hipLaunchKernelGGL((k_rollout_linear<true, false>), dim3(g64), dim3(BLOCK), 0, s, la);
   else if (policy->sample) hipLaunchKernelGGL((k_rollout_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, la);
   else hipLaunchKernelGGL((k_rollout_linear<false, false>), dim3(g64), dim3(BLOCK), 0, s, la);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// what W2A_Q_LAST_ROLLOUT_KERNEL reports after w2a_rollout_mlp
+#define W2A_ROLLOUT_KERNEL_MLP 4
+
+int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                    int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                    int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine)
+  if (!policy) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL policy");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_steps must be positive");
+  if (!policy->params) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL params");
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_groups must be positive");
+  if (policy->n_layers != 1 && policy->n_layers != 2) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_layers must be 1 or 2");
+  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: width must be 16, 32 or 64");
+  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
+  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: sample must be 0 or 1");
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: require_budget must be 0 or 1");
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: params must be 16-B aligned");
+  if (!obs) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL obs (the rows the agent holds are the first day's input)");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL handle");
+  if ((alert_mask || attempt_mask) && mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: alert_mask / attempt_mask need ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: not available with corrected-semantics flags (they change what the "
+                             "observation is)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
+  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_groups * block size must stay below 2^31 floats");
+  REFUSE_WHILE_CAPTURING("w2a_rollout_mlp", stream);
+  MlpRolloutArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_rollout_mlp: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    ma.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = ma.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.pol.seed = policy->seed;
+  a.n_steps = n_steps; a.ret_out = ret_out; a.alerts_out = alerts_out; a.attempts_over_budget = attempts_over_budget;
+  a.alert_mask = alert_mask; a.attempt_mask = attempt_mask; a.mask_words = mask_words; a.last_return = last_return;
+  a.ret_snapshot = ret_snapshot;
+  a.order = policy->order ? reinterpret_cast<const uint32_t *>(policy->order) : env->order;
+  ma.params = policy->params;
+  ma.group = policy->group;
+  ma.n_groups = policy->n_groups;
+  ma.stride = (int32_t)stride;
+  ma.activation = policy->activation;
+  ma.n_obs = env->tb.n_obs;
+  ma.obs_mask = obs_mask;
+  ma.obs = obs;
+  hipStream_t s = (hipStream_t)stream;
+  HipDev dv{env, s};
+  (void)bk_rollout_begin(env->bk, dv, n_steps);  // same lock-step bookkeeping as w2a_rollout
+  env->bk.last_rollout_kernel = W2A_ROLLOUT_KERNEL_MLP;
+  if (alert_mask) HIP_TRY(hipMemsetAsync(alert_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
+  if (attempt_mask) HIP_TRY(hipMemsetAsync(attempt_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  const bool masks = alert_mask || attempt_mask || ret_snapshot;
+  const int32_t smp = policy->sample;
+  switch (policy->width * 4 + policy->n_layers) {
+    case 16 * 4 + 1: launch_rollout_mlp<16, 1>(ma, masks, smp, g64, s); break;
+    case 16 * 4 + 2: launch_rollout_mlp<16, 2>(ma, masks, smp, g64, s); break;
+    case 32 * 4 + 1: launch_rollout_mlp<32, 1>(ma, masks, smp, g64, s); break;
+    case 32 * 4 + 2: launch_rollout_mlp<32, 2>(ma, masks, smp, g64, s); break;
+    case 64 * 4 + 1: launch_rollout_mlp<64, 1>(ma, masks, smp, g64, s); break;
+    default: launch_rollout_mlp<64, 2>(ma, masks, smp, g64, s); break;
+  }
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;

@@ -355,8 +355,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
     @property
     def last_rollout_kernel(self) -> str | None:
         """Which kernel the last sampled-reward rollout() launched: "k_rollout_mfma" (int8 matrix cores), "k_rollout64"
-        (lane = env, vector ALU), "k_rollout" (4 lanes per env), "k_rollout_linear" (kind="linear") or None before the
-        first one."""
+        (lane = env, vector ALU), "k_rollout" (4 lanes per env), "k_rollout_linear" (kind="linear"), "k_rollout_mlp"
+        (kind="mlp") or None before the first one."""
         return _ffi.ROLLOUT_KERNELS.get(self._lib.w2a_query(self._h, _ffi.Q_LAST_ROLLOUT_KERNEL))
 
     def _stream(self):
@@ -786,7 +786,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 {"kind": "threshold", "feature": "heat_qi", "threshold": 0.9, "lag": 1} |
                 {"kind": "table", "table": uint8 [T, R]}   (action = table[day][min(remaining_budget, R-1)]) |
                 {"kind": "linear", "weight": f32 [G, n_obs], "bias": f32 [G], "group": int [num_envs] (may be
-                 omitted when G == 1), "sample": False, "seed": 0}   (weather2alert_amd/policy.py)
+                 omitted when G == 1), "sample": False, "seed": 0}   (weather2alert_amd/policy.py) |
+                {"kind": "mlp", "layers": [(W1, b1), [(W2, b2),] (Wo, bo)] (torch Linear convention, optionally with
+                 a leading G dim), "activation": "tanh" | "relu", "group", "order", "sample", "seed"}
                 plus optional "require_budget": True (never attempt an alert with no budget left).
         The linear policy acts on logit = weight[g] . obs + bias[g] (fp64 over the f32 values) for the env's group g,
         where obs is exactly the row step() would have returned before that decision -- so rollout(linear, k) is
@@ -797,6 +799,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
         rollout that did not end in a whole-batch reset, nor after load_state_dict (RuntimeError). Faithful semantics
         only (fixes other than "budget" change what the observation is) and reward_mode="sampled" (ValueError). Its
         result also holds "group_mean_return" f32 [G]: the mean "return" of each group's envs.
+        The mlp policy is the same with an f32 network of 1-2 hidden layers (width <= 64) in place of the linear logit
+        (k_rollout_mlp, f32 matrix cores; a two-row output is SB3's two action values, logit = row1 - row0); its
+        decisions can differ from an fp64 evaluation only at near-ties (include/w2a.h). policy.mlp_from_module turns a
+        torch Sequential into such a dict.
         The threshold policy sees the lagging observation the reference's agent would see (Q6; lag=0 reads
         today's row instead). Returns device tensors: "return" (rewards summed over the days run), "alerts",
         "attempts_over_budget", "final_return" (episode return of envs that finished), "done", and with
@@ -807,21 +813,24 @@ class HeatAlertVecEnv(_VectorEnvBase):
         ct = self.ct
         kind = policy.get("kind")
         lin = None
-        if kind == "linear":  # every argument is checked before anything runs
+        if kind in ("linear", "mlp"):  # every argument is checked before anything runs
             if self._pm:
-                raise ValueError("rollout(kind='linear') needs reward_mode='sampled'")
+                raise ValueError(f"rollout(kind={kind!r}) needs reward_mode='sampled'")
             if self.fixes - {"budget"}:
-                raise ValueError(f"rollout(kind='linear') needs faithful observations; fixes {sorted(self.fixes - {'budget'})} "
+                raise ValueError(f"rollout(kind={kind!r}) needs faithful observations; fixes {sorted(self.fixes - {'budget'})} "
                                  "change what the observation is")
-            lin = _policy.check_linear_policy(policy, ct.n_obs, self.num_envs, ct.obs_slot, self.device)
+            check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
+            lin = check(policy, ct.n_obs, self.num_envs, ct.obs_slot, self.device)
         elif kind not in _ffi.POLICY_KINDS:
             raise ValueError(f"policy kind {kind!r}")
         if self._pending_reset:  # next_step autoreset in lock step: the finished batch restarts before anything runs
             self._launch_device_reset(None, self._obs_ptr)
         if lin is not None and not self._obs_current:
-            raise RuntimeError("rollout(kind='linear') reads the observation buffer, which does not hold the agents' "
+            raise RuntimeError(f"rollout(kind={kind!r}) reads the observation buffer, which does not hold the agents' "
                                "current rows (write_obs=False, a built-in rollout or load_state_dict since the last "
                                "step()/reset()): call step() or reset() first")
+        if kind == "mlp":
+            return self._rollout_mlp(lin, n_steps, alert_mask)
         if lin is not None:
             return self._rollout_linear(lin, n_steps, alert_mask)
         p = _ffi.Policy()
@@ -853,9 +862,22 @@ class HeatAlertVecEnv(_VectorEnvBase):
         out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
         return out
 
+    def _rollout_mlp(self, mlp, n_steps, alert_mask) -> dict:
+        """rollout(kind="mlp"): w2a_rollout_mlp on the checked, packed policy (weather2alert_amd/policy.py)."""
+        mp = _ffi.MlpPolicy()
+        mp.params = mlp.params.data_ptr()
+        mp.group = None if mlp.group is None else mlp.group.data_ptr()
+        mp.order = None if mlp.order is None else mlp.order.data_ptr()
+        mp.n_groups, mp.n_layers, mp.width = mlp.n_groups, mlp.n_layers, mlp.width
+        mp.activation = _ffi.MLP_ACTIVATIONS[mlp.activation]
+        mp.sample, mp.require_budget, mp.seed = int(mlp.sample), int(mlp.require_budget), mlp.seed
+        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp)
+        out["group_mean_return"] = _policy.group_mean(out["return"], mlp.group, mlp.n_groups)
+        return out
+
     def _rollout_run(self, p, lp, n_steps, alert_mask, keep) -> dict:
         """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
-        linear (lp, w2a_rollout_linear)."""
+        linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp)."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -885,13 +907,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
                     _ffi.check(self._lib.w2a_rollout_mfma_prepare(self._h, self._mfma_ws.data_ptr(), self._mfma_ws.numel(),
                                                                   self._stream()), "w2a_rollout_mfma_prepare")
             if lp is not None:
-                _ffi.check(self._lib.w2a_rollout_linear(self._h, C.byref(lp), steps, self._obs.data_ptr(),
-                                                        out["return"].data_ptr(), out["alerts"].data_ptr(),
-                                                        out["attempts_over_budget"].data_ptr(),
-                                                        None if mask is None else mask.data_ptr(),
-                                                        None if amask is None else amask.data_ptr(), words, self._fr_ptr,
-                                                        None if snap is None else snap.data_ptr(), self._stream()),
-                           "w2a_rollout_linear")
+                fn = "w2a_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_rollout_linear"
+                _ffi.check(getattr(self._lib, fn)(self._h, C.byref(lp), steps, self._obs.data_ptr(),
+                                                  out["return"].data_ptr(), out["alerts"].data_ptr(),
+                                                  out["attempts_over_budget"].data_ptr(),
+                                                  None if mask is None else mask.data_ptr(),
+                                                  None if amask is None else amask.data_ptr(), words, self._fr_ptr,
+                                                  None if snap is None else snap.data_ptr(), self._stream()), fn)
             elif self._pm:
                 steps = self._rollout_posterior_mean(p, steps, out, mask, amask, words, snap, st0)
             else:

@@ -1,4 +1,6 @@
-"""Linear-logistic policies for ``HeatAlertVecEnv.rollout({"kind": "linear", ...})`` (csrc/w2a_rollout_linear.hip.h).
+"""Linear-logistic and MLP policies for ``HeatAlertVecEnv.rollout({"kind": "linear" | "mlp", ...})``
+(csrc/w2a_rollout_linear.hip.h, csrc/w2a_rollout_mlp.hip.h). The MLP kind's host side (checks, packing into the w2a.h
+layout, the group-major visiting order, ``mlp_from_module``) follows the linear kind's, below it.
 
 The host side of w2a_rollout_linear: argument checks, the permutation of the parameters from observation order (the
 columns of ``env.feature_names``) into the kernels' 32-slot feature-row order (``CompiledTables.obs_slot``), and the
@@ -123,3 +125,224 @@ def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) 
     lo = torch.searchsorted(sg, ids, right=False)
     hi = torch.searchsorted(sg, ids, right=True)
     return ((csum[hi] - csum[lo]) / (hi - lo).to(torch.float64)).to(torch.float32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# MLP policies: rollout({"kind": "mlp", ...}) (csrc/w2a_rollout_mlp.hip.h)
+# ----------------------------------------------------------------------------------------------------------------------
+#     {"kind": "mlp",
+#      "layers": [(W1, b1), (W2, b2), (Wo, bo)],  # torch Linear convention: W [out, in] or [G, out, in], b [out] / [G, out]
+#      "activation": "tanh",   # or "relu": after every hidden layer, none after the output
+#      "group": g,             # int [num_envs] in [0, G); may be omitted when G == 1
+#      "order": None,          # optional int [num_envs] visiting permutation (default: the envs stably sorted by group)
+#      "sample": False, "seed": 0, "require_budget": False}   # as for kind="linear"
+# One or two hidden layers of width 1..64; the first takes the n_obs observation columns in observation order; the
+# output has one row (the logit) or two (SB3's two action values: logit = row1 - row0, folded here in fp64).
+
+MLP_KEYS = {"kind", "layers", "activation", "group", "order", "sample", "seed", "require_budget"}
+MLP_WIDTHS = (16, 32, 64)  # the kernel's padded hidden widths
+MLP_MAX_HIDDEN = 2
+MLP_ACTIVATIONS = ("tanh", "relu")
+
+
+def mlp_stride(width: int, n_layers: int) -> int:
+    """Floats per group block of the packed parameters (w2a.h: W2A_MLP_STRIDE)."""
+    return ROW_FLOATS * width + width + (width * width + width if n_layers == 2 else 0) + width + 4
+
+
+def mlp_width(hidden) -> int:
+    """The padded width the kernel runs for these hidden widths."""
+    m = max(hidden)
+    return next(w for w in MLP_WIDTHS if w >= m)
+
+
+@dataclass
+class MlpPolicyArgs:
+    """A checked MLP policy, on the env's device: what w2a_mlp_policy points to, plus the group ids for the per-group
+    mean of the returns."""
+    params: torch.Tensor         # f32 [G, mlp_stride(width, n_layers)], contiguous (the w2a.h layout)
+    group: torch.Tensor | None   # int32 [num_envs], None = every env in group 0
+    order: torch.Tensor | None   # int32 [num_envs] visiting permutation, None = the env's own order
+    n_groups: int
+    n_layers: int                # hidden layers
+    width: int                   # padded hidden width: 16, 32 or 64
+    activation: str
+    sample: bool
+    seed: int
+    require_budget: bool
+
+
+def _real(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.is_complex() or not (t.is_floating_point() or t.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"mlp policy: {what} must be real numbers, got {t.dtype}")
+    return t.to(torch.float64)
+
+
+def _mlp_layers(layers, n_obs: int):
+    """The layers as fp64 [G or 1, out, in] / [G or 1, out] tensors, checked, and G."""
+    if not isinstance(layers, (list, tuple)) or not 2 <= len(layers) <= MLP_MAX_HIDDEN + 1:
+        raise ValueError(f"mlp policy: 'layers' must be a list of 2..{MLP_MAX_HIDDEN + 1} (weight, bias) pairs "
+                         f"(1..{MLP_MAX_HIDDEN} hidden layers and the output layer)")
+    out, G, fan_in = [], None, n_obs
+    for i, layer in enumerate(layers):
+        if not isinstance(layer, (list, tuple)) or len(layer) != 2:
+            raise ValueError(f"mlp policy: layer {i} must be a (weight, bias) pair")
+        W, b = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in layer)
+        W, b = _real(W.detach().cpu(), f"layer {i} weight"), _real(b.detach().cpu(), f"layer {i} bias")
+        if W.dim() == 2:
+            W = W.unsqueeze(0)
+        if W.dim() != 3 or W.shape[2] != fan_in or W.shape[1] < 1 or W.shape[0] < 1:
+            raise ValueError(f"mlp policy: layer {i} weight must be [out, {fan_in}] or [G, out, {fan_in}], "
+                             f"got {tuple(layer[0].shape) if hasattr(layer[0], 'shape') else '?'}")
+        rows = int(W.shape[1])
+        if b.dim() == 1:
+            b = b.unsqueeze(0)
+        if b.dim() != 2 or b.shape[1] != rows or b.shape[0] not in (1, W.shape[0]):
+            raise ValueError(f"mlp policy: layer {i} bias must be [{rows}] or [G, {rows}], got {tuple(b.shape)}")
+        for n_g in (W.shape[0], b.shape[0]):
+            if n_g != 1:
+                if G is not None and n_g != G:
+                    raise ValueError(f"mlp policy: layers disagree on the number of groups ({G} vs {n_g})")
+                G = int(n_g)
+        last = i == len(layers) - 1
+        if last and rows not in (1, 2):
+            raise ValueError(f"mlp policy: the output layer must have 1 or 2 rows, got {rows}")
+        if not last and rows > MLP_WIDTHS[-1]:
+            raise ValueError(f"mlp policy: hidden layer {i} is {rows} wide; at most {MLP_WIDTHS[-1]}")
+        out.append((W, b))
+        fan_in = rows
+    # the kernels compute on the f32 values: a parameter that is not finite there is refused
+    if not all(bool(torch.isfinite(x.to(torch.float32)).all()) for wb in out for x in wb):
+        raise ValueError("mlp policy: weights and biases must be finite (as float32)")
+    return out, (G or 1)
+
+
+def pack_mlp(layers, obs_slot, n_obs: int):
+    """Pack checked or raw layers into the kernel's layout (w2a.h: w2a_mlp_policy): f32 [G, stride] on the CPU, with
+    (width, n_layers, G). A two-row output is folded into logit = row1 - row0 in fp64 before rounding to f32."""
+    L, G = _mlp_layers(layers, n_obs)
+    hidden = [int(W.shape[1]) for W, _ in L[:-1]]
+    nl, w = len(hidden), mlp_width(hidden)
+    s = torch.as_tensor(slot_map(obs_slot, n_obs))
+    P = torch.zeros((G, mlp_stride(w, nl)), dtype=torch.float64)
+    off = 0
+
+    def put(dst_shape, src):
+        nonlocal off
+        n = int(np.prod(dst_shape))
+        P[:, off:off + n].view(G, *dst_shape).copy_(src)
+        off += n
+
+    W1, b1 = (x.expand(G, *x.shape[1:]) for x in L[0])
+    W1s = torch.zeros((G, ROW_FLOATS, w), dtype=torch.float64)
+    W1s[:, s, :hidden[0]] = W1.transpose(1, 2)
+    put((ROW_FLOATS, w), W1s)
+    put((w,), torch.nn.functional.pad(b1, (0, w - hidden[0])))
+    if nl == 2:
+        W2, b2 = (x.expand(G, *x.shape[1:]) for x in L[1])
+        W2p = torch.zeros((G, w, w), dtype=torch.float64)
+        W2p[:, :hidden[0], :hidden[1]] = W2.transpose(1, 2)  # [input unit][output unit]
+        put((w, w), W2p)
+        put((w,), torch.nn.functional.pad(b2, (0, w - hidden[1])))
+    Wo, bo = (x.expand(G, *x.shape[1:]) for x in L[-1])
+    if Wo.shape[1] == 2:  # SB3's two action values: argmax / softmax over {0, 1} is the sign / sigmoid of row1 - row0
+        Wo, bo = Wo[:, 1:] - Wo[:, :1], bo[:, 1:] - bo[:, :1]
+    put((w,), torch.nn.functional.pad(Wo[:, 0], (0, w - hidden[-1])))
+    P[:, off] = bo[:, 0]
+    P = P.to(torch.float32)
+    if not bool(torch.isfinite(P).all()):
+        raise ValueError("mlp policy: the folded output row (row1 - row0) is not finite as float32")
+    return P, w, nl, G
+
+
+def group_order(group: torch.Tensor) -> torch.Tensor:
+    """int32 [num_envs]: the env ids stably sorted by group, so each group's envs fill whole waves."""
+    return torch.sort(group, stable=True).indices.to(torch.int32).contiguous()
+
+
+def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device) -> MlpPolicyArgs:
+    """Validate a {"kind": "mlp", ...} policy (ValueError on anything the kernel could not run as asked) and bring its
+    parameters into the kernel's layout on `device`."""
+    unknown = set(policy) - MLP_KEYS
+    if unknown:
+        raise ValueError(f"mlp policy: unknown key(s) {sorted(unknown)}; choose from {sorted(MLP_KEYS)}")
+    act = policy.get("activation", "tanh")
+    if act not in MLP_ACTIVATIONS:
+        raise ValueError(f"mlp policy: activation must be one of {MLP_ACTIVATIONS}, got {act!r}")
+    if "layers" not in policy:
+        raise ValueError("mlp policy: 'layers' is required")
+    P, width, nl, G = pack_mlp(policy["layers"], obs_slot, n_obs)
+    g = policy.get("group")
+    if g is None:
+        if G != 1:
+            raise ValueError(f"mlp policy: 'group' [num_envs] is required with G={G} parameter blocks")
+    else:
+        g = _tensor(g, "group", device)
+        if g.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+            raise ValueError(f"mlp policy: group must be integer, got {g.dtype}")
+        if g.dim() != 1 or g.numel() != num_envs:
+            raise ValueError(f"mlp policy: group must be [num_envs={num_envs}], got {tuple(g.shape)}")
+        lo, hi = (int(v) for v in torch.stack([g.min(), g.max()]).to(torch.int64).tolist())
+        if lo < 0 or hi >= G:
+            raise ValueError(f"mlp policy: group ids must lie in [0, {G}), got [{lo}, {hi}]")
+        g = g.to(torch.int32).contiguous()
+    order = policy.get("order")
+    if order is not None:
+        order = _tensor(order, "order", device)
+        if order.dtype not in (torch.int16, torch.int32, torch.int64) or order.dim() != 1 or order.numel() != num_envs:
+            raise ValueError(f"mlp policy: order must be an integer [num_envs={num_envs}] permutation")
+        if not torch.equal(torch.sort(order.to(torch.int64)).values,
+                           torch.arange(num_envs, dtype=torch.int64, device=order.device)):
+            raise ValueError("mlp policy: order must be a permutation of the env ids")
+        order = order.to(torch.int32).contiguous()
+    elif g is not None:
+        order = group_order(g)
+    sample = policy.get("sample", False)
+    rb = policy.get("require_budget", False)
+    if not isinstance(sample, (bool, np.bool_)) or not isinstance(rb, (bool, np.bool_)):
+        raise ValueError("mlp policy: 'sample' and 'require_budget' must be bools")
+    seed = policy.get("seed", 0)
+    if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
+        raise ValueError("mlp policy: 'seed' must be an int")
+    return MlpPolicyArgs(P.to(device).contiguous(), g, order, G, nl, width, act, bool(sample), int(seed) & (2**64 - 1),
+                         bool(rb))
+
+
+def mlp_from_module(module: torch.nn.Module, group=None) -> dict:
+    """A {"kind": "mlp", ...} policy from a torch.nn.Sequential of Linear / Tanh / ReLU: Linear, act, [Linear, act,]
+    Linear, with one activation type and an output of 1 or 2 units. Nested Sequentials are flattened, so an SB3 actor is
+    ``mlp_from_module(nn.Sequential(*model.policy.mlp_extractor.policy_net, model.policy.action_net))`` and a DQN
+    Q-net ``mlp_from_module(model.q_net.q_net)``. The parameters are copied (detached) as they are now."""
+    def flat(m):
+        if isinstance(m, torch.nn.Sequential):
+            for c in m:
+                yield from flat(c)
+        else:
+            yield m
+
+    if not isinstance(module, torch.nn.Sequential):
+        raise ValueError(f"mlp_from_module: expected a torch.nn.Sequential, got {type(module).__name__}")
+    mods = [m for m in flat(module) if not isinstance(m, (torch.nn.Identity, torch.nn.Flatten))]
+    acts = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu"}
+    for m in mods:
+        if not isinstance(m, torch.nn.Linear) and type(m) not in acts:
+            raise ValueError(f"mlp_from_module: unsupported module {type(m).__name__} (Linear, Tanh and ReLU only)")
+    kinds = {acts[type(m)] for m in mods if type(m) in acts}
+    if len(kinds) > 1:
+        raise ValueError("mlp_from_module: one activation type only (Tanh or ReLU), got both")
+    pattern = ["L" if isinstance(m, torch.nn.Linear) else "A" for m in mods]
+    if pattern not in (["L", "A", "L"], ["L", "A", "L", "A", "L"]):
+        raise ValueError(f"mlp_from_module: expected Linear, act, [Linear, act,] Linear; got "
+                         f"{[type(m).__name__ for m in mods]} (1 or 2 hidden layers)")
+    layers = []
+    for m in mods:
+        if isinstance(m, torch.nn.Linear):
+            W = m.weight.detach().clone()
+            b = m.bias.detach().clone() if m.bias is not None else torch.zeros(m.out_features, dtype=W.dtype)
+            layers.append((W, b))
+    if layers[-1][0].shape[0] not in (1, 2):
+        raise ValueError(f"mlp_from_module: the output layer has {layers[-1][0].shape[0]} units; 1 or 2 supported")
+    pol = {"kind": "mlp", "layers": layers, "activation": kinds.pop()}
+    if group is not None:
+        pol["group"] = group
+    return pol
