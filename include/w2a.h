@@ -386,6 +386,40 @@ typedef struct w2a_mlp_policy {
 int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                     int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                     int32_t mask_words, float *last_return, float *ret_snapshot, void *stream);
+/* w2a_rollout_linear / w2a_rollout_mlp that also record the per-day trajectory (on-policy training data). Arguments,
+ * results and refusals are those of the plain forms, which the recording changes in no bit; in addition
+ * W2A_ERR_ARG for a NULL traj or a NULL member pointer (checked on the host, before the handle). Every array is
+ * device memory indexed [call-day s][env id] (n = num_envs, n_obs of w2a_tables), s = 0 .. n_steps - 1:
+ *   obs     f32 [n_steps + 1][n][n_obs], 4-B aligned: slab s is the row the agent held before decision s (exactly what
+ *           w2a_step would have returned); slab 0 is the obs buffer on entry, for every env; slab s + 1 after a
+ *           terminal step repeats slab s (the terminal step leaves the previous row); slab n_steps is, for every env,
+ *           the obs buffer when the call returns -- the bootstrap row of a truncated chunk. Rows past an env's
+ *           terminal day, other than slab n_steps, are unspecified.
+ *   logit   f32 [n_steps][n]: the logit decision s was taken on (linear: the fp64 logit rounded to f32; mlp: the f32
+ *           logit, row1 - row0 for a two-row output)
+ *   reward  f32 [n_steps][n]: the reward w2a_step returns for that day
+ *   action  u8  [n_steps][n]: the action passed to the env (the policy's decision after require_budget)
+ *   flags   u8  [n_steps][n]: W2A_TRAJ_VALID (the env took a step on call-day s) | W2A_TRAJ_TERMINATED (that step ended
+ *           its episode) | W2A_TRAJ_ALERT (an alert was issued: an attempt with no budget left is none). The library
+ *           zeroes flags on the stream first, so entries the env did not step hold 0; their logit, reward, action are
+ *           left unwritten. A recorded call visits the envs in identity order where it can (speed only).
+ * Bytes per env-day: 4 n_obs + 10 (126 on the default schema). */
+enum { W2A_TRAJ_VALID = 1, W2A_TRAJ_TERMINATED = 2, W2A_TRAJ_ALERT = 4 };
+typedef struct w2a_trajectory {
+  float *obs;      /* [n_steps + 1][n][n_obs] */
+  float *logit;    /* [n_steps][n] */
+  float *reward;   /* [n_steps][n] */
+  uint8_t *action; /* [n_steps][n] */
+  uint8_t *flags;  /* [n_steps][n] */
+} w2a_trajectory;
+int w2a_rollout_linear_record(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                              float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                              uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                              void *stream, const w2a_trajectory *traj);
+int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                           int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                           uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                           void *stream, const w2a_trajectory *traj);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

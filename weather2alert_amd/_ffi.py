@@ -23,7 +23,7 @@ SYMBOLS = [
     "w2a_reset_device_rng", "w2a_set_autoreset", "w2a_step", "w2a_get_state", "w2a_read_status",
     "w2a_sort_workspace_bytes", "w2a_sort_episodes", "w2a_reset_device_rng_sorted", "w2a_observe", "w2a_rollout", "w2a_rollout_order_workspace_bytes", "w2a_rollout_order_attach", "w2a_rollout_order", "w2a_rollout_posterior_mean", "w2a_policy_actions", "w2a_set_semantics",
     "w2a_group_workspace_bytes", "w2a_group_by_column", "w2a_posterior_mean_reward", "w2a_set_posterior_kernel", "w2a_invalidate", "w2a_query", "w2a_rollout_mfma_workspace_bytes", "w2a_rollout_mfma_prepare",
-    "w2a_rollout_linear", "w2a_rollout_mlp",
+    "w2a_rollout_linear", "w2a_rollout_mlp", "w2a_rollout_linear_record", "w2a_rollout_mlp_record",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
@@ -49,6 +49,15 @@ class MlpPolicy(C.Structure):
 
 
 MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}  # W2A_MLP_TANH, W2A_MLP_RELU
+
+
+class Trajectory(C.Structure):
+    """w2a_trajectory: device arrays [call-day][env] of w2a_rollout_*_record (include/w2a.h)."""
+    _fields_ = [("obs", C.c_void_p), ("logit", C.c_void_p), ("reward", C.c_void_p), ("action", C.c_void_p),
+                ("flags", C.c_void_p)]
+
+
+TRAJ_VALID, TRAJ_TERMINATED, TRAJ_ALERT = 1, 2, 4  # W2A_TRAJ_* flag bits
 
 
 class Tables(C.Structure):
@@ -162,6 +171,10 @@ def load(build_if_missing: bool = True):
     lib.w2a_rollout_linear.argtypes = [vp, C.POINTER(LinearPolicy), i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.w2a_rollout_mlp.restype = C.c_int
     lib.w2a_rollout_mlp.argtypes = [vp, C.POINTER(MlpPolicy), i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.w2a_rollout_linear_record.restype = C.c_int
+    lib.w2a_rollout_linear_record.argtypes = lib.w2a_rollout_linear.argtypes + [C.POINTER(Trajectory)]
+    lib.w2a_rollout_mlp_record.restype = C.c_int
+    lib.w2a_rollout_mlp_record.argtypes = lib.w2a_rollout_mlp.argtypes + [C.POINTER(Trajectory)]
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     if lib.w2a_abi_version() != ABI_VERSION:

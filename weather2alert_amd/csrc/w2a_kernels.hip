@@ -819,9 +819,24 @@ int w2a_rollout(w2a_env *env, const w2a_policy *policy, int32_t n_steps, float *
 // w2a_bookkeeping.h: bk_rollout_kernel)
 #define W2A_ROLLOUT_KERNEL_LINEAR 3
 
-int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
-                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
+// the host-side checks of a trajectory (w2a_rollout_linear_record, w2a_rollout_mlp_record): before anything else
+static int check_trajectory(const w2a_trajectory *traj, const char *fn) {
+  if (!traj) return fail(W2A_ERR_ARG, "%s: NULL trajectory", fn);
+  if (!traj->obs || !traj->logit || !traj->reward || !traj->action || !traj->flags)
+    return fail(W2A_ERR_ARG, "%s: NULL trajectory array", fn);
+  return W2A_OK;
+}
+
+// zeroes the flags of every (call-day, env) the kernel writes: entries of envs that take no step keep 0
+static int clear_trajectory_flags(const w2a_env *env, int32_t n_steps, const w2a_trajectory *traj, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(traj->flags, 0, (size_t)n_steps * (size_t)env->n, s));
+  return W2A_OK;
+}
+
+static int rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                          int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                          uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                          void *stream, const w2a_trajectory *traj) {
   // what can be checked without the handle first (so that it is checked on any machine)
   if (!policy) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL policy");
   if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_linear: n_steps must be positive");
@@ -877,21 +892,56 @@ int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_
   if (attempt_mask) HIP_TRY(hipMemsetAsync(attempt_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
   const bool masks = alert_mask || attempt_mask || ret_snapshot;
-  if (masks && policy->sample) hipLaunchKernelGGL((k_rollout_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, la);
-  else if (masks) hipLaunchKernelGGL((k_rollout_linear<true, false>), dim3(g64), dim3(BLOCK), 0, s, la);
-  else if (policy->sample) hipLaunchKernelGGL((k_rollout_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, la);
-  else hipLaunchKernelGGL((k_rollout_linear<false, false>), dim3(g64), dim3(BLOCK), 0, s, la);
+  w2a_trajectory tr;
+  memset(&tr, 0, sizeof(tr));
+  if (traj) {
+    tr = *traj;
+    la.r.order = nullptr;  // identity order: the kernel's staged store design (every env's result is order-independent)
+    const int rc = clear_trajectory_flags(env, n_steps, traj, s);
+    if (rc != W2A_OK) return rc;
+  }
+#define W2A_LAUNCH_LINEAR(M, S, R) hipLaunchKernelGGL((k_rollout_linear<M, S, R>), dim3(g64), dim3(BLOCK), 0, s, la, tr)
+  if (traj) {
+    if (masks && policy->sample) W2A_LAUNCH_LINEAR(true, true, true);
+    else if (masks) W2A_LAUNCH_LINEAR(true, false, true);
+    else if (policy->sample) W2A_LAUNCH_LINEAR(false, true, true);
+    else W2A_LAUNCH_LINEAR(false, false, true);
+  } else {
+    if (masks && policy->sample) W2A_LAUNCH_LINEAR(true, true, false);
+    else if (masks) W2A_LAUNCH_LINEAR(true, false, false);
+    else if (policy->sample) W2A_LAUNCH_LINEAR(false, true, false);
+    else W2A_LAUNCH_LINEAR(false, false, false);
+  }
+#undef W2A_LAUNCH_LINEAR
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
 }
 
+int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
+  return rollout_linear(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+                        mask_words, last_return, ret_snapshot, stream, nullptr);
+}
+
+int w2a_rollout_linear_record(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                              float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                              uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                              void *stream, const w2a_trajectory *traj) {
+  const int rc = check_trajectory(traj, "w2a_rollout_linear_record");
+  if (rc != W2A_OK) return rc;
+  return rollout_linear(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+                        mask_words, last_return, ret_snapshot, stream, traj);
+}
+
 // what W2A_Q_LAST_ROLLOUT_KERNEL reports after w2a_rollout_mlp
 #define W2A_ROLLOUT_KERNEL_MLP 4
 
-int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                    int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
-                    int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
+static int rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream,
+                       const w2a_trajectory *traj) {
   // what can be checked without the handle first (so that it is checked on any machine)
   if (!policy) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL policy");
   if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_steps must be positive");
@@ -955,17 +1005,41 @@ int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps,
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
   const bool masks = alert_mask || attempt_mask || ret_snapshot;
   const int32_t smp = policy->sample;
+  if (traj) {
+    const int rc = clear_trajectory_flags(env, n_steps, traj, s);
+    if (rc != W2A_OK) return rc;
+    // one group: identity order, the kernel's staged store design (results are order-independent); with groups the
+    // group-major order keeps the kernel's group loop short and the rows are stored directly
+    if (policy->n_groups == 1) ma.r.order = nullptr;
+  }
   switch (policy->width * 4 + policy->n_layers) {
-    case 16 * 4 + 1: launch_rollout_mlp<16, 1>(ma, masks, smp, g64, s); break;
-    case 16 * 4 + 2: launch_rollout_mlp<16, 2>(ma, masks, smp, g64, s); break;
-    case 32 * 4 + 1: launch_rollout_mlp<32, 1>(ma, masks, smp, g64, s); break;
-    case 32 * 4 + 2: launch_rollout_mlp<32, 2>(ma, masks, smp, g64, s); break;
-    case 64 * 4 + 1: launch_rollout_mlp<64, 1>(ma, masks, smp, g64, s); break;
-    default: launch_rollout_mlp<64, 2>(ma, masks, smp, g64, s); break;
+    case 16 * 4 + 1: launch_rollout_mlp<16, 1>(ma, masks, smp, traj, g64, s); break;
+    case 16 * 4 + 2: launch_rollout_mlp<16, 2>(ma, masks, smp, traj, g64, s); break;
+    case 32 * 4 + 1: launch_rollout_mlp<32, 1>(ma, masks, smp, traj, g64, s); break;
+    case 32 * 4 + 2: launch_rollout_mlp<32, 2>(ma, masks, smp, traj, g64, s); break;
+    case 64 * 4 + 1: launch_rollout_mlp<64, 1>(ma, masks, smp, traj, g64, s); break;
+    default: launch_rollout_mlp<64, 2>(ma, masks, smp, traj, g64, s); break;
   }
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
+}
+
+int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                    int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
+                    int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
+  return rollout_mlp(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+                     mask_words, last_return, ret_snapshot, stream, nullptr);
+}
+
+int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                           int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                           uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                           void *stream, const w2a_trajectory *traj) {
+  const int rc = check_trajectory(traj, "w2a_rollout_mlp_record");
+  if (rc != W2A_OK) return rc;
+  return rollout_mlp(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+                     mask_words, last_return, ret_snapshot, stream, traj);
 }
 
 int w2a_rollout_posterior_mean(w2a_env *env, const w2a_policy *policy, int32_t n_steps, float *ret_out,

@@ -29,11 +29,92 @@ struct LinearRolloutArgs {
   int8_t slot_obs[RO64_SLOTS];  // slot -> observation column, -1 = none (kernel argument: scalar loads, no table)
 };
 
+// RECORD (w2a_rollout_linear_record / w2a_rollout_mlp_record): every active day also stores the trajectory entry of
+// (call-day s, env e) -- action, logit, reward, flags and the observation row the env holds after the step -- with
+// plain per-lane stores at env-id addresses (w2a.h: w2a_trajectory). Addresses are formed where they are used: 64-bit
+// slab offsets ((s + 1) * n * n_obs passes 2^32 at 1 M envs), one pointer per row, nothing held across the day loop.
+__device__ __forceinline__ float *traj_obs_row(const w2a_trajectory &tr, int32_t slab, int64_t n, uint32_t e,
+                                               int32_t n_obs) {
+  uint64_t o = ((uint64_t)slab * (uint64_t)n + e) * (uint64_t)n_obs;
+  asm volatile("" : "+v"(o));  // one offset register pair: the 29 row addresses are not hoisted out of the day loop
+  return tr.obs + o;
+}
+
+// one whole observation row of the caller's buffer into trajectory slab `slab` (slab 0 on entry, slab n_steps at
+// the end, and the repeated row after a terminal step)
+template <class Args>
+__device__ __forceinline__ void traj_copy_row(const Args &pa, const w2a_trajectory &tr, int32_t slab, uint32_t e,
+                                              uint32_t obs0) {
+  float *dst = traj_obs_row(tr, slab, pa.r.n, e, pa.n_obs);
+  uint32_t o = obs0;
+  asm volatile("" : "+v"(o));
+#pragma unroll
+  for (int k = 0; k < RO64_SLOTS; ++k)
+    if (pa.slot_obs[k] >= 0) dst[pa.slot_obs[k]] = pa.obs[o + pa.slot_obs[k]];
+}
+
+// Two store designs for the observation rows (profiles/r09/store_design_ab.log):
+//   staged  (identity visiting order: a wave serves 64 consecutive envs, whose rows of slab s + 1 are one contiguous
+//           64 * n_obs-float block): each lane puts its row into the wave's LDS tile [64][n_obs], then the wave stores
+//           the block with lane-consecutive dwords (every store instruction covers 256 contiguous bytes);
+//   direct  (any other order): each lane stores its own row, n_obs scattered dwords.
+// The host passes no visiting order to a recorded call where it can (w2a_kernels.hip), so the staged form is the usual one.
+#define TRAJ_TILE (64 * RO64_SLOTS)  // floats of a wave's staging tile (n_obs <= RO64_SLOTS)
+
+__device__ __forceinline__ void traj_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the trajectory entry of an active env's call-day s; xv[] is the row it holds after a non-terminal step. stage: the
+// wave's LDS tile (staged design) or nullptr (direct design)
+template <class Args>
+__device__ __forceinline__ void traj_record_day(const Args &pa, const w2a_trajectory &tr, int32_t s, uint32_t e,
+                                                uint32_t obs0, const float (&xv)[32], int32_t act, float logit,
+                                                float r, bool done, uint32_t actual, float *stage) {
+  const size_t d = (size_t)s * (size_t)pa.r.n + e;
+  tr.action[d] = (uint8_t)act;
+  tr.logit[d] = logit;
+  tr.reward[d] = r;
+  tr.flags[d] = (uint8_t)(W2A_TRAJ_VALID | (done ? W2A_TRAJ_TERMINATED : 0) | (actual ? W2A_TRAJ_ALERT : 0));
+  if (s + 1 < pa.r.n_steps) {  // slab n_steps: after the day loop, for every env
+    uint32_t o = obs0;
+    asm volatile("" : "+v"(o));
+    float *dst = stage ? stage + (threadIdx.x & 63) * pa.n_obs : traj_obs_row(tr, s + 1, pa.r.n, e, pa.n_obs);
+    if (done) {  // the terminal step leaves the previous row, still in the buffer
+#pragma unroll
+      for (int k = 0; k < RO64_SLOTS; ++k)
+        if (pa.slot_obs[k] >= 0) dst[pa.slot_obs[k]] = pa.obs[o + pa.slot_obs[k]];
+    } else {
+#pragma unroll
+      for (int k = 0; k < RO64_SLOTS; ++k)
+        if (pa.slot_obs[k] >= 0) dst[pa.slot_obs[k]] = xv[k];
+    }
+  }
+}
+
+// staged design, wave-uniform, after every lane's traj_record_day of call-day s: the wave's tile to slab s + 1. Rows of
+// lanes with no live env carry stale values into entries the contract leaves unspecified; nothing is stored past env
+// n - 1 (e0: the wave's first env)
+template <class Args>
+__device__ __forceinline__ void traj_store_tile(const Args &pa, const w2a_trajectory &tr, int32_t s, uint32_t e0,
+                                                const float *stage) {
+  if (s + 1 >= pa.r.n_steps) return;
+  traj_wave_lds_sync();
+  const int64_t left = pa.r.n - (int64_t)e0;
+  const uint32_t lim = (uint32_t)(left < 64 ? left : 64) * (uint32_t)pa.n_obs;
+  float *blk = traj_obs_row(tr, s + 1, pa.r.n, e0, pa.n_obs);
+  for (uint32_t f = threadIdx.x & 63; f < lim; f += 64) blk[f] = stage[f];
+  traj_wave_lds_sync();  // the tile is read before the next day's rows go in
+}
+
 // Registers: the third coefficient row costs 30 VGPRs over k_rollout64's 121-124. Left to itself the compiler takes
 // 169-189 (2 waves/SIMD, no spill); held to 3 waves/SIMD (168) it spills 14-89 B per lane to scratch and runs faster:
 // 1.50 ms against 1.71 ms per 1 M-env episode (profiles/r07/kernel_trace_linear.txt).
-template <bool MASKS, bool SAMPLE>
-__global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRolloutArgs la) {
+// RECORD = false compiles to the kernel without a trajectory (same registers, scratch and LDS).
+template <bool MASKS, bool SAMPLE, bool RECORD>
+__global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRolloutArgs la, const w2a_trajectory tr) {
   const RolloutArgs &a = la.r;
   const int64_t slot64 = (int64_t)logical_block(blockIdx.x, gridDim.x >> 3) * BLOCK + threadIdx.x;
   if (slot64 - (threadIdx.x & 63) >= a.n) return;  // whole wave past the end
@@ -71,6 +152,12 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
   }
   const uint64_t pstream = SAMPLE ? rng_stream(a.pol.seed ^ 0xA5A5A5A55A5A5A5Aull, (uint64_t)(a.gid0 + e), cold.w) : 0ull;
   const uint32_t obs0 = e * (uint32_t)la.n_obs;  // first element of the env's observation row (host: n * n_obs < 2^31)
+  if (RECORD && valid) traj_copy_row(la, tr, 0, e, obs0);  // slab 0: the row every env holds on entry
+  float *stage = nullptr;  // staged store design: identity order (wave-uniform)
+  if constexpr (RECORD) {
+    __shared__ float s_traj[BLOCK / 64][TRAJ_TILE];
+    if (!a.order) stage = s_traj[threadIdx.x >> 6];
+  }
   float ret = 0.0f;
   int32_t alerts = 0, over = 0;
   uint32_t mask_word = 0, mask_idx = 0xFFFFFFFFu;
@@ -156,6 +243,7 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
         att_word |= 1u << (t & 31);
       }
       if (MASKS && (done ? t : t + 1) + 2 == ndays) { snap = ret_total; snapped = true; }
+      if (RECORD) traj_record_day(la, tr, s, e, obs0, xv, act, (float)z, r, done, actual, stage);
       // the row the agent now holds is xv[] (a terminal step leaves the previous one): written back once, when it is
       // the last row of this call -- its last day, or the day before the terminal one
       if (!done && (s + 1 == a.n_steps || t + 2 >= ndays)) {
@@ -172,7 +260,9 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
       else { fin = true; active = false; }
       z = zp;
     }
+    if (RECORD && stage) traj_store_tile(la, tr, s, (uint32_t)(slot64 - (threadIdx.x & 63)), stage);
   }
+  if (RECORD && valid) traj_copy_row(la, tr, a.n_steps, e, obs0);  // slab n_steps: the buffer as the call leaves it
   if (valid) {
     store_hot(a.st, e, make_uint4(pack_d0(t, used, streak, last, atb), pack_d1(hist, ndays, fin ? 1u : 0u),
                                   __float_as_uint(ret_total), (uint32_t)budget));

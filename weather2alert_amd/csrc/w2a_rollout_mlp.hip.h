@@ -151,8 +151,11 @@ __device__ __forceinline__ float mlp_logit_groups(const MlpRolloutArgs &ma, int3
 }
 
 // Registers: see DESIGN.md (k_rollout_mlp); held to 2 waves/SIMD like the other large day loops
-template <int WIDTH, int LAYERS, bool MASKS>
-__global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs ma, const int32_t sample) {
+// RECORD: the trajectory of w2a_rollout_mlp_record (k_rollout_linear's traj_record_day); RECORD = false compiles to the
+// kernel without one
+template <int WIDTH, int LAYERS, bool MASKS, bool RECORD>
+__global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs ma, const int32_t sample,
+                                                          const w2a_trajectory tr) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
   const RolloutArgs &a = ma.r;
   const int64_t slot64 = (int64_t)logical_block(blockIdx.x, gridDim.x >> 3) * BLOCK + threadIdx.x;
@@ -189,6 +192,12 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
   g = g < 0 ? 0 : (g >= ma.n_groups ? ma.n_groups - 1 : g);
   const uint64_t pstream = sample ? rng_stream(a.pol.seed ^ 0xA5A5A5A55A5A5A5Aull, (uint64_t)(a.gid0 + e), cold.w) : 0ull;
   const uint32_t obs0 = e * (uint32_t)ma.n_obs;  // first element of the env's observation row (host: n * n_obs < 2^31)
+  if (RECORD && valid) traj_copy_row(ma, tr, 0, e, obs0);  // slab 0: the row every env holds on entry
+  float *stage = nullptr;  // staged store design: identity order (wave-uniform)
+  if constexpr (RECORD) {
+    __shared__ float s_traj[MLP_WAVES][TRAJ_TILE];
+    if (!a.order) stage = s_traj[threadIdx.x >> 6];
+  }
   float ret = 0.0f;
   int32_t alerts = 0, over = 0;
   uint32_t mask_word = 0, mask_idx = 0xFFFFFFFFu;
@@ -282,6 +291,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
         att_word |= 1u << (t & 31);
       }
       if (MASKS && (done ? t : t + 1) + 2 == ndays) { snap = ret_total; snapped = true; }
+      if (RECORD) traj_record_day(ma, tr, s, e, obs0, xv, act, z, r, done, actual, stage);
       // the row the agent now holds is xv[] (a terminal step leaves the previous one): written back once, when it is
       // the last row of this call -- its last day, or the day before the terminal one
       if (!done && (s + 1 == a.n_steps || t + 2 >= ndays)) {
@@ -295,11 +305,13 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
       if (!done) { streak = actual ? streak + 1 : 0; t = t + 1; }
       else { fin = true; active = false; }
     }
+    if (RECORD && stage) traj_store_tile(ma, tr, s, (uint32_t)(slot64 - (threadIdx.x & 63)), stage);
     if (s + 1 < a.n_steps) {  // wave-uniform: the logit of the row each env now holds, for tomorrow
       mlp_wave_lds_sync();
       z = mlp_logit_groups<WIDTH, LAYERS>(ma, g, xs);
     }
   }
+  if (RECORD && valid) traj_copy_row(ma, tr, a.n_steps, e, obs0);  // slab n_steps: the buffer as the call leaves it
   if (valid) {
     store_hot(a.st, e, make_uint4(pack_d0(t, used, streak, last, atb), pack_d1(hist, ndays, fin ? 1u : 0u),
                                   __float_as_uint(ret_total), (uint32_t)budget));
@@ -315,11 +327,17 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
   }
 }
 
-// the host side's launch of one of the 12 instantiations (w2a_rollout_mlp)
+// the host side's launch of one of the 24 instantiations (w2a_rollout_mlp, w2a_rollout_mlp_record: traj non-NULL)
 template <int WIDTH, int LAYERS>
-static void launch_rollout_mlp(const MlpRolloutArgs &ma, bool masks, int32_t sample, unsigned grid, hipStream_t s) {
-  if (masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample);
-  else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false>), dim3(grid), dim3(BLOCK), 0, s, ma, sample);
+static void launch_rollout_mlp(const MlpRolloutArgs &ma, bool masks, int32_t sample, const w2a_trajectory *traj,
+                               unsigned grid, hipStream_t s) {
+  w2a_trajectory tr;
+  memset(&tr, 0, sizeof(tr));
+  if (traj) tr = *traj;
+  if (traj && masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else if (traj) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else if (masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
 }
 
 #endif  // W2A_ROLLOUT_MLP_HIP_H

@@ -774,7 +774,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return RecordedSteps(self, one_day, days, warmup)
 
     # ------------------------------------------------------------------ rollout
-    def rollout(self, policy: dict, n_steps: int | None = None, alert_mask: bool = False) -> dict:
+    def rollout(self, policy: dict, n_steps: int | None = None, alert_mask: bool = False, record: bool = False) -> dict:
         """Run a built-in policy inside the kernel for ``n_steps`` days (default: to the end of the episode)
         without returning to Python between days (replaces loops like env.py:265-277). With
         reward_mode="posterior_mean" the whole rollout is one launch of k_pm_rollout (vector kernel, <= 112 posterior
@@ -807,12 +807,31 @@ class HeatAlertVecEnv(_VectorEnvBase):
         today's row instead). Returns device tensors: "return" (rewards summed over the days run), "alerts",
         "attempts_over_budget", "final_return" (episode return of envs that finished), "done", and with
         alert_mask=True "alert_days" bool [N, T]. In lock-step same_step-autoreset mode a finished batch is
-        reset, so consecutive calls evaluate consecutive episodes."""
+        reset, so consecutive calls evaluate consecutive episodes.
+        record=True (linear and mlp kinds only; ValueError otherwise) also returns the per-day trajectory for
+        on-policy training, "trajectory": a dict of device tensors indexed [call-day s, env id] (S = the days the call
+        was asked to run, N = num_envs), written by the same kernel launch (w2a_rollout_*_record, include/w2a.h):
+          "obs"        f32 [S+1, N, n_obs]  obs[s]: the row the agent held before decision s (what step() returned);
+                                            obs[S]: the observation buffer as the call leaves it, before any lock-step
+                                            autoreset it triggers -- the bootstrap row of a truncated chunk
+          "action"     u8   [S, N]  the action passed to the env (after require_budget)
+          "logit"      f32  [S, N]  the logit of that decision (linear: the fp64 logit rounded to f32)
+          "reward"     f32  [S, N]  the reward step() returns for that day
+          "valid"      bool [S, N]  the env took a step on call-day s
+          "terminated" bool [S, N]  that step ended its episode
+          "alert"      bool [S, N]  the alert actually issued
+        Entries where valid is False are unspecified, except that valid, terminated and alert are False there.
+        Recording changes nothing else the call returns or leaves behind, bit for bit; two calls of k and S - k days
+        record what one call of S days does. policy.action_log_prob(logit, action) gives the log-probability of a
+        recorded action. The tensors are allocated per call (torch's caching allocator): 4 n_obs + 10 bytes per
+        env-day plus one obs slab -- 126 B on the default schema, about 20 GB for 1 M envs x 153 days."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         ct = self.ct
         kind = policy.get("kind")
         lin = None
+        if record and kind not in ("linear", "mlp"):
+            raise ValueError(f"rollout(record=True) needs kind 'linear' or 'mlp', got {kind!r}")
         if kind in ("linear", "mlp"):  # every argument is checked before anything runs
             if self._pm:
                 raise ValueError(f"rollout(kind={kind!r}) needs reward_mode='sampled'")
@@ -830,9 +849,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                "current rows (write_obs=False, a built-in rollout or load_state_dict since the last "
                                "step()/reset()): call step() or reset() first")
         if kind == "mlp":
-            return self._rollout_mlp(lin, n_steps, alert_mask)
+            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record))
         if lin is not None:
-            return self._rollout_linear(lin, n_steps, alert_mask)
+            return self._rollout_linear(lin, n_steps, alert_mask, bool(record))
         p = _ffi.Policy()
         p.kind = _ffi.POLICY_KINDS[kind]
         p.p = float(policy.get("p", 0.0))
@@ -852,17 +871,17 @@ class HeatAlertVecEnv(_VectorEnvBase):
             p.table, p.table_R = keep.data_ptr(), int(keep.shape[1])
         return self._rollout_run(p, None, n_steps, alert_mask, keep)
 
-    def _rollout_linear(self, lin, n_steps, alert_mask) -> dict:
+    def _rollout_linear(self, lin, n_steps, alert_mask, record=False) -> dict:
         """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
         lp = _ffi.LinearPolicy()
         lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
         lp.group = None if lin.group is None else lin.group.data_ptr()
         lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
-        out = self._rollout_run(None, lp, n_steps, alert_mask, lin)
+        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record)
         out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
         return out
 
-    def _rollout_mlp(self, mlp, n_steps, alert_mask) -> dict:
+    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False) -> dict:
         """rollout(kind="mlp"): w2a_rollout_mlp on the checked, packed policy (weather2alert_amd/policy.py)."""
         mp = _ffi.MlpPolicy()
         mp.params = mlp.params.data_ptr()
@@ -871,13 +890,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mp.n_groups, mp.n_layers, mp.width = mlp.n_groups, mlp.n_layers, mlp.width
         mp.activation = _ffi.MLP_ACTIVATIONS[mlp.activation]
         mp.sample, mp.require_budget, mp.seed = int(mlp.sample), int(mlp.require_budget), mlp.seed
-        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp)
+        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record)
         out["group_mean_return"] = _policy.group_mean(out["return"], mlp.group, mlp.n_groups)
         return out
 
-    def _rollout_run(self, p, lp, n_steps, alert_mask, keep) -> dict:
+    def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False) -> dict:
         """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
-        linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp)."""
+        linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True)."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -889,6 +908,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
         amask = torch.empty((n, words), dtype=torch.int32, device=dev) if alert_mask else None
         snap = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if alert_mask else None
         st0 = self.state() if (alert_mask or self._pm) else None
+        traj = tr = None
+        if record:  # lp is not None: rollout() refuses record=True for the other kinds
+            traj = {"obs": torch.empty((steps + 1, n, ct.n_obs), dtype=torch.float32, device=dev),
+                    "logit": torch.empty((steps, n), dtype=torch.float32, device=dev),
+                    "reward": torch.empty((steps, n), dtype=torch.float32, device=dev),
+                    "action": torch.empty((steps, n), dtype=torch.uint8, device=dev),
+                    "flags": torch.empty((steps, n), dtype=torch.uint8, device=dev)}  # zeroed by the library
+            tr = _ffi.Trajectory(*(traj[k].data_ptr() for k in ("obs", "logit", "reward", "action", "flags")))
         with torch.cuda.device(dev):
             if not self._pm and getattr(self, "_order_stale", True) and self.rollout_order:
                 if self._order_ws is None:
@@ -908,12 +935,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                                   self._stream()), "w2a_rollout_mfma_prepare")
             if lp is not None:
                 fn = "w2a_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_rollout_linear"
-                _ffi.check(getattr(self._lib, fn)(self._h, C.byref(lp), steps, self._obs.data_ptr(),
-                                                  out["return"].data_ptr(), out["alerts"].data_ptr(),
-                                                  out["attempts_over_budget"].data_ptr(),
-                                                  None if mask is None else mask.data_ptr(),
-                                                  None if amask is None else amask.data_ptr(), words, self._fr_ptr,
-                                                  None if snap is None else snap.data_ptr(), self._stream()), fn)
+                args = (self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
+                        out["alerts"].data_ptr(), out["attempts_over_budget"].data_ptr(),
+                        None if mask is None else mask.data_ptr(), None if amask is None else amask.data_ptr(), words,
+                        self._fr_ptr, None if snap is None else snap.data_ptr(), self._stream())
+                if tr is not None:
+                    fn += "_record"
+                    args += (C.byref(tr),)
+                _ffi.check(getattr(self._lib, fn)(*args), fn)
             elif self._pm:
                 steps = self._rollout_posterior_mean(p, steps, out, mask, amask, words, snap, st0)
             else:
@@ -928,6 +957,12 @@ class HeatAlertVecEnv(_VectorEnvBase):
         st = self.state() if mask is not None else self._state_packed(("finished",))[1]
         out["done"] = st["finished"].bool()  # the terminal step has run (t stops at n_days-1 before AND after it)
         out["final_return"] = self._final_return.clone()  # meaningful where out["done"]
+        if traj is not None:
+            flags = traj.pop("flags")
+            traj["valid"] = (flags & _ffi.TRAJ_VALID) != 0
+            traj["terminated"] = (flags & _ffi.TRAJ_TERMINATED) != 0
+            traj["alert"] = (flags & _ffi.TRAJ_ALERT) != 0
+            out["trajectory"] = traj
         if mask is not None:
             bits = torch.arange(32, device=dev, dtype=torch.int32)
             unpack = lambda m: (((m.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()  # noqa: E731

@@ -346,3 +346,17 @@ def mlp_from_module(module: torch.nn.Module, group=None) -> dict:
     if group is not None:
         pol["group"] = group
     return pol
+
+
+def action_log_prob(logit, action):
+    """log P(action | logit) of the Bernoulli policy pi(alert) = sigmoid(logit): the decision rule of ``sample=True``
+    (alert iff u < sigmoid(logit)) and SB3's two-way categorical on its two action values (logit = row1 - row0).
+    Computed stably, elementwise and differentiably: -softplus(-logit) for action 1, -softplus(logit) for action 0.
+    ``logit`` is a float tensor (as recorded in ``rollout(..., record=True)["trajectory"]["logit"]`` or recomputed by
+    the learner), ``action`` anything that broadcasts with it (0 / 1, bool or u8).
+    With ``require_budget=True`` the kernel forces the action to 0 when no budget is left, whatever the draw: such
+    actions are off the policy's distribution, and their log-probability here is that of the policy, not of the
+    forced choice -- mask them (or do not use require_budget) when computing on-policy ratios."""
+    logit = logit if torch.is_tensor(logit) else torch.as_tensor(logit)
+    a = torch.as_tensor(action, device=logit.device).to(torch.bool)
+    return -torch.nn.functional.softplus(torch.where(a, -logit, logit))
