@@ -420,6 +420,34 @@ int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n
                            int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
                            uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
                            void *stream, const w2a_trajectory *traj);
+/* The returns of a stretch of days under EVERY posterior draw of each env's coefficient column. The trajectory does not
+ * depend on the draw (the state update reads only the actions and the alert buffers; the draw enters only the reward,
+ * env.py:197-226), so the state at the start of the stretch and the bitmap of the alerts issued in it fix every day's
+ * input vector, and
+ *     out[e][k] = sum over the days env e ran of reward(x_t, a_t; W[coef_col[e] * n_samples + k]),  k < n_samples,
+ * summed in f32 in day order. Draw k is a joint posterior sample over all counties: the mean over a set of envs of
+ * out[.][k] is one posterior sample of the mean return.
+ *   start       device i32 arrays of the state BEFORE the stretch, as w2a_get_state decodes it; read: t, used, streak,
+ *               hist14, budget, n_days, county_w, year_i, coef_col, finished (the others may be NULL)
+ *   alert_mask  device u32 [num_envs][mask_words], bit d = an alert was issued on day d (the alert_mask output of the
+ *               rollout that ran the stretch, the reference's actual_alert_buffer); mask_words * 32 >= T
+ *   n_steps     days of the stretch: each env runs from its start day t for at most n_steps days, stopping after its
+ *               terminal day; envs finished on entry get a row of zeros
+ *   out         device f32 [num_envs][n_samples]
+ * Numerics contract: every day rebuilds the 32-slot vector exactly as the rollout kernels do (the table row of day t,
+ * the faithful run-time fields: alert_lag1, the pre-update alert_streak, remaining_budget, alert_2wks from the bitmap)
+ * and evaluates both logits as fp64 FMA chains over slots 0..29 in slot order, the heat gate, the f32 sigmoids and the
+ * reward of w2a_step. Hence column sample_e (the env's own draw) is BIT-IDENTICAL to the ret_out of the rollout that
+ * produced the bitmap for the fp64-chain kernels (k_rollout64, k_rollout_linear, k_rollout_mlp: w2a_rollout with a
+ * visiting order and no matrix-core prepare, w2a_rollout_linear, w2a_rollout_mlp), and within 2e-6 relative of it for
+ * k_rollout_mfma (int8 digits of the table-sourced terms); every column is within the reward bars (1e-5 per day) of an
+ * fp64 restatement. A start state outside the tables (no reset produces one) gives NaN rows.
+ * Reads the tables and the caller's arrays only: the handle's state and bookkeeping are untouched. W2A_ERR_ARG for NULL
+ * pointers, n_steps <= 0, mask_words <= 0 (checked on the host, before the handle), mask_words * 32 < T, and on a handle
+ * with corrected-semantics flags (the reward then depends on attempts and on other table rows); W2A_ERR_STATE while
+ * `stream` is recording a hipGraph. */
+int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint32_t *alert_mask, int32_t mask_words,
+                          int32_t n_steps, float *out, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

@@ -47,6 +47,7 @@
 #include "w2a_rollout_mlp.hip.h"
 #include "w2a_rollout_i8.hip.h"
 #include "w2a_rollout_mfma.hip.h"
+#include "w2a_posterior_returns.hip.h"
 #include "w2a_sort.hip.h"
 
 // ----------------------------------------------------------------------------------------
@@ -1040,6 +1041,36 @@ int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n
   if (rc != W2A_OK) return rc;
   return rollout_mlp(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
                      mask_words, last_return, ret_snapshot, stream, traj);
+}
+
+int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint32_t *alert_mask, int32_t mask_words,
+                          int32_t n_steps, float *out, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine)
+  if (!start || !alert_mask || !out) return fail(W2A_ERR_ARG, "w2a_posterior_returns: NULL argument");
+  if (!start->t || !start->used || !start->streak || !start->hist14 || !start->budget || !start->n_days ||
+      !start->county_w || !start->year_i || !start->coef_col || !start->finished)
+    return fail(W2A_ERR_ARG, "w2a_posterior_returns: NULL start-state array (t, used, streak, hist14, budget, n_days, "
+                             "county_w, year_i, coef_col and finished are read)");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_posterior_returns: n_steps must be positive");
+  if (mask_words <= 0) return fail(W2A_ERR_ARG, "w2a_posterior_returns: mask_words must be positive");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_posterior_returns: NULL handle");
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_posterior_returns: alert_mask needs ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_posterior_returns: not available with corrected-semantics flags (the reward then "
+                             "depends on attempts and on other table rows)");
+  REFUSE_WHILE_CAPTURING("w2a_posterior_returns", stream);
+  const uint64_t lanes = (uint64_t)env->n * (uint64_t)env->tb.n_samples;
+  if (lanes == 0) return W2A_OK;
+  if ((lanes + 255) / 256 > 0x7FFFFFFFull) return fail(W2A_ERR_ARG, "w2a_posterior_returns: num_envs * n_samples too large");
+  PostRetArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tb = env->tb; a.st = *start; a.alert_mask = alert_mask; a.mask_words = mask_words; a.n_steps = n_steps;
+  a.n = env->n; a.out = out;
+  // reads the tables and the caller's arrays only: the handle's state buffer and bookkeeping are not touched
+  hipLaunchKernelGGL(k_posterior_returns, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return W2A_OK;
 }
 
 int w2a_rollout_posterior_mean(w2a_env *env, const w2a_policy *policy, int32_t n_steps, float *ret_out,

@@ -774,7 +774,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return RecordedSteps(self, one_day, days, warmup)
 
     # ------------------------------------------------------------------ rollout
-    def rollout(self, policy: dict, n_steps: int | None = None, alert_mask: bool = False, record: bool = False) -> dict:
+    def rollout(self, policy: dict, n_steps: int | None = None, alert_mask: bool = False, record: bool = False,
+                posterior_returns: bool = False) -> dict:
         """Run a built-in policy inside the kernel for ``n_steps`` days (default: to the end of the episode)
         without returning to Python between days (replaces loops like env.py:265-277). With
         reward_mode="posterior_mean" the whole rollout is one launch of k_pm_rollout (vector kernel, <= 112 posterior
@@ -824,7 +825,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
         Recording changes nothing else the call returns or leaves behind, bit for bit; two calls of k and S - k days
         record what one call of S days does. policy.action_log_prob(logit, action) gives the log-probability of a
         recorded action. The tensors are allocated per call (torch's caching allocator): 4 n_obs + 10 bytes per
-        env-day plus one obs slab -- 126 B on the default schema, about 20 GB for 1 M envs x 153 days."""
+        env-day plus one obs slab -- 126 B on the default schema, about 20 GB for 1 M envs x 153 days.
+        posterior_returns=True (every kind, with or without record, both reward modes) also returns
+        "posterior_returns" f32 [N, n_samples]: each env's return over the days this call ran under EVERY posterior draw
+        of its coefficient column (w2a_posterior_returns, include/w2a.h: the trajectory does not depend on the draw, so
+        the call's alert bitmap and start state fix every day's input). Column "sample" of an env is its own draw: bit
+        for bit "return" for the fp64-chain rollout kernels, within 2e-6 relative for k_rollout_mfma. The linear and mlp
+        kinds also return "group_posterior_returns" f32 [G, n_samples], the mean over each group's envs per draw (one
+        posterior sample of the group's value per column; stats.posterior_summary, stats.prob_better). Nothing else the
+        call returns or leaves behind changes. Faithful semantics only (fixes other than "budget": ValueError)."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         ct = self.ct
@@ -832,6 +841,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         lin = None
         if record and kind not in ("linear", "mlp"):
             raise ValueError(f"rollout(record=True) needs kind 'linear' or 'mlp', got {kind!r}")
+        if posterior_returns and self.fixes - {"budget"}:
+            raise ValueError(f"rollout(posterior_returns=True) needs faithful semantics; fixes "
+                             f"{sorted(self.fixes - {'budget'})} make the reward depend on attempts and other rows")
         if kind in ("linear", "mlp"):  # every argument is checked before anything runs
             if self._pm:
                 raise ValueError(f"rollout(kind={kind!r}) needs reward_mode='sampled'")
@@ -848,10 +860,11 @@ class HeatAlertVecEnv(_VectorEnvBase):
             raise RuntimeError(f"rollout(kind={kind!r}) reads the observation buffer, which does not hold the agents' "
                                "current rows (write_obs=False, a built-in rollout or load_state_dict since the last "
                                "step()/reset()): call step() or reset() first")
+        pr = bool(posterior_returns)
         if kind == "mlp":
-            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record))
+            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr)
         if lin is not None:
-            return self._rollout_linear(lin, n_steps, alert_mask, bool(record))
+            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr)
         p = _ffi.Policy()
         p.kind = _ffi.POLICY_KINDS[kind]
         p.p = float(policy.get("p", 0.0))
@@ -869,19 +882,21 @@ class HeatAlertVecEnv(_VectorEnvBase):
             if keep.dim() != 2 or keep.shape[0] < ct.T:
                 raise ValueError(f"policy table must be [T >= {ct.T}, R]")
             p.table, p.table_R = keep.data_ptr(), int(keep.shape[1])
-        return self._rollout_run(p, None, n_steps, alert_mask, keep)
+        return self._rollout_run(p, None, n_steps, alert_mask, keep, posterior_returns=pr)
 
-    def _rollout_linear(self, lin, n_steps, alert_mask, record=False) -> dict:
+    def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False) -> dict:
         """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
         lp = _ffi.LinearPolicy()
         lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
         lp.group = None if lin.group is None else lin.group.data_ptr()
         lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
-        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record)
+        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns)
         out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
+        if posterior_returns:
+            out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], lin.group, lin.n_groups)
         return out
 
-    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False) -> dict:
+    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False) -> dict:
         """rollout(kind="mlp"): w2a_rollout_mlp on the checked, packed policy (weather2alert_amd/policy.py)."""
         mp = _ffi.MlpPolicy()
         mp.params = mlp.params.data_ptr()
@@ -890,13 +905,17 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mp.n_groups, mp.n_layers, mp.width = mlp.n_groups, mlp.n_layers, mlp.width
         mp.activation = _ffi.MLP_ACTIVATIONS[mlp.activation]
         mp.sample, mp.require_budget, mp.seed = int(mlp.sample), int(mlp.require_budget), mlp.seed
-        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record)
+        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns)
         out["group_mean_return"] = _policy.group_mean(out["return"], mlp.group, mlp.n_groups)
+        if posterior_returns:
+            out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], mlp.group, mlp.n_groups)
         return out
 
-    def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False) -> dict:
+    def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False, posterior_returns=False) -> dict:
         """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
-        linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True)."""
+        linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True).
+        posterior_returns: the alert bitmap is taken in any case (the rollout kernels' results do not depend on it) and
+        w2a_posterior_returns runs on it and the start state right after the rollout."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -904,10 +923,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
                "alerts": torch.empty(n, dtype=torch.int32, device=dev),
                "attempts_over_budget": torch.empty(n, dtype=torch.int32, device=dev)}
         words = (ct.T + 31) // 32
-        mask = torch.empty((n, words), dtype=torch.int32, device=dev) if alert_mask else None
+        mask = torch.empty((n, words), dtype=torch.int32, device=dev) if (alert_mask or posterior_returns) else None
         amask = torch.empty((n, words), dtype=torch.int32, device=dev) if alert_mask else None
         snap = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if alert_mask else None
-        st0 = self.state() if (alert_mask or self._pm) else None
+        st0 = self.state() if (alert_mask or self._pm or posterior_returns) else None
         traj = tr = None
         if record:  # lp is not None: rollout() refuses record=True for the other kinds
             traj = {"obs": torch.empty((steps + 1, n, ct.n_obs), dtype=torch.float32, device=dev),
@@ -951,10 +970,12 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                  None if mask is None else mask.data_ptr(),
                                                  None if amask is None else amask.data_ptr(), words, self._fr_ptr,
                                                  None if snap is None else snap.data_ptr(), self._stream()), "w2a_rollout")
+            if posterior_returns:
+                out["posterior_returns"] = self._posterior_returns_packed(st0, mask, words, steps)
         self._keep_pol = keep
         self._obs_current = lp is not None  # built-in policies write no observation rows (a reset below may)
         # only what this call returns is decoded (sixteen arrays of N int32 otherwise: 64 MB of writes at 1 M envs)
-        st = self.state() if mask is not None else self._state_packed(("finished",))[1]
+        st = self.state() if alert_mask else self._state_packed(("finished",))[1]
         out["done"] = st["finished"].bool()  # the terminal step has run (t stops at n_days-1 before AND after it)
         out["final_return"] = self._final_return.clone()  # meaningful where out["done"]
         if traj is not None:
@@ -963,7 +984,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
             traj["terminated"] = (flags & _ffi.TRAJ_TERMINATED) != 0
             traj["alert"] = (flags & _ffi.TRAJ_ALERT) != 0
             out["trajectory"] = traj
-        if mask is not None:
+        if alert_mask:
             bits = torch.arange(32, device=dev, dtype=torch.int32)
             unpack = lambda m: (((m.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()  # noqa: E731
             out["alert_days"] = unpack(mask)      # the reference's actual_alert_buffer (env.py:248), per day
@@ -979,6 +1000,49 @@ class HeatAlertVecEnv(_VectorEnvBase):
                     self._launch_device_reset(None, self._obs_ptr)
                 else:
                     self._pending_reset = True
+        return out
+
+    # ------------------------------------------------------------------ returns under every posterior draw
+    def posterior_returns(self, start_state: dict, alert_days, n_steps: int | None = None) -> torch.Tensor:
+        """f32 [N, n_samples]: each env's return over a stretch of days under every posterior draw of its coefficient
+        column -- what rollout(..., posterior_returns=True) returns, for any way the days were run (a torch policy
+        driven through step(), say). start_state: a state() dict taken before the stretch; alert_days: bool [N, T], the
+        alerts issued (day d of the episode; rollout(alert_mask=True)'s "alert_days", or built from the actions and the
+        budget); n_steps: the stretch's length in days (default: to the end of every episode). Envs finished in
+        start_state give zeros. w2a_posterior_returns (include/w2a.h): the same vector and the same fp64 FMA chains as
+        the step and rollout kernels. Faithful semantics only (fixes other than "budget": ValueError)."""
+        if self.fixes - {"budget"}:
+            raise ValueError(f"posterior_returns() needs faithful semantics; fixes {sorted(self.fixes - {'budget'})} "
+                             "make the reward depend on attempts and other rows")
+        ct, n, dev = self.ct, self.num_envs, self.device
+        words = (ct.T + 31) // 32
+        ad = torch.as_tensor(alert_days, device=dev)
+        if ad.dim() != 2 or ad.shape[0] != n or ad.shape[1] > words * 32:
+            raise ValueError(f"alert_days must be bool [{n}, T <= {words * 32}], got {tuple(ad.shape)}")
+        a32 = torch.nn.functional.pad(ad.to(torch.int32), (0, words * 32 - ad.shape[1])).view(n, words, 32)
+        # bits of one word are distinct powers of two: their int32 sum is the word (bit 31 as -2^31, no overflow)
+        mask = (a32 << torch.arange(32, dtype=torch.int32, device=dev)).sum(-1, dtype=torch.int32)
+        st = {}
+        for k in _PR_FIELDS:
+            if k not in start_state:
+                raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
+            st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
+            if st[k].shape != (n,):
+                raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
+        steps = int(n_steps) if n_steps is not None else ct.T
+        with torch.cuda.device(dev):
+            return self._posterior_returns_packed(st, mask.contiguous(), words, steps)
+
+    def _posterior_returns_packed(self, st0: dict, mask: torch.Tensor, words: int, steps: int) -> torch.Tensor:
+        """w2a_posterior_returns on device int32 state arrays and a packed [N, words] alert bitmap."""
+        out = torch.zeros((self.num_envs, self.ct.n_samples), dtype=torch.float32, device=self.device)
+        if steps <= 0:
+            return out
+        v = _ffi.StateView()
+        for k in _PR_FIELDS:
+            setattr(v, k, st0[k].data_ptr())
+        _ffi.check(self._lib.w2a_posterior_returns(self._h, C.byref(v), mask.data_ptr(), words, steps, out.data_ptr(),
+                                                   self._stream()), "w2a_posterior_returns")
         return out
 
     def _rollout_posterior_mean(self, p, steps, out, mask, amask, words, snap, st0) -> int:
@@ -1048,6 +1112,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
 
     def _info(self):
         return _LazyInfo(self)
+
+
+# the start-state fields w2a_posterior_returns reads
+_PR_FIELDS = ("t", "used", "streak", "hist14", "budget", "n_days", "county_w", "year_i", "coef_col", "finished")
 
 
 def __getattr__(name):  # weather2alert_amd.env.HeatAlertEnv: the drop-in lives in dropin.py (it builds on this module)

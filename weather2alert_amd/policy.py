@@ -112,19 +112,23 @@ def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, devic
 
 
 def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) -> torch.Tensor:
-    """f32 [n_groups]: the mean of `values` over each group's envs (NaN for a group without envs), on the device of
-    `values`: the groups' segments of the values sorted by group, summed as differences of one fp64 prefix sum. (An
-    index_add into n_groups fp64 cells measured 7.7 ms at 1 048 576 envs and G = 1024 -- four times the rollout it
-    follows -- every env's atomic contending with a thousand others for its cell; this is a sort and a scan.)"""
+    """f32 [n_groups] (values [N]) or [n_groups, K] (values [N, K], e.g. returns under K posterior draws): the mean of
+    `values` over each group's envs, per column (NaN for a group without envs), on the device of `values`: the groups'
+    segments of the rows sorted by group, summed as differences of one fp64 prefix sum down the rows. (An index_add into
+    n_groups fp64 cells measured 7.7 ms at 1 048 576 envs and G = 1024 -- four times the rollout it follows -- every
+    env's atomic contending with a thousand others for its cell; this is a sort and a scan.)"""
     if group is None:
-        return values.to(torch.float32).mean().reshape(1)
+        if values.dim() == 1:
+            return values.to(torch.float32).mean().reshape(1)
+        return values.to(torch.float64).mean(0, keepdim=True).to(torch.float32)
     sg, perm = torch.sort(group.to(torch.int32))
-    csum = torch.cat([torch.zeros(1, dtype=torch.float64, device=values.device),
-                      torch.cumsum(values.to(torch.float64)[perm], dim=0)])
+    csum = torch.cumsum(values.to(torch.float64)[perm], dim=0)
+    csum = torch.cat([torch.zeros((1,) + tuple(csum.shape[1:]), dtype=torch.float64, device=values.device), csum])
     ids = torch.arange(n_groups, dtype=torch.int32, device=values.device)
     lo = torch.searchsorted(sg, ids, right=False)
     hi = torch.searchsorted(sg, ids, right=True)
-    return ((csum[hi] - csum[lo]) / (hi - lo).to(torch.float64)).to(torch.float32)
+    cnt = (hi - lo).to(torch.float64).reshape((n_groups,) + (1,) * (values.dim() - 1))
+    return ((csum[hi] - csum[lo]) / cnt).to(torch.float32)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

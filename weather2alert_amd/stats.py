@@ -144,3 +144,41 @@ def write_episode_csv(path: str, out: dict) -> None:
         w.writeheader()
         for row in episode_rows(out):
             w.writerow(row)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# returns under the reward model's posterior: rollout(..., posterior_returns=True) / HeatAlertVecEnv.posterior_returns
+# ----------------------------------------------------------------------------------------------------------------------
+def posterior_summary(R, probs=(0.05, 0.5, 0.95), cvar_alpha: float = 0.1) -> dict:
+    """Summary over posterior draws, which lie in the LAST dimension of R (e.g. "group_posterior_returns" [G, K], or a
+    batch mean [K]); computed in fp64, returned as fp64 tensors of R's leading shape:
+      "mean", "std" (population: the K draws are the distribution itself),
+      "quantiles" [len(probs), ...] at `probs` (linear interpolation between order statistics, numpy's default),
+      "cvar": the mean of the worst (lowest-return) cvar_alpha fraction of the draws, the lower-tail expectation of the
+      K equally weighted draws: with m = floor(alpha K), the m lowest draws count fully and the (m+1)-th with weight
+      alpha K - m, all over alpha K (so alpha K need not be an integer; alpha = 1 gives the mean)."""
+    R = torch.as_tensor(R).to(torch.float64)
+    K = R.shape[-1]
+    if K < 1:
+        raise ValueError("posterior_summary needs at least one draw")
+    if not 0.0 < cvar_alpha <= 1.0:
+        raise ValueError(f"cvar_alpha must be in (0, 1], got {cvar_alpha}")
+    q = torch.as_tensor(probs, dtype=torch.float64, device=R.device)
+    srt = torch.sort(R, dim=-1).values
+    ak = cvar_alpha * K
+    m = min(int(ak + 1e-9), K)  # floor, robust to alpha K = 3 arriving as 2.9999999999999996
+    wts = torch.zeros(K, dtype=torch.float64, device=R.device)
+    wts[:m] = 1.0
+    if m < K and ak - m > 1e-9:
+        wts[m] = ak - m
+    return {"mean": R.mean(-1), "std": R.std(-1, unbiased=False), "quantiles": torch.quantile(R, q, dim=-1),
+            "cvar": (srt * wts).sum(-1) / wts.sum()}
+
+
+def prob_better(Ra, Rb) -> torch.Tensor:
+    """P(A beats B) under the posterior: the fraction of draws (last dimension, paired by draw: the same joint posterior
+    sample scores both) with Ra > Rb, ties counting 1/2. fp64 tensor of the leading shape."""
+    Ra, Rb = torch.as_tensor(Ra).to(torch.float64), torch.as_tensor(Rb).to(torch.float64)
+    if Ra.shape[-1] != Rb.shape[-1]:
+        raise ValueError(f"draws differ: {Ra.shape[-1]} and {Rb.shape[-1]}")
+    return ((Ra > Rb).to(torch.float64) + 0.5 * (Ra == Rb).to(torch.float64)).mean(-1)
