@@ -10,9 +10,10 @@
  *   - Every pointer is a DEVICE pointer owned by the caller (PyTorch) unless marked host.
  *     The library allocates nothing on the device and frees nothing but the handle.
  *   - All calls are asynchronous on `stream` (a hipStream_t passed as void*; NULL = the
- *     default stream). Two calls wait for the device: w2a_create (once per handle: it uploads the slot map and
- *     scans the tables on the NULL stream, then hipDeviceSynchronize) and w2a_read_status (waits for `stream`
- *     only, to read the status word back). Nothing else synchronises or allocates. What may be RECORDED into a
+ *     default stream). Three calls wait for the device: w2a_create (once per handle: it uploads the slot map and
+ *     scans the tables on the NULL stream, then hipDeviceSynchronize), w2a_read_status (waits for `stream`
+ *     only, to read the status word back) and w2a_hindsight_optimum (waits for `stream`: a slot-27 flag and a
+ *     histogram of the budgets come to the host). Nothing else synchronises or allocates. What may be RECORDED into a
  *     hipGraph is w2a_step (w2a_state_bytes below says what a recording implies) and, while they need no
  *     conversion of the state's form, w2a_posterior_mean_reward / w2a_policy_actions / w2a_get_state; every
  *     other entry point that launches work fails with W2A_ERR_STATE while `stream` is capturing -- a replay
@@ -448,6 +449,46 @@ int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n
  * `stream` is recording a hipGraph. */
 int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint32_t *alert_mask, int32_t mask_words,
                           int32_t n_steps, float *out, void *stream);
+/* The hindsight optimum: every env's best alert schedule for a stretch of days, knowing the whole stretch's weather,
+ * its own posterior draw and its remaining budget -- the upper bound against which a policy's return reads as regret.
+ * Under the faithful semantics the reward of a day depends on the agent only through four run-time slots: 24
+ * alert_lag1 (today's alert, 0 on day 0), 25 the streak before today's update, 26 budget - used after today's alert, 27
+ * the agent's 14-day count, whose coefficient is zero (the reference's weights key the historical alerts_2wks). So
+ * with j = alerts issued in the stretch and s = the current streak, a finite-horizon DP over (j, s) is exact:
+ *     V_d(j, s) = max( r0 + V_{d+1}(j, 0),  r1 + V_{d+1}(j + 1, s + 1) ),  V_H = 0,
+ * the alert allowed only while used + j < budget (an attempt at the budget is a no-op), values fp64 sums of the f32
+ * rewards, an alert taken only if STRICTLY better (ties do not alert); the schedule is backtracked from (0, streak).
+ * Each env runs from its start day t for H = min(n_steps, n_days - t) days, stopping after its terminal day (the
+ * convention of w2a_posterior_returns); U = min(budget - used, H) bounds j, (U + 1)(U + 4) / 2 states per day.
+ *   start       device i32 arrays of the state at the start, as w2a_get_state decodes it; read: t, used, streak, budget,
+ *               n_days, county_w, year_i, coef_col, sample, finished (the others may be NULL)
+ *   n_steps     days of the stretch (> 0)
+ *   ret_out     device f32 [num_envs]: the return of the schedule
+ *   alert_mask  device u32 [num_envs][mask_words], bit d = alert on day d of the episode (as w2a_rollout's alert_mask;
+ *               only days t .. t + H - 1 can be set); mask_words * 32 >= T
+ *   alerts_out  device i32 [num_envs]: alerts in the schedule (<= budget - used)
+ *   workspace   device memory of workspace_bytes >= w2a_hindsight_workspace_bytes(env, n_steps, max_remaining, 1)
+ *               bytes, 256-B aligned, max_remaining >= max(budget - used) over the envs of `start`: 8 B per env of
+ *               scratch, and a pool only if that budget's DP does not fit in LDS (budgets far beyond the tables'
+ *               defaults; about U^2 x 10 B per env at a remaining budget U); `big_envs` sizes the pool for that many
+ *               such envs per launch (speed only)
+ * Envs finished on entry (or with t >= n_days) get 0, an empty bitmap and 0 alerts; a start state outside the tables
+ * (no reset produces one) gives NaN, an empty bitmap and 0.
+ * Numerics contract: every reward the DP weighs is bit-identical to the one the env pays on that day in that state (the
+ * fp64 FMA chain of the step and rollout kernels over slots 0..23 once per env-day, continued per state over slots 24,
+ * 25, 26, 28, 29 in slot order, the heat gate, reward_from_logits), and ret_out re-adds the chosen rewards in f32 in day
+ * order: it is BIT-IDENTICAL to column `sample` of w2a_posterior_returns(start, alert_mask) and so to what a
+ * fp64-chain rollout replaying the schedule returns.
+ * Synchronises `stream` (one histogram of U comes to the host to size and bin the launches) and returns after the
+ * work is done. Reads the tables and the caller's arrays only: the handle's state and bookkeeping are untouched.
+ * W2A_ERR_ARG for NULL pointers, n_steps <= 0, mask_words <= 0 (checked on the host, before the handle), mask_words * 32
+ * < T, a handle with corrected-semantics flags, tables where some coefficient row has a nonzero slot-27 term (one
+ * scan of W per call), and a workspace too small for the batch; every refusal comes before any output is written.
+ * W2A_ERR_STATE while `stream` is recording a hipGraph. */
+size_t w2a_hindsight_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_remaining, int32_t big_envs);
+int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                          uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

@@ -24,7 +24,7 @@ SYMBOLS = [
     "w2a_sort_workspace_bytes", "w2a_sort_episodes", "w2a_reset_device_rng_sorted", "w2a_observe", "w2a_rollout", "w2a_rollout_order_workspace_bytes", "w2a_rollout_order_attach", "w2a_rollout_order", "w2a_rollout_posterior_mean", "w2a_policy_actions", "w2a_set_semantics",
     "w2a_group_workspace_bytes", "w2a_group_by_column", "w2a_posterior_mean_reward", "w2a_set_posterior_kernel", "w2a_invalidate", "w2a_query", "w2a_rollout_mfma_workspace_bytes", "w2a_rollout_mfma_prepare",
     "w2a_rollout_linear", "w2a_rollout_mlp", "w2a_rollout_linear_record", "w2a_rollout_mlp_record",
-    "w2a_posterior_returns",
+    "w2a_posterior_returns", "w2a_hindsight_workspace_bytes", "w2a_hindsight_optimum",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
@@ -178,6 +178,10 @@ def load(build_if_missing: bool = True):
     lib.w2a_rollout_mlp_record.argtypes = lib.w2a_rollout_mlp.argtypes + [C.POINTER(Trajectory)]
     lib.w2a_posterior_returns.restype = C.c_int
     lib.w2a_posterior_returns.argtypes = [vp, C.POINTER(StateView), vp, i32, i32, vp, vp]
+    lib.w2a_hindsight_workspace_bytes.restype = C.c_size_t
+    lib.w2a_hindsight_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.w2a_hindsight_optimum.restype = C.c_int
+    lib.w2a_hindsight_optimum.argtypes = [vp, C.POINTER(StateView), i32, vp, vp, i32, vp, vp, C.c_size_t, vp]
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     if lib.w2a_abi_version() != ABI_VERSION:

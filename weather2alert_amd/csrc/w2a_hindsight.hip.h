@@ -1,0 +1,282 @@
+// w2a_hindsight.hip.h -- k_hs_plan / k_hs_scatter / k_hs_dp: every env's best alert schedule in hindsight, by exact DP
+// Part of libw2a.so; included only by w2a_kernels.hip (one translation unit, see the file comment there).
+#ifndef W2A_HINDSIGHT_HIP_H
+#define W2A_HINDSIGHT_HIP_H
+
+// ----------------------------------------------------------------------------------------
+// hindsight optimum (w2a_hindsight_optimum)
+// ----------------------------------------------------------------------------------------
+// Under the faithful semantics the reward of day d reads four run-time slots and nothing else that depends on the
+// agent (w2a_posterior_returns.hip.h): 24 alert_lag1 (today's alert, 0 on day 0), 25 the pre-update streak, 26 the
+// remaining budget after today's alert, 27 the agent's 14-day count -- whose coefficient is zero (quirk Q1: the
+// reference's key is the historical alerts_2wks; the entry refuses tables where it is not). So with j = alerts issued
+// inside the horizon and s = the current streak, (j, s) is an exact DP state:
+//   V_d(j, s) = max( r0 + V_{d+1}(j, 0),  r1 + V_{d+1}(j + 1, s + 1) ),  the second only while used + j < budget,
+// fp64 sums of the f32 rewards, alert only if STRICTLY greater (ties do not alert).
+//   State index. Streaks that started inside the horizon are <= j; the one streak that did not (the start streak s0,
+//   unbroken since) is s0 + j at j = d. Slot k = 0 .. j + 1 of row j holds streak k (k <= j) or s0 + j (k = j + 1):
+//   idx(j, k) = j (j + 3) / 2 + k, NS(U) = (U + 1)(U + 4) / 2 states for j <= U, and both transitions are
+//   (j, k) -> (j, 0) and (j, k) -> (j + 1, k + 1). At day d only rows j <= min(d, U) are reachable and computed.
+//   Mapping: one 64-lane workgroup (one wave) per env, lanes over the day's states in chunks of 64. Envs are binned by
+//   U (k_hs_plan / k_hs_scatter: a counting sort) and each bin is one launch whose dynamic LDS holds exactly its need:
+//   per day the static logit prefixes (slots 0..23, fp64, 16 B) and slots 28..30 (16 B), the double-buffered V
+//   (2 x 8 B x NS) and one ballot word of decision bits per 64-state chunk and day. Bins whose need exceeds
+//   HS_LDS_CAP keep V and the decision words in the caller's workspace instead (the same code through global pointers;
+//   large budgets: correct, not fast).
+//   Numerics: the prefix over slots 0..23 is the FMA chain of the step / rollout kernels up to slot 23; per state the
+//   chain continues over slots 24, 25, 26, 28, 29 in slot order (slot 27's term is +-0 and is left out: the logit can
+//   differ from the env's only in the sign of a zero, which no sigmoid sees), then the heat gate and
+//   reward_from_logits: every reward the DP weighs is the one the env would pay in that state, bit for bit. The
+//   backtrack recomputes the chosen rewards with the same code and adds them in f32 in day order, as the env does.
+#define HS_BLOCK 64
+#define HS_LDS_CAP (64 * 1024)
+#define HS_BINS 1024  // U <= H <= T <= 1023
+
+__host__ __device__ __forceinline__ uint32_t hs_ns(uint32_t U) { return (U + 1u) * (U + 4u) / 2u; }
+__host__ __device__ __forceinline__ uint32_t hs_nc(uint32_t U) { return (hs_ns(U) + 63u) / 64u; }
+// bytes of V + decision words of one env at U over hb days (LDS or workspace)
+__host__ __device__ __forceinline__ size_t hs_dp_bytes(uint32_t U, uint32_t hb) {
+  return 16ull * hs_ns(U) + 8ull * hb * hs_nc(U);
+}
+// bytes of the per-day statics (always LDS)
+__host__ __device__ __forceinline__ size_t hs_day_bytes(uint32_t hb) { return 32ull * hb; }
+
+struct HsArgs {
+  DevTables tb;
+  w2a_state_view st;       // start state (device i32 arrays, w2a_get_state's decoding)
+  int32_t n_steps;
+  int32_t hb;              // min(n_steps, T): bound of every env's horizon (stride of the decision words)
+  int32_t mask_words;
+  int64_t n;
+  float *ret;              // [n]
+  uint32_t *mask;          // [n][mask_words]
+  int32_t *alerts;         // [n]
+  uint32_t *u_env;         // [n] workspace: U, or HS_NONE / HS_BAD (no DP: k_hs_scatter writes the outputs)
+  uint32_t *hist;          // [HS_BINS] workspace: envs per U
+  uint32_t *cursor;        // [HS_BINS] workspace: first position of every bin in `order`, advanced by k_hs_scatter
+  uint32_t *order;         // [n] workspace: env ids by U
+};
+#define HS_NONE 0xFFFFFFFFu  // nothing to choose (finished, or t >= n_days): return 0
+#define HS_BAD 0xFFFFFFFEu   // a start outside the tables: return NaN
+
+struct HsEnv {  // one env's start, decoded and range-checked
+  uint32_t t0, used, s0, ndays, ep_row, wrow;
+  int32_t budget;
+  bool bad;
+  uint32_t H, U;
+};
+__device__ __forceinline__ HsEnv hs_env(const HsArgs &a, uint32_t e) {
+  const w2a_state_view &v = a.st;
+  HsEnv h;
+  h.t0 = (uint32_t)v.t[e]; h.used = (uint32_t)v.used[e]; h.s0 = (uint32_t)v.streak[e];
+  h.budget = v.budget[e]; h.ndays = (uint32_t)v.n_days[e];
+  const uint32_t cw = (uint32_t)v.county_w[e], yi = (uint32_t)v.year_i[e], col = (uint32_t)v.coef_col[e];
+  const uint32_t smp = (uint32_t)v.sample[e];
+  // a start state no reset can produce would index outside the tables: NaN marks the env, nothing is read
+  h.bad = cw >= (uint32_t)a.tb.S_w || yi >= (uint32_t)a.tb.Y || col >= (uint32_t)a.tb.S ||
+          smp >= (uint32_t)a.tb.n_samples || h.ndays > (uint32_t)a.tb.T;
+  h.ep_row = cw * (uint32_t)a.tb.Y + yi;
+  h.wrow = col * (uint32_t)a.tb.n_samples + smp;
+  const bool active = v.finished[e] == 0 && h.t0 < h.ndays;
+  h.H = active ? min((uint32_t)a.n_steps, h.ndays - h.t0) : 0u;
+  const int32_t rem = h.budget - (int32_t)h.used;
+  h.U = rem <= 0 ? 0u : min((uint32_t)rem, h.H);
+  return h;
+}
+
+// per env: horizon and U (envs without a DP are marked); histogram of U. Writes no output: the host checks the
+// workspace against the histogram before anything the caller sees is written.
+__global__ __launch_bounds__(256) void k_hs_plan(const HsArgs a) {
+  __shared__ uint32_t cnt[HS_BINS];
+  const uint32_t nb = (uint32_t)a.hb + 1u;
+  for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
+  __syncthreads();
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (e < (uint64_t)a.n) {
+    const HsEnv h = hs_env(a, (uint32_t)e);
+    if (h.bad || h.H == 0) {
+      a.u_env[e] = h.bad ? HS_BAD : HS_NONE;
+    } else {
+      a.u_env[e] = h.U;
+      atomicAdd(&cnt[h.U], 1u);
+    }
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nb; b += 256)
+    if (cnt[b]) atomicAdd(&a.hist[b], cnt[b]);
+}
+
+// counting sort by U: a block reserves one range per bin, its envs take consecutive places in it; envs without a DP
+// get their outputs here (0 or NaN, an empty bitmap, no alerts)
+__global__ __launch_bounds__(256) void k_hs_scatter(const HsArgs a) {
+  __shared__ uint32_t cnt[HS_BINS];
+  const uint32_t nb = (uint32_t)a.hb + 1u;
+  for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
+  __syncthreads();
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  uint32_t U = e < (uint64_t)a.n ? a.u_env[e] : HS_NONE;
+  if (U == HS_NONE || U == HS_BAD) {
+    if (e < (uint64_t)a.n) {
+      a.ret[e] = U == HS_BAD ? __builtin_nanf("") : 0.0f;
+      a.alerts[e] = 0;
+      for (int w = 0; w < a.mask_words; ++w) a.mask[e * (uint32_t)a.mask_words + w] = 0u;
+    }
+    U = HS_NONE;
+  }
+  const uint32_t rank = U != HS_NONE ? atomicAdd(&cnt[U], 1u) : 0u;
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nb; b += 256)
+    if (cnt[b]) cnt[b] = atomicAdd(&a.cursor[b], cnt[b]);
+  __syncthreads();
+  if (U != HS_NONE) a.order[cnt[U] + rank] = (uint32_t)e;
+}
+
+struct HsCoef {  // the coefficients of the run-time part of both chains (slots 24, 25, 26, 28, 29), fp64
+  double b24, b25, b26, b28, b29, e24, e25, e26, e28, e29;
+};
+// the reward the env pays on a day with static prefixes (pb, pe) and tail (x28, x29, gate), in state (j, streak),
+// for action `act` (1 only where the budget allows it): the chain of the rollout kernels from slot 24 on
+__device__ __forceinline__ float hs_reward(const HsCoef &c, double pb, double pe, float x28, float x29, bool gate,
+                                           bool day0, float streak, int32_t rem, uint32_t act) {
+  const double x24 = (double)((!day0) ? (float)act : 0.0f);
+  const double x25 = (double)streak, x26 = (double)(float)rem, d28 = (double)x28, d29 = (double)x29;
+  double zb = fma(x24, c.b24, pb);
+  zb = fma(x25, c.b25, zb);
+  zb = fma(x26, c.b26, zb);
+  zb = fma(d28, c.b28, zb);
+  zb = fma(d29, c.b29, zb);
+  double ze = -__builtin_inf();  // with no alert the effectiveness does not enter the reward (eff * 0)
+  if (act && gate) {
+    ze = fma(x24, c.e24, pe);
+    ze = fma(x25, c.e25, ze);
+    ze = fma(x26, c.e26, ze);
+    ze = fma(d28, c.e28, ze);
+    ze = fma(d29, c.e29, ze);
+  }
+  return reward_from_logits(zb, ze, act);
+}
+
+__device__ __forceinline__ uint32_t hs_row(uint32_t idx) {  // j of state idx: j (j + 3) / 2 <= idx < (j + 1)(j + 4) / 2
+  uint32_t j = (uint32_t)((__builtin_sqrtf(8.0f * (float)idx + 9.0f) - 3.0f) * 0.5f);
+  while (j > 0 && j * (j + 3u) / 2u > idx) --j;
+  while ((j + 1u) * (j + 4u) / 2u <= idx) ++j;
+  return j;
+}
+
+// one env per 64-lane workgroup; envs list[0 .. gridDim.x) all have this U. GLOBAL: V and the decision words live in
+// `pool` (pool_stride bytes per workgroup) instead of LDS.
+template <bool GLOBAL>
+__global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32_t *list, uint32_t U, char *pool,
+                                                    size_t pool_stride) {
+  extern __shared__ __attribute__((aligned(16))) char hs_lds[];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t e = list[blockIdx.x];
+  const HsEnv h = hs_env(a, e);
+  const uint32_t H = h.H, hb = (uint32_t)a.hb;
+  const uint32_t NCU = hs_nc(U);
+  double2 *pz = reinterpret_cast<double2 *>(hs_lds);               // [hb] prefixes over slots 0..23 (b, e)
+  float4 *tl = reinterpret_cast<float4 *>(hs_lds + 16 * (size_t)hb);  // [hb] x28, x29, gate, -
+  char *dp = GLOBAL ? pool + (size_t)blockIdx.x * pool_stride : hs_lds + hs_day_bytes(hb);
+  double *V0 = reinterpret_cast<double *>(dp);
+  double *V1 = V0 + hs_ns(U);
+  uint64_t *dec = reinterpret_cast<uint64_t *>(V1 + hs_ns(U));     // [hb][NCU]
+
+  // the env's own coefficient rows (wave-uniform), f32 as stored
+  const float4 *wq = a.tb.W + (size_t)h.wrow * (2 * ROWF / 4);
+  // ---- day statics: lanes over days
+  const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
+  for (uint32_t d = lane; d < H; d += HS_BLOCK) {
+    const float4 *xp = a.tb.X + (size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4);
+    double zb = 0.0, ze = 0.0;
+#pragma unroll
+    for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
+      const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
+      zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
+      zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
+      zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
+      zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
+    }
+    const float4 x7 = xp[GATE_QUAD];
+    pz[d] = make_double2(zb, ze);
+    tl[d] = make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
+  }
+  HsCoef c;
+  {
+    const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
+    c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
+    c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
+  }
+  const int32_t rem0 = h.budget - (int32_t)h.used;  // remaining budget at the start; an alert needs j < rem0
+  for (uint32_t i = lane; i < hs_ns(U); i += HS_BLOCK) V1[i] = 0.0;  // V_H = 0
+  __syncthreads();
+
+  // ---- backward DP: V_{d+1} in vn, V_d into vc
+  double *vn = V1, *vc = V0;
+  for (int32_t d = (int32_t)H - 1; d >= 0; --d) {
+    const uint32_t J = min((uint32_t)d, U);
+    const uint32_t nsd = hs_ns(J);
+    const double2 p = pz[d];
+    const float4 tq = tl[d];
+    const bool day0 = (h.t0 + (uint32_t)d) == 0u, gate = tq.z != 0.0f;
+    for (uint32_t c0 = 0; c0 < nsd; c0 += HS_BLOCK) {
+      const uint32_t idx = c0 + lane;
+      const bool valid = idx < nsd;
+      bool alert = false;
+      if (valid) {
+        const uint32_t j = hs_row(idx), k = idx - j * (j + 3u) / 2u;
+        const float s = (float)(k == j + 1u ? h.s0 + j : k);
+        const int32_t rem = h.budget - (int32_t)(h.used + j);
+        const bool allowed = (int32_t)j < rem0;
+        const float r0 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem, 0u);
+        const double q0 = (double)r0 + vn[j * (j + 3u) / 2u];
+        double best = q0;
+        if (allowed) {
+          const float r1 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem - 1, 1u);
+          const double q1 = (double)r1 + vn[(j + 1u) * (j + 4u) / 2u + k + 1u];
+          alert = q1 > q0;
+          best = alert ? q1 : q0;
+        }
+        vc[idx] = best;
+      }
+      const uint64_t bits = __ballot(alert);
+      if (lane == 0) dec[(size_t)d * NCU + c0 / HS_BLOCK] = bits;
+    }
+    __syncthreads();
+    double *tmp = vn; vn = vc; vc = tmp;
+  }
+
+  // ---- backtrack from (0, s0), re-adding the chosen rewards in f32 in day order (every lane the same path)
+  uint32_t j = 0, k = h.s0 > 0 ? 1u : 0u, n_alerts = 0, word = 0;
+  float ret = 0.0f;
+  for (uint32_t d = 0; d < H; ++d) {
+    const uint32_t idx = j * (j + 3u) / 2u + k;
+    const uint32_t act = (uint32_t)(dec[(size_t)d * NCU + (idx >> 6)] >> (idx & 63u)) & 1u;
+    const double2 p = pz[d];
+    const float4 tq = tl[d];
+    const uint32_t tt = h.t0 + d;
+    const float s = (float)(k == j + 1u ? h.s0 + j : k);
+    float r = hs_reward(c, p.x, p.y, tq.x, tq.y, tq.z != 0.0f, tt == 0u, s,
+                        h.budget - (int32_t)(h.used + j + act), act);
+    asm volatile("" : "+v"(r));  // the reward is rounded to f32 before it is added, as in the rollout kernels (no fma)
+    ret += r;
+    if (act && lane == (tt >> 5)) word |= 1u << (tt & 31u);
+    n_alerts += act;
+    j += act;
+    k = act ? k + 1u : 0u;
+  }
+  for (uint32_t w = lane; w < (uint32_t)a.mask_words; w += HS_BLOCK)
+    a.mask[(size_t)e * (uint32_t)a.mask_words + w] = w < HS_BLOCK && w == lane ? word : 0u;
+  if (lane == 0) {
+    a.ret[e] = ret;
+    a.alerts[e] = (int32_t)n_alerts;
+  }
+}
+
+// some coefficient row has a nonzero slot-27 term (the agent's 14-day count): the DP state would not be exact
+__global__ void k_hs_scan_slot27(const float4 *W, int64_t rows, int32_t *flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  if (W[i * (ROWF / 4) + RT_QUAD].w != 0.0f) atomicOr(flag, 1);
+}
+
+#endif  // W2A_HINDSIGHT_HIP_H

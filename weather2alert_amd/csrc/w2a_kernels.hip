@@ -48,6 +48,7 @@
 #include "w2a_rollout_i8.hip.h"
 #include "w2a_rollout_mfma.hip.h"
 #include "w2a_posterior_returns.hip.h"
+#include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
 
 // ----------------------------------------------------------------------------------------
@@ -1070,6 +1071,109 @@ int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint3
   // reads the tables and the caller's arrays only: the handle's state buffer and bookkeeping are not touched
   hipLaunchKernelGGL(k_posterior_returns, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
+  return W2A_OK;
+}
+
+// workspace of w2a_hindsight_optimum: U per env, histogram + cursors of U, env ids by U, then the pool of the bins whose
+// DP does not fit in LDS (big_envs envs of the largest U a horizon of hb days can have)
+static size_t hs_fixed_bytes(int64_t n) { return 2 * align256(4 * (size_t)n) + 2 * align256(4 * HS_BINS); }
+
+size_t w2a_hindsight_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_remaining, int32_t big_envs) {
+  if (!env || n_steps <= 0 || big_envs <= 0) return 0;
+  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
+  const uint32_t u = max_remaining <= 0 ? 0u : min((uint32_t)max_remaining, hb);
+  // the pool only for a U whose DP does not fit in LDS (a larger U than the batch's never occurs)
+  const bool pool = hs_day_bytes(hb) + hs_dp_bytes(u, hb) > HS_LDS_CAP;
+  return hs_fixed_bytes(env->n) + (pool ? (size_t)big_envs * align256(hs_dp_bytes(u, hb)) : 0);
+}
+
+int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                          uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine)
+  if (!start || !ret_out || !alert_mask || !alerts_out || !workspace)
+    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: NULL argument");
+  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
+      !start->year_i || !start->coef_col || !start->sample || !start->finished)
+    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: NULL start-state array (t, used, streak, budget, n_days, county_w, "
+                             "year_i, coef_col, sample and finished are read)");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: n_steps must be positive");
+  if (mask_words <= 0) return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: mask_words must be positive");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: NULL handle");
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: alert_mask needs ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: not available with corrected-semantics flags (the reward then "
+                             "depends on attempts and on the 14-day window)");
+  REFUSE_WHILE_CAPTURING("w2a_hindsight_optimum", stream);
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t n = env->n;
+  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
+  if (workspace_bytes < hs_fixed_bytes(n))
+    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: workspace smaller than w2a_hindsight_workspace_bytes(env, n_steps, "
+                             "0, 1)");
+  char *ws = reinterpret_cast<char *>(workspace);
+  {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
+    int32_t *flag = reinterpret_cast<int32_t *>(ws);
+    const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
+    HIP_TRY(hipGetLastError());
+    int32_t used27 = 1;
+    HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (used27)
+      return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
+                               "agent): the (alerts, streak) DP would not be exact");
+  }
+  HsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.mask_words = mask_words; a.n = n;
+  a.ret = ret_out; a.mask = alert_mask; a.alerts = alerts_out;
+  a.u_env = reinterpret_cast<uint32_t *>(ws);
+  a.order = reinterpret_cast<uint32_t *>(ws + align256(4 * (size_t)n));
+  a.hist = reinterpret_cast<uint32_t *>(ws + 2 * align256(4 * (size_t)n));
+  a.cursor = a.hist + HS_BINS;
+  char *pool = ws + hs_fixed_bytes(n);
+  const size_t pool_bytes = workspace_bytes - hs_fixed_bytes(n);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * HS_BINS, s));
+  hipLaunchKernelGGL(k_hs_plan, dim3(grid), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  uint32_t hist[HS_BINS], off[HS_BINS];
+  HIP_TRY(hipMemcpyAsync(hist, a.hist, 4 * (hb + 1), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  uint32_t acc = 0;
+  for (uint32_t u = 0; u <= hb; ++u) { off[u] = acc; acc += hist[u]; }
+  // bins that do not fit in LDS: the pool must hold one env of the largest of them (checked before any output is
+  // written: k_hs_plan writes none)
+  for (uint32_t u = 0; u <= hb; ++u)
+    if (hist[u] && hs_day_bytes(hb) + hs_dp_bytes(u, hb) > HS_LDS_CAP && pool_bytes < align256(hs_dp_bytes(u, hb)))
+      return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: workspace too small for the largest budget in the batch "
+                               "(w2a_hindsight_workspace_bytes(env, n_steps, max(budget - used), 1) suffices)");
+  HIP_TRY(hipMemcpyAsync(a.cursor, off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t u = 0; u <= hb; ++u) {
+    if (!hist[u]) continue;
+    const size_t need = hs_day_bytes(hb) + hs_dp_bytes(u, hb);
+    if (need <= HS_LDS_CAP) {
+      hipLaunchKernelGGL(k_hs_dp<false>, dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
+      HIP_TRY(hipGetLastError());
+    } else {
+      const size_t stride = align256(hs_dp_bytes(u, hb));
+      const size_t fit = pool_bytes / stride;
+      const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
+      for (uint32_t i = 0; i < hist[u]; i += per) {
+        const uint32_t cnt = min(per, hist[u] - i);
+        hipLaunchKernelGGL(k_hs_dp<true>, dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, a, a.order + off[u] + i, u,
+                           pool, stride);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+  }
+  // the cursor upload reads `off` from this frame: it must have left before the function returns
+  HIP_TRY(hipStreamSynchronize(s));
   return W2A_OK;
 }
 

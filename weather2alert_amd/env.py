@@ -775,7 +775,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
 
     # ------------------------------------------------------------------ rollout
     def rollout(self, policy: dict, n_steps: int | None = None, alert_mask: bool = False, record: bool = False,
-                posterior_returns: bool = False) -> dict:
+                posterior_returns: bool = False, hindsight: bool = False) -> dict:
         """Run a built-in policy inside the kernel for ``n_steps`` days (default: to the end of the episode)
         without returning to Python between days (replaces loops like env.py:265-277). With
         reward_mode="posterior_mean" the whole rollout is one launch of k_pm_rollout (vector kernel, <= 112 posterior
@@ -833,7 +833,12 @@ class HeatAlertVecEnv(_VectorEnvBase):
         for bit "return" for the fp64-chain rollout kernels, within 2e-6 relative for k_rollout_mfma. The linear and mlp
         kinds also return "group_posterior_returns" f32 [G, n_samples], the mean over each group's envs per draw (one
         posterior sample of the group's value per column; stats.posterior_summary, stats.prob_better). Nothing else the
-        call returns or leaves behind changes. Faithful semantics only (fixes other than "budget": ValueError)."""
+        call returns or leaves behind changes. Faithful semantics only (fixes other than "budget": ValueError).
+        hindsight=True (every kind, combinable with record and posterior_returns) also returns "hindsight_return" f32
+        [N]: the return of each env's best alert schedule over the same days from the same start state
+        (hindsight_optimum(), the yardstick that turns "return" into regret); the linear and mlp kinds also return
+        "group_hindsight_return" f32 [G]. Nothing else the call returns or leaves behind changes. Sampled reward and
+        faithful semantics only (ValueError otherwise, and for tables with a nonzero slot-27 coefficient)."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         ct = self.ct
@@ -844,6 +849,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if posterior_returns and self.fixes - {"budget"}:
             raise ValueError(f"rollout(posterior_returns=True) needs faithful semantics; fixes "
                              f"{sorted(self.fixes - {'budget'})} make the reward depend on attempts and other rows")
+        if hindsight:
+            self._check_hindsight("rollout(hindsight=True)")
         if kind in ("linear", "mlp"):  # every argument is checked before anything runs
             if self._pm:
                 raise ValueError(f"rollout(kind={kind!r}) needs reward_mode='sampled'")
@@ -860,11 +867,11 @@ class HeatAlertVecEnv(_VectorEnvBase):
             raise RuntimeError(f"rollout(kind={kind!r}) reads the observation buffer, which does not hold the agents' "
                                "current rows (write_obs=False, a built-in rollout or load_state_dict since the last "
                                "step()/reset()): call step() or reset() first")
-        pr = bool(posterior_returns)
+        pr, hs = bool(posterior_returns), bool(hindsight)
         if kind == "mlp":
-            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr)
+            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr, hs)
         if lin is not None:
-            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr)
+            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr, hs)
         p = _ffi.Policy()
         p.kind = _ffi.POLICY_KINDS[kind]
         p.p = float(policy.get("p", 0.0))
@@ -882,21 +889,23 @@ class HeatAlertVecEnv(_VectorEnvBase):
             if keep.dim() != 2 or keep.shape[0] < ct.T:
                 raise ValueError(f"policy table must be [T >= {ct.T}, R]")
             p.table, p.table_R = keep.data_ptr(), int(keep.shape[1])
-        return self._rollout_run(p, None, n_steps, alert_mask, keep, posterior_returns=pr)
+        return self._rollout_run(p, None, n_steps, alert_mask, keep, posterior_returns=pr, hindsight=hs)
 
-    def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False) -> dict:
+    def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False) -> dict:
         """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
         lp = _ffi.LinearPolicy()
         lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
         lp.group = None if lin.group is None else lin.group.data_ptr()
         lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
-        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns)
+        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns, hindsight)
         out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
         if posterior_returns:
             out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], lin.group, lin.n_groups)
+        if hindsight:
+            out["group_hindsight_return"] = _policy.group_mean(out["hindsight_return"], lin.group, lin.n_groups)
         return out
 
-    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False) -> dict:
+    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False) -> dict:
         """rollout(kind="mlp"): w2a_rollout_mlp on the checked, packed policy (weather2alert_amd/policy.py)."""
         mp = _ffi.MlpPolicy()
         mp.params = mlp.params.data_ptr()
@@ -905,17 +914,21 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mp.n_groups, mp.n_layers, mp.width = mlp.n_groups, mlp.n_layers, mlp.width
         mp.activation = _ffi.MLP_ACTIVATIONS[mlp.activation]
         mp.sample, mp.require_budget, mp.seed = int(mlp.sample), int(mlp.require_budget), mlp.seed
-        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns)
+        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns, hindsight)
         out["group_mean_return"] = _policy.group_mean(out["return"], mlp.group, mlp.n_groups)
         if posterior_returns:
             out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], mlp.group, mlp.n_groups)
+        if hindsight:
+            out["group_hindsight_return"] = _policy.group_mean(out["hindsight_return"], mlp.group, mlp.n_groups)
         return out
 
-    def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False, posterior_returns=False) -> dict:
+    def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False, posterior_returns=False,
+                     hindsight=False) -> dict:
         """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
         linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True).
         posterior_returns: the alert bitmap is taken in any case (the rollout kernels' results do not depend on it) and
-        w2a_posterior_returns runs on it and the start state right after the rollout."""
+        w2a_posterior_returns runs on it and the start state right after the rollout. hindsight: w2a_hindsight_optimum on
+        the same start state and days."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -926,7 +939,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mask = torch.empty((n, words), dtype=torch.int32, device=dev) if (alert_mask or posterior_returns) else None
         amask = torch.empty((n, words), dtype=torch.int32, device=dev) if alert_mask else None
         snap = torch.full((n,), float("nan"), dtype=torch.float32, device=dev) if alert_mask else None
-        st0 = self.state() if (alert_mask or self._pm or posterior_returns) else None
+        st0 = self.state() if (alert_mask or self._pm or posterior_returns or hindsight) else None
         traj = tr = None
         if record:  # lp is not None: rollout() refuses record=True for the other kinds
             traj = {"obs": torch.empty((steps + 1, n, ct.n_obs), dtype=torch.float32, device=dev),
@@ -972,6 +985,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                  None if snap is None else snap.data_ptr(), self._stream()), "w2a_rollout")
             if posterior_returns:
                 out["posterior_returns"] = self._posterior_returns_packed(st0, mask, words, steps)
+            if hindsight:
+                out["hindsight_return"] = self._hindsight_packed(st0, steps)[0]
         self._keep_pol = keep
         self._obs_current = lp is not None  # built-in policies write no observation rows (a reset below may)
         # only what this call returns is decoded (sixteen arrays of N int32 otherwise: 64 MB of writes at 1 M envs)
@@ -1045,6 +1060,81 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                    self._stream()), "w2a_posterior_returns")
         return out
 
+    # ------------------------------------------------------------------ hindsight optimum
+    def hindsight_optimum(self, start_state: dict | None = None, n_steps: int | None = None) -> dict:
+        """Every env's best alert schedule in hindsight: knowing the weather of the whole stretch, the env's own
+        posterior draw and its remaining budget, the schedule of at most budget - used alerts with the highest return
+        over the days from start_state (a state() dict; default: the current state) for n_steps days (default: to the
+        end of every episode; each env stops after its terminal day, as in rollout()). The upper bound a policy's return
+        reads against as regret, and an expert schedule for imitation. Returns
+            "return":     f32 [N]     the schedule's return: bit for bit what the env pays when stepped with it
+                                      (posterior_returns(start_state, alert_days)[:, sample])
+            "alert_days": bool [N, T] the schedule (day of the episode; only the stretch's days can be set)
+            "alerts":     i32 [N]     alerts in it
+        Envs finished in start_state give 0 and an empty schedule. An exact DP over (alerts issued, current streak)
+        (w2a_hindsight_optimum, include/w2a.h); ties do not alert. Reads start_state and the tables only: the env's
+        state, observation buffer and bookkeeping are untouched. Sampled reward and faithful semantics only; tables
+        whose slot-27 (alert_2wks of the agent) coefficient is nonzero are refused (ValueError)."""
+        self._check_hindsight("hindsight_optimum()")
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if start_state is None:
+            st = self._state_packed(_HS_FIELDS)[1]
+        else:
+            st = {}
+            for k in _HS_FIELDS:
+                if k not in start_state:
+                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
+                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
+                if st[k].shape != (n,):
+                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
+        steps = int(n_steps) if n_steps is not None else ct.T
+        if steps <= 0:
+            raise ValueError("n_steps must be positive")
+        with torch.cuda.device(dev):
+            ret, mask, alerts = self._hindsight_packed(st, steps)
+        words = mask.shape[1]
+        bits = torch.arange(32, device=dev, dtype=torch.int32)
+        days = (((mask.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()
+        return {"return": ret, "alert_days": days, "alerts": alerts}
+
+    def _check_hindsight(self, who: str):
+        if self.fixes - {"budget"}:
+            raise ValueError(f"{who} needs faithful semantics; fixes {sorted(self.fixes - {'budget'})} make the reward "
+                             "depend on attempts and on the 14-day window")
+        if self._pm:
+            raise ValueError(f"{who} needs reward_mode='sampled', not 'posterior_mean': that env pays the mean over "
+                             "draws, so an optimum under the env's own draw is not its yardstick")
+        dt = self.dtables
+        if getattr(dt, "_slot27_zero", None) is None:  # once per table
+            dt._slot27_zero = not bool(np.any(np.asarray(self.ct.W).reshape(-1, 2, 32)[:, :, 27] != 0))
+        if not dt._slot27_zero:
+            raise ValueError(f"{who}: some coefficient row has a nonzero slot-27 (alert_2wks of the agent) term; the "
+                             "(alerts, streak) DP is exact only without it")
+
+    def _hindsight_packed(self, st0: dict, steps: int):
+        """w2a_hindsight_optimum on device int32 state arrays: (return f32 [N], packed bitmap i32 [N, words],
+        alerts i32 [N])."""
+        n, dev = self.num_envs, self.device
+        words = (self.ct.T + 31) // 32
+        ret = torch.empty(n, dtype=torch.float32, device=dev)
+        mask = torch.empty((n, words), dtype=torch.int32, device=dev)
+        alerts = torch.empty(n, dtype=torch.int32, device=dev)
+        # one host reduction: the pool for DPs beyond LDS is sized for the batch's largest remaining budget (none at
+        # the tables' default budgets)
+        live = (st0["finished"] == 0) & (st0["t"] < st0["n_days"])
+        rem = 0
+        if n and not torch.cuda.is_current_stream_capturing():  # (a capture is refused by the library itself)
+            rem = int(torch.where(live, st0["budget"] - st0["used"], 0).max().item())
+        ws_bytes = self._lib.w2a_hindsight_workspace_bytes(self._h, steps, max(0, min(rem, 1 << 30)), _HS_BIG_ENVS)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        v = _ffi.StateView()
+        for k in _HS_FIELDS:
+            setattr(v, k, st0[k].data_ptr())
+        _ffi.check(self._lib.w2a_hindsight_optimum(self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words,
+                                                   alerts.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()),
+                   "w2a_hindsight_optimum")
+        return ret, mask, alerts
+
     def _rollout_posterior_mean(self, p, steps, out, mask, amask, words, snap, st0) -> int:
         """rollout() with reward_mode="posterior_mean": one launch of k_pm_rollout when it applies, else per day
         w2a_policy_actions (the policy and counters of k_rollout), w2a_posterior_mean_reward, w2a_step(REWARD_GIVEN |
@@ -1116,6 +1206,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
 
 # the start-state fields w2a_posterior_returns reads
 _PR_FIELDS = ("t", "used", "streak", "hist14", "budget", "n_days", "county_w", "year_i", "coef_col", "finished")
+# the start-state fields w2a_hindsight_optimum reads, and how many envs beyond the LDS budget one launch serves
+_HS_FIELDS = ("t", "used", "streak", "budget", "n_days", "county_w", "year_i", "coef_col", "sample", "finished")
+_HS_BIG_ENVS = 64
 
 
 def __getattr__(name):  # weather2alert_amd.env.HeatAlertEnv: the drop-in lives in dropin.py (it builds on this module)
