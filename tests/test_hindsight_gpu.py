@@ -1,7 +1,9 @@
 """The hindsight optimum on the GPU (w2a_hindsight_optimum): schedules against brute force and the fp64 DP
 restatement (tests/hindsight_restatement.py), bit-identity of the return with posterior_returns and agreement with
 step() driven by the schedule, dominance over every policy kind at full size, budget 0 and budgets far beyond the
-tables' defaults, no side effects, refusals."""
+tables' defaults, no side effects, refusals.
+Uniform tables only; the same kernel on ragged episode lengths and slot-27 coefficient rows:
+tests/test_table_edges_gpu.py."""
 import ctypes as C
 import os
 import sys

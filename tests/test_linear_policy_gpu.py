@@ -1,6 +1,8 @@
 """rollout(kind="linear") on the GPU (k_rollout_linear): against the vector oracle's `a = policy(obs); step(a)` loop,
 against the env's own step() loop, against the built-in policies it contains as special cases, its refusals, and at
-full size."""
+full size.
+Uniform tables only; the same kernel on ragged episode lengths and slot-27 coefficient rows:
+tests/test_table_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch

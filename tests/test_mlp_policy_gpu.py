@@ -1,6 +1,8 @@
 """rollout(kind="mlp") on the GPU (k_rollout_mlp): against the vector oracle's `a = mlp(obs); step(a)` loop in fp64,
 against the env's own step() loop, against rollout(kind="linear") as a special case, bit-identical across visiting
-orders and group layouts, its refusals, and at full size."""
+orders and group layouts, its refusals, and at full size.
+Uniform tables only; the same kernel on ragged episode lengths and slot-27 coefficient rows:
+tests/test_table_edges_gpu.py."""
 import ctypes as C
 
 import numpy as np

@@ -1,7 +1,9 @@
 """Returns under every posterior draw on the GPU (k_posterior_returns): against the reference's per-draw rewards
 (tests/golden/posterior_draws.npz), bit-identity of each env's own draw with the rollout's return, every column against
 the fp64 restatement (tests/posterior_restatement.py), partial and chained calls, unchanged outputs, the
-posterior-mean env, group means, refusals, and full size."""
+posterior-mean env, group means, refusals, and full size.
+Uniform tables only; the same kernel on ragged episode lengths and slot-27 coefficient rows:
+tests/test_table_edges_gpu.py."""
 import ctypes as C
 import json
 import os

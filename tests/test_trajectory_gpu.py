@@ -1,6 +1,8 @@
 """rollout(kind="linear" | "mlp", record=True) on the GPU: the recorded trajectory against the vector oracle's
 `a = policy(obs); step(a)` loop and against the env's own step() loop, recording changing nothing else, chaining,
-order independence, the MLP against torch, refusals and full size."""
+order independence, the MLP against torch, refusals and full size.
+Uniform tables only; the same kernel on ragged episode lengths and slot-27 coefficient rows:
+tests/test_table_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
