@@ -489,6 +489,45 @@ size_t w2a_hindsight_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_
 int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
                           uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
                           size_t workspace_bytes, void *stream);
+/* The score-function (REINFORCE) gradient, with reward-to-go, of the rollout that w2a_rollout_linear(env, policy,
+ * n_steps, obs, ...) with sample = 1 would run from the handle's CURRENT state and observation rows: call it right
+ * before that rollout, with the same policy, n_steps and obs. It reads the state, the tables and obs and modifies none of
+ * them, nor the handle's bookkeeping beyond making the canonical state words current (which the rollout does anyway).
+ * The estimator, for env e of group g over the call-days s = 0 .. S_e - 1 on which the env takes a step:
+ *   o_s      the observation row the agent holds before decision s (slab s of w2a_rollout_linear_record)
+ *   z_s      = weight[g] . o_s + bias[g], the fp64 logit of that decision;  p_s = sigmoid(z_s) in f32, as the rollout's
+ *   a_s      the policy's own draw, u < p_s
+ *   m_s      0 on a day where require_budget forced the action to 0 because no budget was left (the action is off the
+ *            policy's distribution there), else 1; without require_budget an attempt at the budget counts (m_s = 1)
+ *   delta_s  = m_s (a_s - p_s): d log pi(a_s | o_s) / d z_s
+ *   A_s      = r_s - beta_s, r_s the reward w2a_step returns for that day; beta_s = 0 (W2A_PG_BASELINE_NONE) or
+ *            (W2A_PG_BASELINE_NO_ALERT) the reward the same env would have been paid on that day had no alert been
+ *            issued from the call's first day on, starting from the call's start state: alert_lag1 = 0, the streak of
+ *            the start state on the first day and 0 after it, the 14-day window decaying, the remaining budget frozen
+ *            at its start value. It depends on nothing the policy does inside the call, so it is a valid baseline for
+ *            every earlier score. ("Today's reward without today's alert" would not be: today's state depends on
+ *            earlier actions.)
+ *   Q_s      = sum over s' >= s of A_s': undiscounted reward-to-go over the env's days of THIS call -- a chunk that
+ *            ends before the episode does is truncated, nothing is bootstrapped past its last day
+ *   g_e      = sum_s delta_s Q_s (o_s, 1);  envs finished on entry get a row of zeros
+ * grad (device f32 [n_obs + 1][num_envs], column-major: component j of env e at j * num_envs + e) receives g_e: the
+ * weight columns in OBSERVATION order, the bias last. The mean of g_e over a group's envs estimates the gradient of that
+ * group's mean return with respect to its parameter row.
+ * Numerics contract: u, z_s, p_s and r_s are computed by the statements of k_rollout_linear (same uniform, same fp64 FMA
+ * chains: bias first, slots 0..29 in slot order; same f32 sigmoids; reward_from_logits), so they are the values the
+ * rollout then uses; beta_s continues the baseline chain of the played day after slot 23 over the fork's slots 24..29
+ * and goes through reward_from_logits; delta_s and A_s are f32, Q_s and the sums over s fp64, g_e rounded to f32 once.
+ * An env's g_e does not depend on the other envs, the group layout or the visiting order (bit for bit): reduce them
+ * over groups in any fixed order for a deterministic gradient.
+ *   baseline    W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT
+ *   workspace   device memory of w2a_policy_gradient_workspace_bytes(num_envs, n_steps) bytes, 256-B aligned: 9 B per
+ *               env-day (delta_s, A_s and the alert issued); no observation row is written or read per day
+ * W2A_ERR_ARG where w2a_rollout_linear refuses (checked in the same order), for sample != 1, an unknown baseline, a NULL
+ * grad or workspace and a workspace too small or misaligned; W2A_ERR_STATE while `stream` is recording a hipGraph. */
+enum { W2A_PG_BASELINE_NONE = 0, W2A_PG_BASELINE_NO_ALERT = 1 };
+size_t w2a_policy_gradient_workspace_bytes(int64_t num_envs, int32_t n_steps);
+int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
+                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

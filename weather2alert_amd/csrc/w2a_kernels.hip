@@ -48,6 +48,7 @@
 #include "w2a_rollout_i8.hip.h"
 #include "w2a_rollout_mfma.hip.h"
 #include "w2a_posterior_returns.hip.h"
+#include "w2a_policy_gradient.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1042,6 +1043,77 @@ int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n
   if (rc != W2A_OK) return rc;
   return rollout_mlp(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
                      mask_words, last_return, ret_snapshot, stream, traj);
+}
+
+// scratch of w2a_policy_gradient_linear: (delta_s, A_s) and the alert issued, per (call-day, env)
+size_t w2a_policy_gradient_workspace_bytes(int64_t num_envs, int32_t n_steps) {
+  if (num_envs <= 0 || n_steps <= 0) return 0;
+  const size_t days = (size_t)num_envs * (size_t)n_steps;
+  return align256(sizeof(float2) * days) + align256(days);
+}
+
+int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
+                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
+  if (!policy) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL policy");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: n_steps must be positive");
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL weight or bias");
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: n_groups must be positive");
+  if (policy->sample != 1)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: sample must be 1 (a deterministic policy has no score function)");
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: require_budget must be 0 or 1");
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: weight must be 16-B aligned");
+  if (baseline != W2A_PG_BASELINE_NONE && baseline != W2A_PG_BASELINE_NO_ALERT)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT");
+  if (!obs) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL obs (the rows the agent holds are the first day's input)");
+  if (!grad || !workspace) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL grad or workspace");
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: workspace must be 256-B aligned");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL handle");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: not available with corrected-semantics flags (they change what "
+                             "the observation is)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  if (workspace_bytes < w2a_policy_gradient_workspace_bytes(env->n, n_steps))
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: workspace smaller than w2a_policy_gradient_workspace_bytes");
+  REFUSE_WHILE_CAPTURING("w2a_policy_gradient_linear", stream);
+  PolicyGradArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  LinearRolloutArgs &la = ga.l;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_policy_gradient_linear: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    la.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = la.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.pol.seed = policy->seed;
+  a.n_steps = n_steps;
+  a.order = env->order;
+  la.weight = reinterpret_cast<const float4 *>(policy->weight);
+  la.bias = policy->bias;
+  la.group = policy->group;
+  la.n_groups = policy->n_groups;
+  la.n_obs = env->tb.n_obs;
+  la.obs_mask = obs_mask;
+  la.obs = const_cast<float *>(obs);  // the kernel only reads it
+  ga.baseline = baseline;
+  ga.day = reinterpret_cast<float2 *>(workspace);
+  ga.day_alert = reinterpret_cast<uint8_t *>(workspace) + align256(sizeof(float2) * (size_t)env->n * (size_t)n_steps);
+  ga.grad = grad;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words (the rollout that follows would make them current itself); changes nothing else
+  if (!ensure_canonical(env, s, "w2a_policy_gradient_linear")) return W2A_ERR_STATE;
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  hipLaunchKernelGGL(k_policy_gradient_linear, dim3(g64), dim3(BLOCK), 0, s, ga);
+  HIP_TRY(hipGetLastError());
+  return W2A_OK;
 }
 
 int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint32_t *alert_mask, int32_t mask_words,

@@ -775,7 +775,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
 
     # ------------------------------------------------------------------ rollout
     def rollout(self, policy: dict, n_steps: int | None = None, alert_mask: bool = False, record: bool = False,
-                posterior_returns: bool = False, hindsight: bool = False) -> dict:
+                posterior_returns: bool = False, hindsight: bool = False,
+                policy_gradient: bool | str = False) -> dict:
         """Run a built-in policy inside the kernel for ``n_steps`` days (default: to the end of the episode)
         without returning to Python between days (replaces loops like env.py:265-277). With
         reward_mode="posterior_mean" the whole rollout is one launch of k_pm_rollout (vector kernel, <= 112 posterior
@@ -838,7 +839,29 @@ class HeatAlertVecEnv(_VectorEnvBase):
         [N]: the return of each env's best alert schedule over the same days from the same start state
         (hindsight_optimum(), the yardstick that turns "return" into regret); the linear and mlp kinds also return
         "group_hindsight_return" f32 [G]. Nothing else the call returns or leaves behind changes. Sampled reward and
-        faithful semantics only (ValueError otherwise, and for tables with a nonzero slot-27 coefficient)."""
+        faithful semantics only (ValueError otherwise, and for tables with a nonzero slot-27 coefficient).
+        policy_gradient="none" | "no_alert" | True (= "no_alert"); kind="linear" with sample=True only -- ValueError for
+        sample=False, every other kind, reward_mode="posterior_mean", fixes other than "budget", an unknown string, and
+        together with record=True (a recorded trajectory already holds everything a learner needs); combinable with
+        alert_mask, posterior_returns and hindsight. Also returns "policy_gradient": {"weight": f32 [G, n_obs] (columns
+        in observation order, like policy["weight"]), "bias": f32 [G]}, the reward-to-go score-function (REINFORCE)
+        estimate of the gradient of each group's mean "return", so ``W += lr * out["policy_gradient"]["weight"]`` is an
+        ascent step (NaN rows for a group without envs). Per env e, over the call-days s on which it took a step:
+          g_e = sum_s delta_s Q_s (o_s, 1),   delta_s = m_s (a_s - sigmoid(z_s)),   Q_s = sum_{s' >= s} (r_s' - beta_s')
+        with o_s the row held before decision s, z_s its fp64 logit, a_s the policy's own draw, m_s = 0 on a day where
+        require_budget forced the action to 0 with no budget left (off the policy's distribution; without require_budget
+        an attempt at the budget counts), r_s the day's reward; beta_s = 0 ("none") or ("no_alert") the reward the same
+        env would have been paid that day had no alert been issued from the call's first day on, from the call's start
+        state (alert_lag1 0, the start streak on the first day then 0, the 14-day window decaying, the budget frozen):
+        independent of everything the policy does in the call, so a valid baseline for every earlier score, and it
+        removes the large action-independent part of the reward. Undiscounted; Q_s stops at the call's last day -- a
+        chunk shorter than the episode is truncated, nothing is bootstrapped. The group's gradient is the mean of g_e
+        over its envs; envs finished on entry contribute zero and count. w2a_policy_gradient_linear (include/w2a.h)
+        runs right before the rollout on the same state and rows, with the rollout's own statements for u, z_s and
+        r_s; no observation row goes to memory per day (9 B of scratch per env-day). Deterministic: two identical calls
+        return bit-identical gradients. Nothing else the call returns or leaves behind changes, bit for bit."""
+        pg = _policy.check_policy_gradient(policy_gradient, policy.get("kind"), policy.get("sample", False),
+                                           self.reward_mode, self.fixes, record)
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         ct = self.ct
@@ -871,7 +894,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if kind == "mlp":
             return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr, hs)
         if lin is not None:
-            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr, hs)
+            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr, hs, pg)
         p = _ffi.Policy()
         p.kind = _ffi.POLICY_KINDS[kind]
         p.p = float(policy.get("p", 0.0))
@@ -891,18 +914,23 @@ class HeatAlertVecEnv(_VectorEnvBase):
             p.table, p.table_R = keep.data_ptr(), int(keep.shape[1])
         return self._rollout_run(p, None, n_steps, alert_mask, keep, posterior_returns=pr, hindsight=hs)
 
-    def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False) -> dict:
+    def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
+                        policy_gradient=None) -> dict:
         """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
         lp = _ffi.LinearPolicy()
         lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
         lp.group = None if lin.group is None else lin.group.data_ptr()
         lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
-        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns, hindsight)
+        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns, hindsight, policy_gradient)
         out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
         if posterior_returns:
             out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], lin.group, lin.n_groups)
         if hindsight:
             out["group_hindsight_return"] = _policy.group_mean(out["hindsight_return"], lin.group, lin.n_groups)
+        if policy_gradient is not None:
+            # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
+            g = _policy.group_mean_columns(out.pop("_policy_gradient_env"), lin.group, lin.n_groups)
+            out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
         return out
 
     def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False) -> dict:
@@ -923,12 +951,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return out
 
     def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False, posterior_returns=False,
-                     hindsight=False) -> dict:
+                     hindsight=False, policy_gradient=None) -> dict:
         """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
         linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True).
         posterior_returns: the alert bitmap is taken in any case (the rollout kernels' results do not depend on it) and
         w2a_posterior_returns runs on it and the start state right after the rollout. hindsight: w2a_hindsight_optimum on
-        the same start state and days."""
+        the same start state and days. policy_gradient ("none" / "no_alert", linear only): w2a_policy_gradient_linear
+        right before the rollout, on the state and the rows the rollout starts from; its per-env rows come back as
+        "_policy_gradient_env" f32 [n_obs + 1, N]."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -965,6 +995,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
                             n, ct.S_w * ct.Y, ct.S, ct.n_samples), dtype=torch.uint8, device=dev)
                     _ffi.check(self._lib.w2a_rollout_mfma_prepare(self._h, self._mfma_ws.data_ptr(), self._mfma_ws.numel(),
                                                                   self._stream()), "w2a_rollout_mfma_prepare")
+            if policy_gradient is not None:
+                out["_policy_gradient_env"] = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
+                ws = torch.empty(self._lib.w2a_policy_gradient_workspace_bytes(n, steps), dtype=torch.uint8, device=dev)
+                _ffi.check(self._lib.w2a_policy_gradient_linear(
+                    self._h, C.byref(lp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
+                    out["_policy_gradient_env"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                    "w2a_policy_gradient_linear")
             if lp is not None:
                 fn = "w2a_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_rollout_linear"
                 args = (self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),

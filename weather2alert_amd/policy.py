@@ -111,6 +111,38 @@ def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, devic
                             int(seed) & (2**64 - 1), bool(rb))
 
 
+PG_BASELINES = ("none", "no_alert")
+
+
+def check_policy_gradient(policy_gradient, kind, sample, reward_mode="sampled", fixes=(), record=False):
+    """The ``policy_gradient`` keyword of ``rollout()``: None when it is off (False), else the baseline's name ("none" or
+    "no_alert"; True means "no_alert"). ValueError for everything the gradient kernel does not serve: a kind other
+    than "linear", sample=False (a deterministic policy has no score function), reward_mode="posterior_mean", fixes
+    other than "budget", record=True (take one or the other per call) and an unknown baseline."""
+    if policy_gradient is False or policy_gradient is None:
+        return None
+    if policy_gradient is True:
+        policy_gradient = "no_alert"
+    if not isinstance(policy_gradient, str) or policy_gradient not in PG_BASELINES:
+        raise ValueError(f"rollout(policy_gradient=...) must be False, True or one of {PG_BASELINES}, "
+                         f"got {policy_gradient!r}")
+    if kind != "linear":
+        raise ValueError(f"rollout(policy_gradient=...) needs kind 'linear', got {kind!r}")
+    if not isinstance(sample, (bool, np.bool_)) or not sample:
+        raise ValueError("rollout(policy_gradient=...) needs a sampled policy (sample=True): a deterministic policy "
+                         "has no score function")
+    if reward_mode != "sampled":
+        raise ValueError("rollout(policy_gradient=...) needs reward_mode='sampled'")
+    extra = set(fixes) - {"budget"}
+    if extra:
+        raise ValueError(f"rollout(policy_gradient=...) needs faithful observations; fixes {sorted(extra)} change what "
+                         "the observation is")
+    if record:
+        raise ValueError("rollout(policy_gradient=...) and record=True are not combined: a recorded trajectory already "
+                         "holds everything a learner needs")
+    return policy_gradient
+
+
 def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) -> torch.Tensor:
     """f32 [n_groups] (values [N]) or [n_groups, K] (values [N, K], e.g. returns under K posterior draws): the mean of
     `values` over each group's envs, per column (NaN for a group without envs), on the device of `values`: the groups'
@@ -129,6 +161,21 @@ def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) 
     hi = torch.searchsorted(sg, ids, right=True)
     cnt = (hi - lo).to(torch.float64).reshape((n_groups,) + (1,) * (values.dim() - 1))
     return ((csum[hi] - csum[lo]) / cnt).to(torch.float32)
+
+
+def group_mean_columns(values_t: torch.Tensor, group: torch.Tensor | None, n_groups: int) -> torch.Tensor:
+    """group_mean for K values per env stored column-major: values_t [K, N] -> f32 [n_groups, K]. The same sort and fp64
+    prefix sum, but the scan runs along memory (one row of N per column); down the rows of an [N, K] array it measured
+    410 ms at 1 048 576 envs, K = 30 and G = 1024. A fixed summation order: identical inputs give identical bits."""
+    if group is None:
+        return values_t.to(torch.float64).mean(1)[None, :].to(torch.float32)
+    sg, perm = torch.sort(group.to(torch.int32), stable=True)
+    csum = torch.cumsum(values_t.to(torch.float64)[:, perm], dim=1)
+    csum = torch.cat([torch.zeros((values_t.shape[0], 1), dtype=torch.float64, device=values_t.device), csum], dim=1)
+    ids = torch.arange(n_groups, dtype=torch.int32, device=values_t.device)
+    lo = torch.searchsorted(sg, ids, right=False)
+    hi = torch.searchsorted(sg, ids, right=True)
+    return ((csum[:, hi] - csum[:, lo]) / (hi - lo).to(torch.float64)[None, :]).T.contiguous().to(torch.float32)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
