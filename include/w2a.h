@@ -528,6 +528,33 @@ enum { W2A_PG_BASELINE_NONE = 0, W2A_PG_BASELINE_NO_ALERT = 1 };
 size_t w2a_policy_gradient_workspace_bytes(int64_t num_envs, int32_t n_steps);
 int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
                                const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream);
+/* The same estimator for w2a_rollout_mlp(env, policy, n_steps, obs, ...) with sample = 1, already reduced per group:
+ * z_s is the f32 logit k_rollout_mlp computes for o_s (the same bits: pass 1 is that kernel's day loop), dz_s/dtheta the
+ * backward pass of the f32 network (the ReLU derivative is 0 at a pre-activation of exactly 0), delta_s, A_s, Q_s and the
+ * baselines as above, and
+ *     grad[g] = (1 / N_g) sum over the envs e of group g of  sum_s delta_s Q_s dz_s/dtheta(theta_g),
+ * N_g the number of envs of group g (envs finished on entry contribute zero and count; a group without envs gives a
+ * block of NaN). Call it right before that rollout, with the same policy, n_steps and obs; it reads the state, the tables
+ * and obs and modifies none of them, nor the handle's bookkeeping beyond making the canonical state words current.
+ *   grad        device f32 [n_groups][W2A_MLP_STRIDE(width, n_layers)]: every block in the layout of `params` (rows of
+ *               W1 on non-observation slots, padding units and the three trailing floats are zero)
+ *   policy->order  the visiting order of THESE kernels (they write no state, so it need not be the rollout's): pass the
+ *               env ids stably sorted by group (NULL = identity order: right for n_groups == 1). The workspace holds one
+ *               partial block per wave and one per group boundary of a group-major order; an order that changes group
+ *               more often than that runs out of blocks, and grad is then filled with NaN.
+ *   workspace   device memory of w2a_policy_gradient_mlp_workspace_bytes(...) bytes, 256-B aligned: 9 B per env-day and
+ *               12 B per env of scratch, and the partial blocks (fp64 [stride] each)
+ * Numerics contract: u, z_s, p_s, r_s and beta_s are computed by the statements of k_rollout_mlp and of
+ * w2a_policy_gradient_linear's fork; delta_s and A_s are f32, Q_s fp64, c_s = delta_s Q_s rounded to f32; the forward
+ * recomputation, the backward pass and the sums over the days of one 64-env tile are f32 (matrix-core accumulators);
+ * the tiles' sums are added in fp64 in a fixed order and the mean is rounded to f32 once. No atomics: two identical
+ * calls give identical bits. The partial sums (not the estimator) depend on the visiting order.
+ * W2A_ERR_ARG where w2a_rollout_mlp refuses (checked in the same order), for sample != 1, an unknown baseline, a NULL
+ * grad or workspace and a workspace too small or misaligned; W2A_ERR_STATE while `stream` is recording a hipGraph. */
+size_t w2a_policy_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                               int32_t n_layers);
+int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
+                            const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

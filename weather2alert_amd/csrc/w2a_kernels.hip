@@ -49,6 +49,7 @@
 #include "w2a_rollout_mfma.hip.h"
 #include "w2a_posterior_returns.hip.h"
 #include "w2a_policy_gradient.hip.h"
+#include "w2a_policy_gradient_mlp.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1112,6 +1113,144 @@ int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, in
   if (!ensure_canonical(env, s, "w2a_policy_gradient_linear")) return W2A_ERR_STATE;
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
   hipLaunchKernelGGL(k_policy_gradient_linear, dim3(g64), dim3(BLOCK), 0, s, ga);
+  HIP_TRY(hipGetLastError());
+  return W2A_OK;
+}
+
+// the workspace of w2a_policy_gradient_mlp: pass 1's scratch (9 B per env-day, 12 B per env) and the partial blocks
+// (fp64 [stride] each) of pass 2's waves
+struct PgmLayout {
+  int32_t tiles;      // 64-env tiles per wave of pass 2
+  uint32_t n_chunks;  // its waves
+  uint32_t capacity;  // partial blocks: one per wave and one per group boundary of a group-major order
+  size_t day, day_alert, total, n_valid, chunk_count, chunk_base, tag, pcount, partial, bytes;
+};
+#define PGM_TARGET_WAVES 1024  // one wave per SIMD of the device
+#define PGM_MAX_TILES 16
+
+static PgmLayout pgm_layout(int64_t n, int32_t n_steps, int32_t n_groups, int32_t width, int32_t n_layers) {
+  PgmLayout L;
+  const int64_t n_tiles = (n + 63) / 64;
+  int64_t tiles = (n_tiles + PGM_TARGET_WAVES - 1) / PGM_TARGET_WAVES;
+  tiles = tiles < 1 ? 1 : (tiles > PGM_MAX_TILES ? PGM_MAX_TILES : tiles);
+  L.tiles = (int32_t)tiles;
+  L.n_chunks = (uint32_t)((n_tiles + tiles - 1) / tiles);
+  const int64_t groups = (int64_t)n_groups < n ? (int64_t)n_groups : n;
+  L.capacity = (uint32_t)(L.n_chunks + groups);
+  const size_t days = (size_t)n * (size_t)n_steps;
+  const size_t stride = (size_t)W2A_MLP_STRIDE((int64_t)width, n_layers);
+  size_t off = 0;
+  L.day = off; off += align256(sizeof(float2) * days);
+  L.day_alert = off; off += align256(days);
+  L.total = off; off += align256(sizeof(double) * (size_t)n);
+  L.n_valid = off; off += align256(sizeof(int32_t) * (size_t)n);
+  L.chunk_count = off; off += align256(sizeof(uint32_t) * L.n_chunks);
+  L.chunk_base = off; off += align256(sizeof(uint32_t) * ((size_t)L.n_chunks + 1));
+  L.tag = off; off += align256(sizeof(int32_t) * (size_t)L.capacity);
+  L.pcount = off; off += align256(sizeof(uint32_t) * (size_t)L.capacity);
+  L.partial = off; off += align256(sizeof(double) * (size_t)L.capacity * stride);
+  L.bytes = off;
+  return L;
+}
+
+size_t w2a_policy_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                               int32_t n_layers) {
+  if (num_envs <= 0 || n_steps <= 0 || n_groups <= 0) return 0;
+  if ((width != 16 && width != 32 && width != 64) || (n_layers != 1 && n_layers != 2)) return 0;
+  return pgm_layout(num_envs, n_steps, n_groups, width, n_layers).bytes;
+}
+
+int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
+                            const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
+  if (!policy) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL policy");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_steps must be positive");
+  if (!policy->params) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL params");
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_groups must be positive");
+  if (policy->n_layers != 1 && policy->n_layers != 2)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_layers must be 1 or 2");
+  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: width must be 16, 32 or 64");
+  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
+  if (policy->sample != 1)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: sample must be 1 (a deterministic policy has no score function)");
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: require_budget must be 0 or 1");
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: params must be 16-B aligned");
+  if (baseline != W2A_PG_BASELINE_NONE && baseline != W2A_PG_BASELINE_NO_ALERT)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT");
+  if (!obs) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL obs (the rows the agent holds are the first day's input)");
+  if (!grad || !workspace) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL grad or workspace");
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: workspace must be 256-B aligned");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL handle");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: not available with corrected-semantics flags (they change what "
+                             "the observation is)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
+  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_groups * block size must stay below 2^31 floats");
+  const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: workspace smaller than w2a_policy_gradient_mlp_workspace_bytes");
+  REFUSE_WHILE_CAPTURING("w2a_policy_gradient_mlp", stream);
+  MlpGradArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  MlpRolloutArgs &ma = ga.m;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_policy_gradient_mlp: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    ma.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = ma.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.pol.seed = policy->seed;
+  a.n_steps = n_steps;
+  // the gradient kernels write no state, so their visiting order is their own: the policy's (group-major, so that the
+  // partial blocks fit the workspace) or identity -- never the handle's feature-row order
+  a.order = reinterpret_cast<const uint32_t *>(policy->order);
+  ma.params = policy->params;
+  ma.group = policy->group;
+  ma.n_groups = policy->n_groups;
+  ma.stride = (int32_t)stride;
+  ma.activation = policy->activation;
+  ma.n_obs = env->tb.n_obs;
+  ma.obs_mask = obs_mask;
+  ma.obs = const_cast<float *>(obs);  // the kernels only read it
+  ga.baseline = baseline;
+  char *ws = reinterpret_cast<char *>(workspace);
+  ga.day = reinterpret_cast<float2 *>(ws + L.day);
+  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
+  ga.total = reinterpret_cast<double *>(ws + L.total);
+  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
+  ga.tiles = L.tiles;
+  ga.n_chunks = L.n_chunks;
+  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
+  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
+  ga.capacity = L.capacity;
+  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
+  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
+  ga.partial = reinterpret_cast<double *>(ws + L.partial);
+  ga.grad = grad;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words (the rollout that follows would make them current itself); changes nothing else
+  if (!ensure_canonical(env, s, "w2a_policy_gradient_mlp")) return W2A_ERR_STATE;
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  switch (policy->width * 4 + policy->n_layers) {
+    case 16 * 4 + 1: launch_pgm<16, 1>(ga, g64, s); break;
+    case 16 * 4 + 2: launch_pgm<16, 2>(ga, g64, s); break;
+    case 32 * 4 + 1: launch_pgm<32, 1>(ga, g64, s); break;
+    case 32 * 4 + 2: launch_pgm<32, 2>(ga, g64, s); break;
+    case 64 * 4 + 1: launch_pgm<64, 1>(ga, g64, s); break;
+    default: launch_pgm<64, 2>(ga, g64, s); break;
+  }
   HIP_TRY(hipGetLastError());
   return W2A_OK;
 }

@@ -840,7 +840,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         (hindsight_optimum(), the yardstick that turns "return" into regret); the linear and mlp kinds also return
         "group_hindsight_return" f32 [G]. Nothing else the call returns or leaves behind changes. Sampled reward and
         faithful semantics only (ValueError otherwise, and for tables with a nonzero slot-27 coefficient).
-        policy_gradient="none" | "no_alert" | True (= "no_alert"); kind="linear" with sample=True only -- ValueError for
+        policy_gradient="none" | "no_alert" | True (= "no_alert"); kind="linear" or "mlp" with sample=True only -- ValueError for
         sample=False, every other kind, reward_mode="posterior_mean", fixes other than "budget", an unknown string, and
         together with record=True (a recorded trajectory already holds everything a learner needs); combinable with
         alert_mask, posterior_returns and hindsight. Also returns "policy_gradient": {"weight": f32 [G, n_obs] (columns
@@ -859,9 +859,17 @@ class HeatAlertVecEnv(_VectorEnvBase):
         over its envs; envs finished on entry contribute zero and count. w2a_policy_gradient_linear (include/w2a.h)
         runs right before the rollout on the same state and rows, with the rollout's own statements for u, z_s and
         r_s; no observation row goes to memory per day (9 B of scratch per env-day). Deterministic: two identical calls
-        return bit-identical gradients. Nothing else the call returns or leaves behind changes, bit for bit."""
+        return bit-identical gradients. Nothing else the call returns or leaves behind changes, bit for bit.
+        For kind="mlp" the same estimator with z_s the f32 logit k_rollout_mlp acts on and (o_s, 1) replaced by
+        dz_s/dtheta, the backward pass of the f32 network (ReLU' = 0 at a pre-activation of exactly 0):
+        "policy_gradient": {"layers": [(dW, db), ...]} in the shapes and torch Linear convention of policy["layers"]
+        with a leading G ([G, out, in] / [G, out], f32; for a two-row output row 1 gets +g and row 0 -g, the adjoint of
+        logit = row1 - row0). w2a_policy_gradient_mlp: the forward pass is recomputed and backpropagated on the matrix
+        cores inside the kernel, the parameter gradients are summed over envs in registers and reduced per group in
+        fp64 in a fixed order (no atomics; a few tens of MB of partial blocks at 1 M envs). policy.mlp_grad_to_module
+        writes a group's gradient into the .grad of the torch module the policy came from."""
         pg = _policy.check_policy_gradient(policy_gradient, policy.get("kind"), policy.get("sample", False),
-                                           self.reward_mode, self.fixes, record)
+                                           self.reward_mode, self.fixes, record, kinds=("linear", "mlp"))
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         ct = self.ct
@@ -892,7 +900,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                "step()/reset()): call step() or reset() first")
         pr, hs = bool(posterior_returns), bool(hindsight)
         if kind == "mlp":
-            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr, hs)
+            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr, hs, pg)
         if lin is not None:
             return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr, hs, pg)
         p = _ffi.Policy()
@@ -933,7 +941,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
             out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
         return out
 
-    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False) -> dict:
+    def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
+                     policy_gradient=None) -> dict:
         """rollout(kind="mlp"): w2a_rollout_mlp on the checked, packed policy (weather2alert_amd/policy.py)."""
         mp = _ffi.MlpPolicy()
         mp.params = mlp.params.data_ptr()
@@ -942,7 +951,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mp.n_groups, mp.n_layers, mp.width = mlp.n_groups, mlp.n_layers, mlp.width
         mp.activation = _ffi.MLP_ACTIVATIONS[mlp.activation]
         mp.sample, mp.require_budget, mp.seed = int(mlp.sample), int(mlp.require_budget), mlp.seed
-        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns, hindsight)
+        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns, hindsight, policy_gradient)
+        if policy_gradient is not None:
+            out["policy_gradient"] = {"layers": _policy.unpack_mlp_grad(
+                out.pop("_policy_gradient_blocks"), self.ct.obs_slot, self.ct.n_obs, mlp.hidden, mlp.n_out)}
         out["group_mean_return"] = _policy.group_mean(out["return"], mlp.group, mlp.n_groups)
         if posterior_returns:
             out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], mlp.group, mlp.n_groups)
@@ -956,9 +968,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
         linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True).
         posterior_returns: the alert bitmap is taken in any case (the rollout kernels' results do not depend on it) and
         w2a_posterior_returns runs on it and the start state right after the rollout. hindsight: w2a_hindsight_optimum on
-        the same start state and days. policy_gradient ("none" / "no_alert", linear only): w2a_policy_gradient_linear
-        right before the rollout, on the state and the rows the rollout starts from; its per-env rows come back as
-        "_policy_gradient_env" f32 [n_obs + 1, N]."""
+        the same start state and days. policy_gradient ("none" / "no_alert"): w2a_policy_gradient_linear /
+        w2a_policy_gradient_mlp right before the rollout, on the state and the rows the rollout starts from; the linear
+        kind's per-env rows come back as "_policy_gradient_env" f32 [n_obs + 1, N], the mlp kind's per-group blocks as
+        "_policy_gradient_blocks" f32 [G, stride] (the layout of the packed parameters)."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -995,7 +1008,21 @@ class HeatAlertVecEnv(_VectorEnvBase):
                             n, ct.S_w * ct.Y, ct.S, ct.n_samples), dtype=torch.uint8, device=dev)
                     _ffi.check(self._lib.w2a_rollout_mfma_prepare(self._h, self._mfma_ws.data_ptr(), self._mfma_ws.numel(),
                                                                   self._stream()), "w2a_rollout_mfma_prepare")
-            if policy_gradient is not None:
+            if policy_gradient is not None and isinstance(lp, _ffi.MlpPolicy):
+                # the gradient kernels write no state, so their visiting order is their own: always group-major (the
+                # partial blocks of w2a_policy_gradient_mlp are sized for it), whatever "order" the rollout itself uses
+                gp = _ffi.MlpPolicy.from_buffer_copy(lp)
+                gorder = None if keep.group is None else (keep.order if keep.group_major else _policy.group_order(keep.group))
+                gp.order = None if gorder is None else gorder.data_ptr()
+                out["_policy_gradient_blocks"] = torch.empty(
+                    (keep.n_groups, _policy.mlp_stride(keep.width, keep.n_layers)), dtype=torch.float32, device=dev)
+                ws = torch.empty(self._lib.w2a_policy_gradient_mlp_workspace_bytes(
+                    n, steps, keep.n_groups, keep.width, keep.n_layers), dtype=torch.uint8, device=dev)
+                _ffi.check(self._lib.w2a_policy_gradient_mlp(
+                    self._h, C.byref(gp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
+                    out["_policy_gradient_blocks"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                    "w2a_policy_gradient_mlp")
+            elif policy_gradient is not None:
                 out["_policy_gradient_env"] = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
                 ws = torch.empty(self._lib.w2a_policy_gradient_workspace_bytes(n, steps), dtype=torch.uint8, device=dev)
                 _ffi.check(self._lib.w2a_policy_gradient_linear(

@@ -114,11 +114,13 @@ def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, devic
 PG_BASELINES = ("none", "no_alert")
 
 
-def check_policy_gradient(policy_gradient, kind, sample, reward_mode="sampled", fixes=(), record=False):
+def check_policy_gradient(policy_gradient, kind, sample, reward_mode="sampled", fixes=(), record=False,
+                          kinds=("linear",)):
     """The ``policy_gradient`` keyword of ``rollout()``: None when it is off (False), else the baseline's name ("none" or
-    "no_alert"; True means "no_alert"). ValueError for everything the gradient kernel does not serve: a kind other
-    than "linear", sample=False (a deterministic policy has no score function), reward_mode="posterior_mean", fixes
-    other than "budget", record=True (take one or the other per call) and an unknown baseline."""
+    "no_alert"; True means "no_alert"). ValueError for everything the gradient kernels do not serve: a kind outside
+    `kinds` (rollout() passes ("linear", "mlp")), sample=False (a deterministic policy has no score function),
+    reward_mode="posterior_mean", fixes other than "budget", record=True (take one or the other per call) and an unknown
+    baseline."""
     if policy_gradient is False or policy_gradient is None:
         return None
     if policy_gradient is True:
@@ -126,8 +128,8 @@ def check_policy_gradient(policy_gradient, kind, sample, reward_mode="sampled", 
     if not isinstance(policy_gradient, str) or policy_gradient not in PG_BASELINES:
         raise ValueError(f"rollout(policy_gradient=...) must be False, True or one of {PG_BASELINES}, "
                          f"got {policy_gradient!r}")
-    if kind != "linear":
-        raise ValueError(f"rollout(policy_gradient=...) needs kind 'linear', got {kind!r}")
+    if kind not in kinds:
+        raise ValueError(f"rollout(policy_gradient=...) needs kind {' or '.join(repr(k) for k in kinds)}, got {kind!r}")
     if not isinstance(sample, (bool, np.bool_)) or not sample:
         raise ValueError("rollout(policy_gradient=...) needs a sampled policy (sample=True): a deterministic policy "
                          "has no score function")
@@ -221,6 +223,9 @@ class MlpPolicyArgs:
     sample: bool
     seed: int
     require_budget: bool
+    hidden: tuple = ()           # the real (unpadded) hidden widths
+    n_out: int = 1               # rows of the output layer as given (2: folded into row1 - row0)
+    group_major: bool = False    # `order` is group_order(group), built here (no "order" key in the policy)
 
 
 def _real(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -306,6 +311,66 @@ def pack_mlp(layers, obs_slot, n_obs: int):
     return P, w, nl, G
 
 
+def unpack_mlp_grad(P, obs_slot, n_obs: int, hidden, n_out: int = 1):
+    """A gradient in the kernel's block layout (f32 or f64 [G, mlp_stride(width, n_layers)], as w2a_policy_gradient_mlp
+    writes it) -> layers [(dW [G, out, in], db [G, out]), ...] in torch's Linear convention with the real widths
+    `hidden` and `n_out` output rows: the adjoint of pack_mlp's placement, <pack(L), P> = <L, unpack(P)>. Padding units
+    and non-observation slots are dropped; a two-row output gets +g on row 1 and -g on row 0 (the adjoint of the fold
+    logit = row1 - row0)."""
+    hidden = [int(h) for h in hidden]
+    nl, w = len(hidden), mlp_width(hidden)
+    if P.dim() != 2 or P.shape[1] != mlp_stride(w, nl):
+        raise ValueError(f"unpack_mlp_grad: expected [G, {mlp_stride(w, nl)}] for hidden widths {hidden}, got {tuple(P.shape)}")
+    if n_out not in (1, 2):
+        raise ValueError(f"unpack_mlp_grad: n_out must be 1 or 2, got {n_out}")
+    G = int(P.shape[0])
+    s = torch.as_tensor(slot_map(obs_slot, n_obs), device=P.device)
+    off = 0
+
+    def take(shape):
+        nonlocal off
+        n = int(np.prod(shape))
+        v = P[:, off:off + n].reshape(G, *shape)
+        off += n
+        return v
+
+    W1s = take((ROW_FLOATS, w))
+    layers = [(W1s[:, s, :hidden[0]].transpose(1, 2).contiguous(), take((w,))[:, :hidden[0]].contiguous())]
+    if nl == 2:
+        W2p = take((w, w))
+        layers.append((W2p[:, :hidden[0], :hidden[1]].transpose(1, 2).contiguous(), take((w,))[:, :hidden[1]].contiguous()))
+    go, gb = take((w,))[:, None, :hidden[-1]], P[:, off:off + 1]
+    if n_out == 2:
+        go, gb = torch.cat([-go, go], dim=1), torch.cat([-gb, gb], dim=1)
+    layers.append((go.contiguous(), gb.contiguous()))
+    return layers
+
+
+def mlp_grad_to_module(module: torch.nn.Module, grad: dict, group: int = 0, ascent: bool = True) -> None:
+    """Write ``rollout(mlp, policy_gradient=...)["policy_gradient"]`` of group `group` into the ``.grad`` of the Linears
+    of the Sequential mlp_from_module accepts (in order). ascent=True writes the NEGATED gradient, so that a torch
+    optimizer's ``step()`` (which descends) ascends the return; ascent=False writes it as it is."""
+    def flat(m):
+        if isinstance(m, torch.nn.Sequential):
+            for c in m:
+                yield from flat(c)
+        else:
+            yield m
+
+    lins = [m for m in flat(module) if isinstance(m, torch.nn.Linear)]
+    layers = grad["layers"]
+    if len(lins) != len(layers):
+        raise ValueError(f"mlp_grad_to_module: the module has {len(lins)} Linear layers, the gradient {len(layers)}")
+    sign = -1.0 if ascent else 1.0
+    for m, (dW, db) in zip(lins, layers):
+        dW, db = dW[group], db[group]
+        if tuple(dW.shape) != tuple(m.weight.shape):
+            raise ValueError(f"mlp_grad_to_module: gradient {tuple(dW.shape)} for a weight {tuple(m.weight.shape)}")
+        m.weight.grad = (sign * dW).to(device=m.weight.device, dtype=m.weight.dtype)
+        if m.bias is not None:
+            m.bias.grad = (sign * db).to(device=m.bias.device, dtype=m.bias.dtype)
+
+
 def group_order(group: torch.Tensor) -> torch.Tensor:
     """int32 [num_envs]: the env ids stably sorted by group, so each group's envs fill whole waves."""
     return torch.sort(group, stable=True).indices.to(torch.int32).contiguous()
@@ -348,6 +413,7 @@ def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device) 
         order = order.to(torch.int32).contiguous()
     elif g is not None:
         order = group_order(g)
+    group_major = policy.get("order") is None and g is not None
     sample = policy.get("sample", False)
     rb = policy.get("require_budget", False)
     if not isinstance(sample, (bool, np.bool_)) or not isinstance(rb, (bool, np.bool_)):
@@ -355,8 +421,9 @@ def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device) 
     seed = policy.get("seed", 0)
     if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
         raise ValueError("mlp policy: 'seed' must be an int")
+    shapes = [tuple(np.shape(W)) for W, _ in policy["layers"]]
     return MlpPolicyArgs(P.to(device).contiguous(), g, order, G, nl, width, act, bool(sample), int(seed) & (2**64 - 1),
-                         bool(rb))
+                         bool(rb), tuple(int(sh[-2]) for sh in shapes[:-1]), int(shapes[-1][-2]), group_major)
 
 
 def mlp_from_module(module: torch.nn.Module, group=None) -> dict:
