@@ -19,6 +19,7 @@ import copy
 import numpy as np
 
 from oracle import heatalert_oracle as O
+from posterior_restatement import posterior_returns_fp64
 from weather2alert_amd import synth, tables
 
 GID0 = 300
@@ -49,8 +50,8 @@ class Table:
         self.sd, self.ct = sd, tables.compile_from_synth(sd)
         self.ref = O.RefData.from_synth(sd_oracle)
 
-    def oracle(self):
-        return O.VectorOracle(self.ref, self.sd.fips_weather, self.sd.years)
+    def oracle(self, reward_mode="sampled"):
+        return O.VectorOracle(self.ref, self.sd.fips_weather, self.sd.years, reward_mode=reward_mode)
 
 
 def _lengths(sd, lo, hi, seed):
@@ -245,4 +246,112 @@ def oracle_record(V, logit_fn, S, ties, uniform=None, T=None):
         R["days"][rows[live & (actual == 1)], tday[live & (actual == 1)]] = True
         R["att"][rows[live & (act == 1)], tday[live & (act == 1)]] = True
     R["obs"][S] = V.obs.astype(np.float32)
+    return R
+
+
+# ------------------------------------------------------------------ reward_mode="posterior_mean"
+PR_KEYS = ("t", "used", "streak", "hist14", "budget", "n_days", "county_w", "year_i", "coef_col", "finished")
+
+
+def start_state(tup):
+    """the state() of a batch right after the reset that drew `tup` (host_tuples), as the restatements take it"""
+    z = np.zeros(len(tup["budget"]), np.int64)
+    return dict(t=z, used=z, streak=z, hist14=z, finished=z,
+                **{k: tup[k] for k in ("budget", "n_days", "county_w", "year_i", "coef_col")})
+
+
+def pm_rewards_fp64(ct, start, alert_days, n_steps):
+    """The posterior-mean reward in fp64 with every slot, slot 27 included: the mean over the draw axis of the
+    restatement's per-day rewards (tests/posterior_restatement.py). start: a state() dict (PR_KEYS are read);
+    alert_days bool [N, >= T]. Returns ([n_steps, N] rewards, NaN where the env did not step; [N] summed return)."""
+    st = {k: np.asarray(start[k]) for k in PR_KEYS}
+    ret, days = posterior_returns_fp64(ct.X, ct.W, ct.n_samples, ct.Y, st, np.asarray(alert_days), n_steps, per_day=True)
+    return days.mean(axis=2).T, ret.mean(axis=1)
+
+
+def pi8_flagged_columns(ct, max_budget):
+    """Host restatement of which coefficient columns the int8 posterior-mean kernels send down their exact fp64 path
+    (k_pi8_slot_max, k_pi8_scales and the flag test of k_pi8_wq): 2^ex_k is the power of two above the largest |x_k| of
+    slot k -- over the whole feature table for the table-sourced slots, from the run-time slots' ranges for a batch
+    whose largest budget is `max_budget` (lag 1, streak min(T, B), remaining budget B, 14-day count min(14, B)) -- and
+    a column is flagged when frexp(max_k |w_k| 2^ex_k) of any of its coefficient rows has an exponent above 4. Reads
+    nothing from the device; bool [S]."""
+    xmax = np.abs(np.asarray(ct.X, np.float64)).reshape(-1, 32).max(axis=0)
+    b = float(max_budget)
+    xmax[24:28] = 1.0, min(float(ct.T), b), b, min(14.0, b)
+    ex = np.where(xmax > 0, np.frexp(xmax)[1], 0)
+    W = np.abs(np.asarray(ct.W, np.float64)).reshape(-1, ct.n_samples * 2, 32)  # [S, rows of the column, 32]
+    m = (W * np.ldexp(1.0, ex)[None, None, :]).max(axis=2)
+    ew = np.where(m > 0, np.frexp(m)[1], 0)
+    return (ew > 4).any(axis=1)
+
+
+def builtin_policies(ct):
+    """kind -> the policy dict rollout() takes (oracle_policy() makes it the one O.oracle_rollout takes). The kinds
+    decide on table-sourced columns, the remaining budget and the device RNG, all of which the oracle restates
+    exactly: no env is a near-tie."""
+    table = (np.random.default_rng(0).random((ct.T, 5)) < 0.3).astype(np.uint8)
+    return {"bernoulli": dict(kind="bernoulli", p=0.3, seed=POLICY_SEED),
+            "threshold": dict(kind="threshold", feature="heat_qi", threshold=0.8, require_budget=True),
+            "table": dict(kind="table", table=table), "always": dict(kind="always")}
+
+
+def oracle_policy(ct, pol):
+    return dict(pol, col=ct.columns.index("heat_qi"))
+
+
+class PolicyStream:
+    """O.oracle_rollout's seed_stream for the bernoulli kind: the device RNG's uniform of (env, episode_no, day)"""
+
+    def __init__(self, n, episode_no=None, seed=POLICY_SEED):
+        self.seed, self.gid = seed, GID0 + np.arange(n)
+        self.episode_no = np.zeros(n, np.int64) if episode_no is None else np.asarray(episode_no, np.int64)
+
+    def vec(self, t):
+        return O.devrng_policy_uniform_vec(self.seed, self.gid, self.episode_no, t)
+
+
+def oracle_builtin_rollout(V, opol, n_steps, stream=None):
+    """O.oracle_rollout(V, opol, n_steps, stream) and, beside its (ret, alerts, over, alert days), the attempt days:
+    the actions the loop hands to V.step, by episode day, for the envs still running."""
+    n, T = len(V.t), V.X.shape[2]
+    att = np.zeros((n, T), bool)
+    step = V.step
+
+    def spy(act):
+        sel = ~V._finished & (np.asarray(act) == 1)
+        att[np.arange(n)[sel], V.t[sel]] = True
+        return step(act)
+
+    V.step = spy
+    try:
+        ret, alerts, over, days = O.oracle_rollout(V, opol, n_steps, stream)
+    finally:
+        del V.step
+    return dict(ret=ret, alerts=alerts, over=over, days=days, att=att)
+
+
+def pm_step_reference(tb, n, seed=12, p=0.3):
+    """step() for ct.T days with random actions (zeroed once an env is finished) on the posterior-mean oracle, and the
+    fp64 reference of the same days: dict(actions int32 [T, n], live bool [T, n], done bool [T, n], oracle f64 [T, n]
+    (right on the `known` envs), alert_days bool [n, T], reward f64 [T, n] (NaN where the env did not step), ret [n],
+    known [n], tup)."""
+    ct = tb.ct
+    tup = host_tuples(tb, n)
+    V = tb.oracle("posterior_mean")
+    oracle_reset(V, tup)
+    rng = np.random.default_rng(seed)
+    T = ct.T
+    R = dict(actions=np.zeros((T, n), np.int32), live=np.zeros((T, n), bool), done=np.zeros((T, n), bool),
+             oracle=np.zeros((T, n)), alert_days=np.zeros((n, T), bool), tup=tup, known=~tb.a2w[tup["coef_col"]])
+    rows = np.arange(n)
+    for s in range(T):
+        act = np.where(V._finished, 0, rng.random(n) < p).astype(np.int32)
+        tday = V.t.copy()
+        r, done, actual, live = oracle_step(V, act)
+        R["actions"][s], R["live"][s], R["done"][s], R["oracle"][s] = act, live, live & done, np.where(live, r, 0.0)
+        R["alert_days"][rows[live & (actual == 1)], tday[live & (actual == 1)]] = True
+    assert V._finished.all()
+    R["reward"], R["ret"] = pm_rewards_fp64(ct, start_state(tup), R["alert_days"], T)
+    R["state"] = oracle_state(V)
     return R

@@ -1,7 +1,10 @@
 """The references of tests/test_table_edges_gpu.py on their own (no GPU): the three tables have the edges they claim,
 the batches drawn on them put many episode lengths into every wave, and the fp64 oracle loop of every policy meets a
 near-tie on fewer than 1 % of the envs while the policy really decides -- so the 1 % the GPU tests allow is a property
-of the seeds and weight scales, not of the kernels."""
+of the seeds and weight scales, not of the kernels. And those of tests/test_posterior_mean_edges_gpu.py: the fp64
+posterior-mean reward (the draw-mean of the restatement) against the posterior-mean oracle, the host restatement of the
+int8 kernels' column flags (the slot-27 fixtures run both of their paths in one launch), and built-in policies that
+decide."""
 import os
 import sys
 
@@ -84,3 +87,62 @@ def test_oracle_loop_decides_and_rarely_ties(tabs, name, pol):
     np.testing.assert_allclose(own[known], R["ret"][known], rtol=1e-9, atol=1e-9)
     if tb.slot27:  # the slot-27 coefficients act: the oracle, which has none, is off where a column has one
         assert np.abs(own - R["ret"])[~known].max() > 1e-4
+
+
+# ------------------------------------------------------------------ reward_mode="posterior_mean"
+@pytest.mark.parametrize("name", ["ragged", "slot27", "ragged27"])
+def test_posterior_mean_reference_matches_the_oracle_where_it_knows(tabs, name):
+    tb = tabs[name]
+    R = E.pm_step_reference(tb, 300)
+    live, known = R["live"], R["known"]
+    assert np.array_equal(np.isnan(R["reward"]), ~live)  # NaN marks exactly the days an env did not step
+    assert (live.sum(0) == R["tup"]["n_days"]).all() and (R["done"].sum(0) == 1).all()
+    err = np.abs(np.where(live, R["reward"], 0.0) - R["oracle"])
+    assert err[:, known].max() <= 1e-12, err[:, known].max()
+    np.testing.assert_allclose(R["ret"][known], R["oracle"].sum(0)[known], rtol=0, atol=1e-12 * tb.ct.T)
+    if tb.slot27:  # the slot-27 coefficients act: the oracle, which has none, is off on those columns
+        assert (~known).any() and err[:, ~known].max() > 1e-4
+    else:
+        assert known.all()
+    # the schedule reaches what the fixed-point ranges and the 4-bit field are about: granted, refused, long windows
+    assert R["alert_days"].any() and (R["actions"].sum(0) > R["alert_days"].sum(1)).any()
+
+
+def test_int8_column_flags_mix_both_paths_on_the_slot27_tables(tabs):
+    for name, tb in tabs.items():
+        tup = E.host_tuples(tb, E.N_ENVS[name])
+        flag = E.pi8_flagged_columns(tb.ct, int(tup["budget"].max()))
+        assert flag.shape == (tb.ct.S,)
+        if not tb.slot27:
+            assert not flag.any()
+            continue
+        assert flag.any() and not flag.all()  # a strict, non-empty subset: one launch runs both paths
+        share = flag[tup["coef_col"]].mean()
+        assert 0.2 < share < 0.8, share  # envs on both sides
+        assert not flag[tb.a2w].any()  # the slot-27 columns stay on the matrix cores, where slot 27's range matters
+        assert np.array_equal(flag, tb.big)
+
+
+@pytest.mark.parametrize("name", ["ragged", "slot27", "ragged27"])
+def test_builtin_policies_decide(tabs, name):
+    tb = tabs[name]
+    ct, n = tb.ct, E.N_ENVS[name]
+    tup = E.host_tuples(tb, n)
+    V = tb.oracle("posterior_mean")
+    granted = refused = absent = False
+    for kind, pol in E.builtin_policies(ct).items():
+        E.oracle_reset(V, tup)
+        R = E.oracle_builtin_rollout(V, E.oracle_policy(ct, pol), ct.T, E.PolicyStream(n))
+        assert V._finished.all() and (V.t == tup["n_days"] - 1).all()
+        assert (R["days"].sum(1) == R["alerts"]).all() and not (R["days"] & ~R["att"]).any()
+        assert ((R["att"] & ~R["days"]).sum(1) == R["over"]).all()
+        assert (R["alerts"] <= np.minimum(tup["budget"], tup["n_days"])).all() and (R["alerts"][tup["budget"] == 0] == 0).all()
+        assert R["alerts"].sum() > 0
+        if kind != "always":  # not an attempt on every day
+            assert (R["att"].sum(1) < tup["n_days"]).mean() > 0.5
+        if kind != "threshold":  # require_budget: that kind never attempts at the budget
+            assert R["over"].sum() > 0
+        granted |= bool(R["alerts"].any())
+        refused |= bool(R["over"].any())
+        absent |= bool((R["att"].sum(1) < tup["n_days"]).any())
+    assert granted and refused and absent

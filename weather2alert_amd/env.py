@@ -200,6 +200,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         self.rollout_mfma = bool(rollout_mfma)
         self._mfma_ws = None
         self.pm_rollout_kernel = True  # posterior_mean rollouts in one launch when possible (False: per-day launches)
+        # which path the last posterior_mean rollout() took: "k_pm_rollout" / "k_pm_rollout_i8" (one launch), "per_day"
+        # (policy kernel + reward kernel + step kernel per day), None before the first one or when no env had a day left
+        self.last_pm_rollout: str | None = None
         self._order_stale = True
         if episode_order not in ("iid", "sorted"):
             raise ValueError(f"episode_order {episode_order!r}")
@@ -1213,6 +1216,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         left = torch.where(st0["finished"].bool(), torch.zeros_like(st0["t"]), st0["n_days"] - st0["t"])
         steps = min(steps, int(left.max()))
         lib, h, stream = self._lib, self._h, self._stream()
+        self.last_pm_rollout = "per_day" if steps else None
         if steps and self.pm_rollout_kernel:  # the whole rollout in one launch, when the kernel applies
             rc = lib.w2a_rollout_posterior_mean(h, C.byref(p), steps, out["return"].data_ptr(), out["alerts"].data_ptr(),
                                                 out["attempts_over_budget"].data_ptr(),
@@ -1220,6 +1224,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                 None if amask is None else amask.data_ptr(), words, self._fr_ptr,
                                                 None if snap is None else snap.data_ptr(), stream)
             if rc == 0:
+                self.last_pm_rollout = "k_pm_rollout_i8" if self.pm_kernel_choice == "matrix_i8" else "k_pm_rollout"
                 return steps
             if rc != 1:
                 _ffi.check(rc, "w2a_rollout_posterior_mean")
