@@ -1,7 +1,8 @@
 """rollout(mlp, policy_gradient=...) without a GPU: the fp64 restatement the GPU tests hold the kernels to
 (tests/policy_gradient_mlp_restatement.py) is the gradient of the REINFORCE surrogate by torch autograd, its bound admits
-the f32 evaluation and rejects three wrong gradients, the ReLU cases of the GPU tests are almost never near a kink, the
-block-layout helpers are adjoint to pack_mlp, and the C entry refuses bad arguments before any launch."""
+the f32 evaluation and rejects three wrong gradients, the ReLU cases of the GPU tests are almost never near a kink,
+every net of the instantiation matrix (tests/policy_gradient_mlp_cases.py) pads as listed and takes both actions in
+every group, the block-layout helpers are adjoint to pack_mlp, and the C entry refuses bad arguments before any launch."""
 import ctypes as C
 import os
 import sys
@@ -12,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import table_edges as E  # noqa: E402
+from policy_gradient_mlp_cases import MATRIX, net as _case_net  # noqa: E402
 from policy_gradient_mlp_restatement import policy_gradient_mlp_fp64  # noqa: E402
 from policy_gradient_restatement import forced_days  # noqa: E402
 
@@ -21,6 +23,8 @@ from weather2alert_amd import _ffi, build, policy  # noqa: E402
 # (hidden widths, activation, output rows): unpadded widths, one and two layers, a two-row output
 NETS = {"tanh16": ((16,), "tanh", 1), "relu24x40": ((24, 40), "relu", 2), "tanh64x64": ((64, 64), "tanh", 2),
         "relu32x32": ((32, 32), "relu", 1), "tanh24": ((24,), "tanh", 2)}
+# and the instantiation matrix of the GPU tests: padded widths under every (WIDTH, LAYERS) pair of the kernels
+NETS.update({name: spec[1:] for name, spec in MATRIX.items()})
 
 
 @pytest.fixture(scope="module")
@@ -45,7 +49,7 @@ def recorded(tabs):
         r, _, _, live = E.oracle_step(V, np.zeros(n, np.int64))
         beta[s] = np.where(live, r, 0.0)
     for name, (hidden, act, n_out) in NETS.items():
-        layers = E.net(ct, hidden, n_out, seed=len(hidden) * 10 + hidden[0])
+        layers = _case_net(ct, name, hidden, n_out)  # seed len(hidden) * 10 + hidden[0] unless the matrix names another
         E.oracle_reset(V, tup)
         R = E.oracle_record(V, lambda obs: E.mlp64(layers, act, obs, g), ct.T, (1e-5, 1e-5), uniform=uni, T=ct.T)
         forced = forced_days(True, tup["budget"], np.zeros(n, np.int64), R["alert"], R["valid"])
@@ -171,7 +175,7 @@ def test_f32_chain_emulation(recorded):
     assert worst <= 0.1 * 16 * S
 
 
-@pytest.mark.parametrize("name", ["relu24x40", "relu32x32"])
+@pytest.mark.parametrize("name", ["relu24x40", "relu32x32"] + [k for k, v in MATRIX.items() if v[2] == "relu"])
 def test_relu_cases_are_rarely_near_a_kink(recorded, name):
     """(iii) under 1 % of all unit-days, by the reference alone"""
     c = recorded[name]
@@ -180,7 +184,25 @@ def test_relu_cases_are_rarely_near_a_kink(recorded, name):
     assert frac < 0.01
 
 
-@pytest.mark.parametrize("hidden,n_out", [((16,), 1), ((24, 40), 2), ((64, 64), 1), ((7,), 2)])
+@pytest.mark.parametrize("name", list(MATRIX))
+def test_matrix_nets_pad_as_listed_and_take_both_actions(recorded, name):
+    """Every net of the instantiation matrix pads to the (WIDTH, LAYERS) pair it is listed under, and on the recorded
+    batch its sampled policy takes both actions and issues alerts in every group: a gradient of all-zero deltas, or of
+    one action only, would test little (the GPU tests' _twin_case asserts alerts on its own batch too)."""
+    (width, n_layers), hidden, _, n_out = MATRIX[name]
+    assert (policy.mlp_width(hidden), len(hidden)) == (width, n_layers)
+    c = recorded[name]
+    assert [tuple(W.shape[1:]) for W, _ in c["layers"]] == list(zip(list(hidden) + [n_out], [c["ct"].n_obs] + list(hidden)))
+    R, g = c["R"], c["g"]
+    free = R["valid"] & ~c["forced"]
+    for k in range(E.G):
+        a = R["action"][:, g == k][free[:, g == k]]
+        assert (a == 1).any() and (a == 0).any(), (name, k)
+        assert R["alert"][:, g == k].any(), (name, k)
+
+
+@pytest.mark.parametrize("hidden,n_out", [((16,), 1), ((24, 40), 2), ((64, 64), 1), ((7,), 2), ((7, 13), 1), ((29, 9), 1),
+                                          ((33,), 1), ((64,), 2)])
 def test_unpack_is_the_adjoint_of_pack(tabs, hidden, n_out):
     """(iv) <pack(L), P> = <L, unpack(P)>, the two-row fold included (fp64 throughout: pack rounds to f32 last, so L is
     drawn on the f32 grid and the comparison made to that rounding)"""
