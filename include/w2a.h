@@ -555,6 +555,61 @@ size_t w2a_policy_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps
                                                int32_t n_layers);
 int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
                             const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream);
+/* The gradient of the log-likelihood of a GIVEN alert schedule under a linear policy (teacher forcing): the supervised
+ * counterpart of w2a_policy_gradient_linear. Every env is forced along its own schedule from the handle's CURRENT state
+ * and observation rows, and the policy is evaluated on the rows it would have held. It reads the state, the tables, the
+ * schedule and obs and modifies none of them, nor the RNG, nor the handle's bookkeeping beyond making the canonical state
+ * words current: epochs over the same episodes need no reset in between.
+ * The estimator, for env e of group g over the call-days s = 0 .. S_e - 1 on which the env takes a step (at most n_steps,
+ * and none after its terminal day):
+ *   a*_s     bit (t & 31) of alert_mask[e][t >> 5], t the env's day of the episode: the action ATTEMPTED. The alert
+ *            issued is a*_s unless used == budget, then 0 (an attempt over budget, as w2a_step treats it); the state
+ *            fields advance as in the step and rollout kernels
+ *   o_s      the observation row the agent holds before decision s: row e of obs for s = 0, after that the table row of
+ *            the day before with its four run-time fields -- the row w2a_step(a*_{s-1}) would have returned
+ *   z_s      = weight[g] . o_s + bias[g], the fp64 logit;  p_s = sigmoid(z_s) in f32, as the rollout's
+ *   m_s      0 on a day where require_budget is set and no budget is left (the policy's action is forced there and
+ *            carries no likelihood; the action taken is 0), else 1
+ *   delta_s  = m_s (a*_s - p_s): d log pi(a*_s | o_s) / d z_s
+ *   ll_e     = sum_s m_s log pi(a*_s | o_s), each term -softplus(-z_s) (a* = 1) or -softplus(z_s) (a* = 0)
+ *   g_e      = w_e sum_s delta_s (o_s, 1), w_e = env_weight[e] (NULL: 1); envs finished on entry get zeros
+ * grad (device f32 [n_obs + 1][num_envs], column-major: component j of env e at j * num_envs + e) receives g_e: the
+ * weight columns in OBSERVATION order, the bias last. loglik (f32 [num_envs]) receives ll_e (unweighted), days (i32
+ * [num_envs]) sum_s m_s. The mean of g_e over a group's envs is the gradient of that group's mean w_e ll_e, so
+ * theta += lr * mean is an ascent step on the likelihood.
+ * Numerics contract: z_s is computed by the statements of k_rollout_linear (the same fp64 FMA chain: bias first, slots
+ * 0..29 in slot order) and p_s by its f32 sigmoid; delta_s is f32; the products with w_e and o_s and the sums over s are
+ * fp64, g_e is rounded to f32 once. Every term of ll_e is computed stably in fp64 from z_s, the sum is fp64 and rounded to
+ * f32 once. An env's outputs do not depend on the other envs, the group layout or the visiting order (bit for bit).
+ * policy->sample and policy->seed are ignored (nothing is drawn). No scratch memory.
+ *   alert_mask  device u32 [num_envs][mask_words], mask_words * 32 >= T (the format w2a_rollout and w2a_hindsight_optimum
+ *               write); bits of days outside the stretch are ignored
+ * W2A_ERR_ARG where w2a_rollout_linear refuses (checked in the same order), for a NULL alert_mask, obs, grad, loglik or
+ * days and for mask_words * 32 < T; W2A_ERR_STATE while `stream` is recording a hipGraph. */
+int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                                  float *grad, float *loglik, int32_t *days, void *stream);
+/* The same estimator for an MLP policy, already reduced per group: z_s is the f32 logit k_rollout_mlp computes for o_s
+ * (the same mlp_logit_groups call on the same rows), dz_s/dtheta the backward pass of the f32 network as in
+ * w2a_policy_gradient_mlp, and
+ *     grad[g] = (1 / N_g) sum over the envs e of group g of  w_e sum_s delta_s dz_s/dtheta(theta_g)
+ * (envs finished on entry contribute zero and count; a group without envs gives a block of NaN). grad, policy->order,
+ * the workspace and the partial-block rule are those of w2a_policy_gradient_mlp; the workspace size is
+ * w2a_imitation_gradient_mlp_workspace_bytes(...), equal to w2a_policy_gradient_mlp_workspace_bytes(...). loglik and days
+ * as above, per env.
+ * Numerics contract: c_s = w_e delta_s is formed in fp64 and rounded to f32 once; from there on the second pass, the
+ * fp64 sums over tiles and the reduction are the kernels of w2a_policy_gradient_mlp, run unchanged (its c_s = delta_s Q_s
+ * is fed Q_s = 1). The terms of ll_e are computed in fp64 from the f32 logit. No atomics: two identical calls give
+ * identical bits.
+ * W2A_ERR_ARG where w2a_rollout_mlp refuses (checked in the same order), for a NULL alert_mask, obs, grad, loglik, days
+ * or workspace, mask_words * 32 < T and a workspace too small or misaligned; W2A_ERR_STATE while `stream` is recording a
+ * hipGraph. */
+size_t w2a_imitation_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                  int32_t n_layers);
+int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                               float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                               void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

@@ -50,6 +50,7 @@
 #include "w2a_posterior_returns.hip.h"
 #include "w2a_policy_gradient.hip.h"
 #include "w2a_policy_gradient_mlp.hip.h"
+#include "w2a_imitation.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1252,6 +1253,181 @@ int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t 
     default: launch_pgm<64, 2>(ga, g64, s); break;
   }
   HIP_TRY(hipGetLastError());
+  return W2A_OK;
+}
+
+// the checks w2a_imitation_gradient_linear and _mlp share once the policy's own have passed (same order in both)
+static int check_imitation(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
+                           const float *loglik, const int32_t *days) {
+  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to score)", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!grad || !loglik || !days) return fail(W2A_ERR_ARG, "%s: NULL grad, loglik or days", fn);
+  return W2A_OK;
+}
+
+int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                                  float *grad, float *loglik, int32_t *days, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
+  if (!policy) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: NULL policy");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: n_steps must be positive");
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: NULL weight or bias");
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: n_groups must be positive");
+  if (policy->sample != 0 && policy->sample != 1)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: sample must be 0 or 1");
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: require_budget must be 0 or 1");
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: weight must be 16-B aligned");
+  const int rc = check_imitation("w2a_imitation_gradient_linear", alert_mask, obs, grad, loglik, days);
+  if (rc != W2A_OK) return rc;
+  if (!env) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: NULL handle");
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: alert_mask needs ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: not available with corrected-semantics flags (they change "
+                             "what the observation is)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  REFUSE_WHILE_CAPTURING("w2a_imitation_gradient_linear", stream);
+  ImLinearArgs ia;
+  memset(&ia, 0, sizeof(ia));
+  LinearRolloutArgs &la = ia.l;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_imitation_gradient_linear: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    la.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = la.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.n_steps = n_steps;
+  a.order = env->order;
+  la.weight = reinterpret_cast<const float4 *>(policy->weight);
+  la.bias = policy->bias;
+  la.group = policy->group;
+  la.n_groups = policy->n_groups;
+  la.n_obs = env->tb.n_obs;
+  la.obs_mask = obs_mask;
+  la.obs = const_cast<float *>(obs);  // the kernel only reads it
+  ia.im.alert_mask = alert_mask; ia.im.mask_words = mask_words; ia.im.env_weight = env_weight;
+  ia.im.loglik = loglik; ia.im.days = days;
+  ia.grad = grad;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, "w2a_imitation_gradient_linear")) return W2A_ERR_STATE;
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  hipLaunchKernelGGL(k_imitation_linear, dim3(g64), dim3(BLOCK), 0, s, ia);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
+size_t w2a_imitation_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                  int32_t n_layers) {
+  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
+}
+
+int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                               float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
+  if (!policy) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL policy");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_steps must be positive");
+  if (!policy->params) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL params");
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_groups must be positive");
+  if (policy->n_layers != 1 && policy->n_layers != 2)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_layers must be 1 or 2");
+  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: width must be 16, 32 or 64");
+  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
+  if (policy->sample != 0 && policy->sample != 1)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: sample must be 0 or 1");
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: require_budget must be 0 or 1");
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: params must be 16-B aligned");
+  const int rc = check_imitation("w2a_imitation_gradient_mlp", alert_mask, obs, grad, loglik, days);
+  if (rc != W2A_OK) return rc;
+  if (!workspace) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL workspace");
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: workspace must be 256-B aligned");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL handle");
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: alert_mask needs ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: not available with corrected-semantics flags (they change what "
+                             "the observation is)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
+  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_groups * block size must stay below 2^31 floats");
+  const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: workspace smaller than w2a_imitation_gradient_mlp_workspace_bytes");
+  REFUSE_WHILE_CAPTURING("w2a_imitation_gradient_mlp", stream);
+  ImMlpArgs ia;
+  memset(&ia, 0, sizeof(ia));
+  MlpGradArgs &ga = ia.g;
+  MlpRolloutArgs &ma = ga.m;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_imitation_gradient_mlp: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    ma.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = ma.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.n_steps = n_steps;
+  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the policy's (group-major) or identity
+  a.order = reinterpret_cast<const uint32_t *>(policy->order);
+  ma.params = policy->params;
+  ma.group = policy->group;
+  ma.n_groups = policy->n_groups;
+  ma.stride = (int32_t)stride;
+  ma.activation = policy->activation;
+  ma.n_obs = env->tb.n_obs;
+  ma.obs_mask = obs_mask;
+  ma.obs = const_cast<float *>(obs);  // the kernels only read it
+  char *ws = reinterpret_cast<char *>(workspace);
+  ga.day = reinterpret_cast<float2 *>(ws + L.day);
+  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
+  ga.total = reinterpret_cast<double *>(ws + L.total);
+  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
+  ga.tiles = L.tiles;
+  ga.n_chunks = L.n_chunks;
+  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
+  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
+  ga.capacity = L.capacity;
+  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
+  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
+  ga.partial = reinterpret_cast<double *>(ws + L.partial);
+  ga.grad = grad;
+  ia.im.alert_mask = alert_mask; ia.im.mask_words = mask_words; ia.im.env_weight = env_weight;
+  ia.im.loglik = loglik; ia.im.days = days;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, "w2a_imitation_gradient_mlp")) return W2A_ERR_STATE;
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  switch (policy->width * 4 + policy->n_layers) {
+    case 16 * 4 + 1: launch_im<16, 1>(ia, g64, s); break;
+    case 16 * 4 + 2: launch_im<16, 2>(ia, g64, s); break;
+    case 32 * 4 + 1: launch_im<32, 1>(ia, g64, s); break;
+    case 32 * 4 + 2: launch_im<32, 2>(ia, g64, s); break;
+    case 64 * 4 + 1: launch_im<64, 1>(ia, g64, s); break;
+    default: launch_im<64, 2>(ia, g64, s); break;
+  }
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
   return W2A_OK;
 }
 

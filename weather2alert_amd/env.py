@@ -1127,6 +1127,89 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                                    self._stream()), "w2a_posterior_returns")
         return out
 
+    # ------------------------------------------------------------------ imitation: likelihood of a given schedule
+    def imitation_gradient(self, policy: dict, alert_days, env_weight=None, n_steps: int | None = None) -> dict:
+        """The gradient of the log-likelihood of a GIVEN alert schedule under a linear or MLP policy: the supervised
+        counterpart of rollout(policy_gradient=...). Every env is forced along its own schedule from its current state
+        and the policy is evaluated on the rows it would have held (teacher forcing), all inside the kernel: behaviour
+        cloning of hindsight_optimum()["alert_days"], and with env_weight fitting to the elite envs of a population or
+        reward- / advantage-weighted regression.
+          policy      a kind="linear" or kind="mlp" dict, as rollout() takes it (group, order, require_budget and the
+                      two-row MLP output included; sample and seed are ignored: nothing is drawn)
+          alert_days  bool [N, T] by day of the episode: the actions ATTEMPTED (hindsight_optimum()["alert_days"],
+                      rollout(alert_mask=True)["alert_days"]); an attempt with used == budget issues no alert, as in step()
+          env_weight  optional float [N], finite (default 1)
+          n_steps     days from every env's current day (default: to the end of every episode; an env stops after its
+                      terminal day, as in rollout())
+        Returns
+          "policy_gradient"       linear: {"weight" f32 [G, n_obs], "bias" f32 [G]}; mlp: {"layers": [(dW, db), ...]}: the
+                                  gradient of "group_log_likelihood" (shapes, column order and NaN for a group without
+                                  envs as rollout(policy_gradient=...)), so ``theta += lr * grad`` ascends the likelihood
+          "log_likelihood"        f32 [N]  sum over the env's scored days of log pi(a*_s | o_s) (unweighted)
+          "days"                  i32 [N]  scored days: the days stepped, less those on which require_budget forced the
+                                  action because no budget was left (they carry no likelihood)
+          "group_log_likelihood"  f32 [G]  mean over the group's envs of env_weight * log_likelihood
+        Envs finished on entry contribute zero and count. No side effects: the state, the tables, the observation buffer
+        and the RNG are only read, so ``reset -> hindsight_optimum -> K x (imitation_gradient, optimizer step)`` works
+        on the same episodes. Needs the observation buffer current (RuntimeError as rollout(kind="linear")) and
+        faithful observations (fixes other than "budget": ValueError); reward_mode and the tables' slot-27 coefficients
+        do not matter, rewards never enter. w2a_imitation_gradient_linear / _mlp (include/w2a.h)."""
+        kind = policy.get("kind") if isinstance(policy, dict) else None
+        ct, n, dev = self.ct, self.num_envs, self.device
+        mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes)
+        check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
+        pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        if self._needs_reset:
+            raise RuntimeError("call reset() before imitation_gradient()")
+        if not self._obs_current:
+            raise RuntimeError(f"imitation_gradient(kind={kind!r}) reads the observation buffer, which does not hold the "
+                               "agents' current rows (write_obs=False, a built-in rollout or load_state_dict since the "
+                               "last step()/reset()): call step() or reset() first")
+        words = mask.shape[1]
+        out = {"log_likelihood": torch.empty(n, dtype=torch.float32, device=dev),
+               "days": torch.empty(n, dtype=torch.int32, device=dev)}
+        wp = None if w is None else w.data_ptr()
+        with torch.cuda.device(dev):
+            if kind == "linear":
+                lp = _ffi.LinearPolicy()
+                lp.weight, lp.bias = pol.weight_slots.data_ptr(), pol.bias.data_ptr()
+                lp.group = None if pol.group is None else pol.group.data_ptr()
+                lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
+                rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
+                _ffi.check(self._lib.w2a_imitation_gradient_linear(
+                    self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
+                    out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream()),
+                    "w2a_imitation_gradient_linear")
+                # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
+                g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
+                out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
+            else:
+                mp = _ffi.MlpPolicy()
+                mp.params = pol.params.data_ptr()
+                mp.group = None if pol.group is None else pol.group.data_ptr()
+                # always group-major (the partial blocks are sized for it), whatever "order" a rollout would use
+                gorder = None if pol.group is None else (pol.order if pol.group_major else _policy.group_order(pol.group))
+                mp.order = None if gorder is None else gorder.data_ptr()
+                mp.n_groups, mp.n_layers, mp.width = pol.n_groups, pol.n_layers, pol.width
+                mp.activation = _ffi.MLP_ACTIVATIONS[pol.activation]
+                mp.sample, mp.require_budget, mp.seed = 0, int(pol.require_budget), 0
+                blocks = torch.empty((pol.n_groups, _policy.mlp_stride(pol.width, pol.n_layers)), dtype=torch.float32,
+                                     device=dev)
+                ws = torch.empty(self._lib.w2a_imitation_gradient_mlp_workspace_bytes(
+                    n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
+                _ffi.check(self._lib.w2a_imitation_gradient_mlp(
+                    self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
+                    out["log_likelihood"].data_ptr(), out["days"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                    "w2a_imitation_gradient_mlp")
+                out["policy_gradient"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden,
+                                                                            pol.n_out)}
+            wll = out["log_likelihood"].double() if w is None else (w.double() * out["log_likelihood"].double())
+            if pol.group is None:  # one group: the fp64 mean, rounded once
+                out["group_log_likelihood"] = wll.mean().to(torch.float32).reshape(1)
+            else:
+                out["group_log_likelihood"] = _policy.group_mean(wll, pol.group, pol.n_groups)
+        return out
+
     # ------------------------------------------------------------------ hindsight optimum
     def hindsight_optimum(self, start_state: dict | None = None, n_steps: int | None = None) -> dict:
         """Every env's best alert schedule in hindsight: knowing the weather of the whole stretch, the env's own

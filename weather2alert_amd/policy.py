@@ -145,6 +145,57 @@ def check_policy_gradient(policy_gradient, kind, sample, reward_mode="sampled", 
     return policy_gradient
 
 
+IMITATION_KINDS = ("linear", "mlp")
+
+
+def pack_alert_days(alert_days: torch.Tensor, words: int) -> torch.Tensor:
+    """bool [N, T <= 32 * words] by day of the episode -> int32 [N, words], bit (t & 31) of word t >> 5: the bitmap the
+    rollout kernels write and w2a_posterior_returns / w2a_imitation_gradient_* read."""
+    n = alert_days.shape[0]
+    a32 = torch.nn.functional.pad(alert_days.to(torch.int32), (0, words * 32 - alert_days.shape[1])).view(n, words, 32)
+    # bits of one word are distinct powers of two: their int32 sum is the word (bit 31 as -2^31, no overflow)
+    shifts = torch.arange(32, dtype=torch.int32, device=alert_days.device)
+    return (a32 << shifts).sum(-1, dtype=torch.int32).contiguous()
+
+
+def check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: int, device, fixes=()):
+    """The arguments of ``imitation_gradient()`` that are not the policy itself: ValueError for a kind other than linear
+    or mlp, fixes other than "budget" (they change what the observation is), an alert_days that is not bool
+    [num_envs, T], an env_weight that is not a finite float [num_envs], and n_steps <= 0. Returns (packed schedule int32
+    [num_envs, ceil(T / 32)], env_weight f32 [num_envs] or None, days to run) on `device`."""
+    if kind not in IMITATION_KINDS:
+        raise ValueError(f"imitation_gradient() needs kind {' or '.join(repr(k) for k in IMITATION_KINDS)}, got {kind!r}")
+    extra = set(fixes) - {"budget"}
+    if extra:
+        raise ValueError(f"imitation_gradient() needs faithful observations; fixes {sorted(extra)} change what the "
+                         "observation is")
+    if n_steps is not None:
+        if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)):
+            raise ValueError(f"imitation_gradient(): n_steps must be an int, got {n_steps!r}")
+        if n_steps <= 0:
+            raise ValueError("imitation_gradient(): n_steps must be positive")
+    if alert_days is None:
+        raise ValueError("imitation_gradient(): alert_days is required")
+    ad = alert_days if torch.is_tensor(alert_days) else torch.as_tensor(np.asarray(alert_days))
+    if ad.dtype != torch.bool:
+        raise ValueError(f"imitation_gradient(): alert_days must be bool, got {ad.dtype}")
+    if ad.dim() != 2 or tuple(ad.shape) != (num_envs, T):
+        raise ValueError(f"imitation_gradient(): alert_days must be bool [{num_envs}, {T}] (by day of the episode), "
+                         f"got {tuple(ad.shape)}")
+    w = None
+    if env_weight is not None:
+        w = env_weight if torch.is_tensor(env_weight) else torch.as_tensor(np.asarray(env_weight))
+        if not w.is_floating_point():
+            raise ValueError(f"imitation_gradient(): env_weight must be float, got {w.dtype}")
+        if tuple(w.shape) != (num_envs,):
+            raise ValueError(f"imitation_gradient(): env_weight must be [{num_envs}], got {tuple(w.shape)}")
+        w = w.detach().to(device=device, dtype=torch.float32).contiguous()
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("imitation_gradient(): env_weight must be finite (as float32)")
+    words = (T + 31) // 32
+    return pack_alert_days(ad.to(device), words), w, (int(n_steps) if n_steps is not None else T)
+
+
 def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) -> torch.Tensor:
     """f32 [n_groups] (values [N]) or [n_groups, K] (values [N, K], e.g. returns under K posterior draws): the mean of
     `values` over each group's envs, per column (NaN for a group without envs), on the device of `values`: the groups'
