@@ -81,10 +81,11 @@ RESET = {"ragged": dict(seed=5, opts={"sample_budget": True, "sample_budget_type
 N_ENVS = {"ragged": 2000 + 37, "slot27": 1500 + 11, "ragged27": 2500 + 29}  # no multiples of 64 or 256
 
 
-def host_tuples(tb: Table, n: int):
+def host_tuples(tb: Table, n: int, cfg=None):
     """The episode tuples env.reset(seed=RESET[..]["seed"], options=RESET[..]["opts"]) draws on a fresh env with
-    env_gid0=GID0 and similar_climate_counties=True (the oracle's restatement of the device RNG)."""
-    ct, cfg = tb.ct, RESET[tb.name]
+    env_gid0=GID0 and similar_climate_counties=True (the oracle's restatement of the device RNG). `cfg`: the reset
+    settings of a table that is not one of the three above (tests/obs_layouts.py)."""
+    ct, cfg = tb.ct, (RESET[tb.name] if cfg is None else cfg)
     mode = 1 if cfg["opts"].get("sample_budget") else 0
     bkw = int(cfg["opts"].get("budget", -1))
     rows = [O.devrng_reset_tuple(cfg["seed"], GID0 + i, 0, ct.S, ct.Y, ct.n_samples, ct.fips_to_weather, ct.sim_ptr,
