@@ -610,6 +610,86 @@ int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
                                int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
                                float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
                                void *stream);
+/* w2a_imitation_gradient_linear / _mlp with a weight per call-day: the estimator becomes
+ *     g_e = w_e sum_s d_{s,e} delta_s dz_s/dtheta,   d_{s,e} = day_weight[s * num_envs + e]
+ * (device f32 [day_weight_days][num_envs], indexed by CALL-DAY and ENV ID -- the layout of w2a_value_gradient_*'s
+ * advantage; entries of days the env does not step are not read). ll_e and days are unchanged. day_weight = NULL is the
+ * unweighted call, bit for bit (the two entry points above forward NULL). The product w_e delta_s d_{s,e} is formed in
+ * fp64 in that order; the MLP form rounds it to f32 once, as before.
+ * With the schedule a sampled rollout ISSUED (w2a_rollout_*'s alert bitmap) and day_weight an advantage, this is the
+ * score-function gradient of that rollout with the advantage in place of the reward-to-go -- exactly so only under
+ * require_budget = 1, where attempts and issued alerts agree on every scored day; without it the policy gradient scores
+ * an attempt at the budget as a_s = 1 while the bitmap of issued alerts holds 0 there.
+ * day_weight is read as given: a NaN or infinite weight on a scored day goes into the gradient (the Python binding
+ * refuses non-finite weights).
+ * W2A_ERR_ARG as the unweighted entry points (same order), and for day_weight != NULL with day_weight_days < n_steps
+ * (after every NULL and alignment check, the workspace's included, before the handle is looked at). */
+int w2a_imitation_gradient_linear_weighted(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                           int32_t mask_words, const float *env_weight, const float *day_weight,
+                                           int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                           float *loglik, int32_t *days, void *stream);
+int w2a_imitation_gradient_mlp_weighted(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                                        int32_t mask_words, const float *env_weight, const float *day_weight,
+                                        int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                        float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+/* The gradient of a least-squares fit of a state-value function to the reward-to-go along a GIVEN alert schedule: the
+ * critic's counterpart of w2a_imitation_gradient_linear. `value` is a linear policy struct whose logit is read as a
+ * value, V(o) = weight[g] . o + bias[g]: no sigmoid, nothing drawn; value->sample, ->seed and ->require_budget are
+ * ignored. Every env is forced along its own schedule from the handle's CURRENT state and observation rows, with
+ * alert_mask, a*_s, the alert issued and o_s exactly as w2a_imitation_gradient_linear defines them. It reads the state,
+ * the tables, the schedule and obs and modifies none of them, nor the RNG, nor the handle's bookkeeping beyond making
+ * the canonical state words current.
+ * The estimator, for env e of group g over the call-days s = 0 .. S_e - 1 on which the env takes a step:
+ *   r_s      the reward w2a_step pays for that day under the env's own posterior draw
+ *   Q_s      = sum over s' >= s of r_s': undiscounted, truncated at the call's last day, nothing is bootstrapped
+ *   V_s      = V(o_s)
+ *   g_e      = w_e sum_s (Q_s - V_s) (o_s, 1), w_e = env_weight[e] (NULL: 1); envs finished on entry get zeros
+ * grad (device f32 [n_obs + 1][num_envs], column-major, as w2a_policy_gradient_linear) receives g_e; the mean of g_e
+ * over a group's envs is MINUS the gradient of 1/2 mean_e w_e sum_s (V_s - Q_s)^2, so theta += lr * mean descends it.
+ *   sq_error    f32 [num_envs]: sum_s (Q_s - V_s)^2 (unweighted)
+ *   days        i32 [num_envs]: S_e
+ *   ret         f32 [num_envs]: Q_0
+ *   advantage   nullable; device f32 [n_steps][num_envs] by call-day and ENV ID: Q_s - V_s on stepped days, 0 elsewhere
+ *               (the library zero-fills it on `stream` first)
+ *   workspace   w2a_value_gradient_linear_workspace_bytes(num_envs, n_steps) bytes, 256-B aligned: 9 B per env-day
+ * Numerics contract: r_s is computed by the statements of k_rollout_linear (the two fp64 chains, reward_from_logits,
+ * f32), V_s by its fp64 logit chain (bias first, slots 0..29 in slot order). The one-step residual
+ * y_s = r_s + V_{s+1} - V_s (V := 0 past the env's last stepped day of the call) is formed and kept in fp64,
+ * Q_s - V_s = sum_s y - sum_{s' < s} y_s' in fp64, the products with w_e and o_s and the sums over s in fp64; g_e,
+ * sq_error, ret and advantage are rounded to f32 once. An env's outputs do not depend on the other envs, the group
+ * layout or the visiting order (bit for bit). No atomics: two identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_imitation_gradient_linear refuses (same order; sample and require_budget are not looked at),
+ * for a NULL sq_error, days, ret or workspace and a workspace too small or misaligned; W2A_ERR_STATE while `stream`
+ * is recording a hipGraph. */
+size_t w2a_value_gradient_linear_workspace_bytes(int64_t num_envs, int32_t n_steps);
+int w2a_value_gradient_linear(w2a_env *env, const w2a_linear_policy *value, const uint32_t *alert_mask,
+                              int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                              float *grad, float *sq_error, int32_t *days, float *ret, float *advantage,
+                              void *workspace, size_t workspace_bytes, void *stream);
+/* The same estimator for an MLP, already reduced per group: V_s is the f32 logit k_rollout_mlp computes for o_s (the same
+ * mlp_logit_groups call on the same rows), (o_s, 1) becomes dV_s/dtheta, the backward pass of the f32 network as in
+ * w2a_policy_gradient_mlp, and
+ *     grad[g] = (1 / N_g) sum over the envs e of group g of  w_e sum_s (Q_s - V_s) dV_s/dtheta(theta_g)
+ * (envs finished on entry contribute zero and count; a group without envs gives a block of NaN). grad, value->order, the
+ * workspace and the partial-block rule are those of w2a_policy_gradient_mlp; the workspace size is
+ * w2a_value_gradient_mlp_workspace_bytes(...), equal to w2a_policy_gradient_mlp_workspace_bytes(...). sq_error, days, ret
+ * and advantage as above, per env.
+ * Numerics contract: r_s by the statements of k_rollout_mlp; y_s = r_s + V_{s+1} - V_s is formed in fp64 from the f32
+ * values and rounded to f32 once (the scratch holds f32); total = the fp64 sum of the rounded y_s, so Q_s - V_s is taken
+ * as total - sum_{s' < s} y_s', exactly the sum of the stored residuals of the days still to come: it differs from the
+ * unrounded residual by at most 2^-24 sum_{s' >= s} |y_s'|. c_s = w_e (Q_s - V_s) is formed in fp64 and rounded to
+ * f32 once; from there on the second pass, the fp64 sums over tiles and the reduction are the kernels of
+ * w2a_policy_gradient_mlp, run unchanged (day = (w_e, y_s)). sq_error and advantage come from the same fp64
+ * differences. No atomics: two identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_imitation_gradient_mlp refuses (same order; sample and require_budget are not looked at), for a
+ * NULL sq_error, days or ret; W2A_ERR_STATE while `stream` is recording a hipGraph. */
+size_t w2a_value_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                              int32_t n_layers);
+int w2a_value_gradient_mlp(w2a_env *env, const w2a_mlp_policy *value, const uint32_t *alert_mask, int32_t mask_words,
+                           const float *env_weight, int32_t n_steps, const float *obs, float *grad, float *sq_error,
+                           int32_t *days, float *ret, float *advantage, void *workspace, size_t workspace_bytes,
+                           void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

@@ -18,11 +18,15 @@
 //                       leaves day = (f32(w_e delta_s), 0), the alert issued, total = 1 and n_valid, so that
 //                       k_pgm_pass2's c_s = day.x (total - prefix) is exactly w_e delta_s (prefix sums day.y = 0): the
 //                       count, scan, pass 2 and reduce kernels of w2a_policy_gradient_mlp.hip.h run unchanged.
+// An optional weight per (call-day, env id) multiplies c_s (w2a_imitation_gradient_*_weighted: an advantage along a
+// sampled rollout's schedule makes this the score-function gradient with a learned baseline); NULL is the unweighted
+// computation bit for bit.
 // No floating-point atomics: identical calls give identical bits.
 struct ImitationArgs {
   const uint32_t *alert_mask;  // [n][mask_words] the schedule: bit (t & 31) of word t >> 5 = attempt an alert on day t
   int32_t mask_words;
   const float *env_weight;     // [n] w_e (nullable = 1)
+  const float *day_weight;     // [n_steps][n] d_{s,e} by call-day and ENV ID (nullable = 1): c_s = w_e delta_s d_{s,e}
   float *loglik;               // [n] sum_s m_s log pi(a*_s | o_s)
   int32_t *days;               // [n] sum_s m_s
 };
@@ -39,14 +43,25 @@ struct ImMlpArgs {
 };
 
 // the schedule's bit of day t; the word is loaded once per 32 days
-__device__ __forceinline__ uint32_t im_label(const ImitationArgs &im, uint32_t e, uint32_t t, uint32_t &word,
-                                             uint32_t &idx) {
+__device__ __forceinline__ uint32_t im_label_bits(const uint32_t *alert_mask, int32_t mask_words, uint32_t e, uint32_t t,
+                                                  uint32_t &word, uint32_t &idx) {
   const uint32_t wi = t >> 5;
   if (wi != idx) {
     idx = wi;
-    word = wi < (uint32_t)im.mask_words ? im.alert_mask[(size_t)e * im.mask_words + wi] : 0u;
+    word = wi < (uint32_t)mask_words ? alert_mask[(size_t)e * mask_words + wi] : 0u;
   }
   return (word >> (t & 31)) & 1u;
+}
+
+__device__ __forceinline__ uint32_t im_label(const ImitationArgs &im, uint32_t e, uint32_t t, uint32_t &word,
+                                             uint32_t &idx) {
+  return im_label_bits(im.alert_mask, im.mask_words, e, t, word, idx);
+}
+
+// c_s = w_e delta_s, times the day's weight where the caller gave one (the products are fp64)
+__device__ __forceinline__ double im_coef(const ImitationArgs &im, double w_e, float delta, size_t day_env) {
+  const double c = w_e * (double)delta;
+  return im.day_weight ? c * (double)im.day_weight[day_env] : c;
 }
 
 // log pi(a | z) of the Bernoulli policy pi(1) = sigmoid(z): -softplus(-z) for a = 1, -softplus(z) for a = 0, stable
@@ -106,7 +121,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
     scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
     if (scores) {
       const float delta = (float)lab - sigmoid_f32((float)z);
-      const double c = w_e * (double)delta;
+      const double c = im_coef(ia.im, w_e, delta, e);
 #pragma unroll
       for (int k = 0; k < RO64_SLOTS; ++k)
         if (la.slot_obs[k] >= 0) g[k] = c * (double)la.obs[obs0 + la.slot_obs[k]];
@@ -156,7 +171,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
         scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
         if (scores) {
           const float delta = (float)lab - sigmoid_f32((float)zp);
-          const double c = w_e * (double)delta;
+          const double c = im_coef(ia.im, w_e, delta, (size_t)(s + 1) * n + e);
 #pragma unroll
           for (int k = 0; k < RO64_SLOTS; ++k)
             if (la.slot_obs[k] >= 0) g[k] = fma(c, (double)xv[k], g[k]);
@@ -253,7 +268,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
     if (active) {
       const bool done = (t + 1 >= ndays);
       const size_t d = (size_t)s * n + slot;
-      ga.day[d] = make_float2((float)(w_e * (double)delta), 0.0f);  // pass 2: c_s = day.x (1 - 0)
+      ga.day[d] = make_float2((float)im_coef(ia.im, w_e, delta, (size_t)s * n + e), 0.0f);  // pass 2: c_s = day.x (1 - 0)
       ga.day_alert[d] = (uint8_t)actual;
       if (scores) { ll += im_log_pi((double)z, lab); scored += 1; }
       n_valid = s + 1;

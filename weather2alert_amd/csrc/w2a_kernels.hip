@@ -51,6 +51,7 @@
 #include "w2a_policy_gradient.hip.h"
 #include "w2a_policy_gradient_mlp.hip.h"
 #include "w2a_imitation.hip.h"
+#include "w2a_value.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1265,30 +1266,35 @@ static int check_imitation(const char *fn, const uint32_t *alert_mask, const flo
   return W2A_OK;
 }
 
-int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                                  float *grad, float *loglik, int32_t *days, void *stream) {
+static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy,
+                                     const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                                     const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
+                                     float *grad, float *loglik, int32_t *days, void *stream) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
-  if (!policy) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: NULL policy");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: n_steps must be positive");
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: NULL weight or bias");
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: n_groups must be positive");
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
   if (policy->sample != 0 && policy->sample != 1)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: sample must be 0 or 1");
+    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
   if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: require_budget must be 0 or 1");
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: weight must be 16-B aligned");
-  const int rc = check_imitation("w2a_imitation_gradient_linear", alert_mask, obs, grad, loglik, days);
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
+  const int rc = check_imitation(fn, alert_mask, obs, grad, loglik, days);
   if (rc != W2A_OK) return rc;
-  if (!env) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: NULL handle");
+  if (day_weight && day_weight_days < n_steps)
+    return fail(W2A_ERR_ARG, "%s: day_weight holds fewer call-days than n_steps", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: alert_mask needs ceil(T/32) words per env");
+    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: not available with corrected-semantics flags (they change "
-                             "what the observation is)");
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change "
+                             "what the observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
-  REFUSE_WHILE_CAPTURING("w2a_imitation_gradient_linear", stream);
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   ImLinearArgs ia;
   memset(&ia, 0, sizeof(ia));
   LinearRolloutArgs &la = ia.l;
@@ -1297,7 +1303,7 @@ int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy,
   for (int j = 0; j < env->tb.n_obs; ++j) {
     const int sl = env->obs_slot_host[j];
     if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_imitation_gradient_linear: an observation column sits on slot 30 or 31 of the feature row");
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
     obs_mask |= 1u << sl;
     la.slot_obs[sl] = (int8_t)j;
   }
@@ -1314,16 +1320,32 @@ int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy,
   la.obs_mask = obs_mask;
   la.obs = const_cast<float *>(obs);  // the kernel only reads it
   ia.im.alert_mask = alert_mask; ia.im.mask_words = mask_words; ia.im.env_weight = env_weight;
+  ia.im.day_weight = day_weight;
   ia.im.loglik = loglik; ia.im.days = days;
   ia.grad = grad;
   hipStream_t s = (hipStream_t)stream;
   // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, "w2a_imitation_gradient_linear")) return W2A_ERR_STATE;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
   hipLaunchKernelGGL(k_imitation_linear, dim3(g64), dim3(BLOCK), 0, s, ia);
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
+}
+
+int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                                  float *grad, float *loglik, int32_t *days, void *stream) {
+  return imitation_gradient_linear("w2a_imitation_gradient_linear", env, policy, alert_mask, mask_words, env_weight,
+                                   nullptr, 0, n_steps, obs, grad, loglik, days, stream);
+}
+
+int w2a_imitation_gradient_linear_weighted(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                           int32_t mask_words, const float *env_weight, const float *day_weight,
+                                           int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                           float *loglik, int32_t *days, void *stream) {
+  return imitation_gradient_linear("w2a_imitation_gradient_linear_weighted", env, policy, alert_mask, mask_words,
+                                   env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream);
 }
 
 // the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
@@ -1332,45 +1354,50 @@ size_t w2a_imitation_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_st
   return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
 }
 
-int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                               float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
-                               void *stream) {
+static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy,
+                                  const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                                  const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
+                                  float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
-  if (!policy) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL policy");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_steps must be positive");
-  if (!policy->params) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL params");
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_groups must be positive");
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
   if (policy->n_layers != 1 && policy->n_layers != 2)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_layers must be 1 or 2");
+    return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
   if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: width must be 16, 32 or 64");
+    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
   if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
+    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
   if (policy->sample != 0 && policy->sample != 1)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: sample must be 0 or 1");
+    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
   if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: require_budget must be 0 or 1");
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: params must be 16-B aligned");
-  const int rc = check_imitation("w2a_imitation_gradient_mlp", alert_mask, obs, grad, loglik, days);
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
+  const int rc = check_imitation(fn, alert_mask, obs, grad, loglik, days);
   if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL workspace");
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: workspace must be 256-B aligned");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: NULL handle");
+  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
+  if (day_weight && day_weight_days < n_steps)
+    return fail(W2A_ERR_ARG, "%s: day_weight holds fewer call-days than n_steps", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: alert_mask needs ceil(T/32) words per env");
+    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: not available with corrected-semantics flags (they change what "
-                             "the observation is)");
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
+                             "the observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
   const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
   if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: n_groups * block size must stay below 2^31 floats");
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
   const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
   if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "w2a_imitation_gradient_mlp: workspace smaller than w2a_imitation_gradient_mlp_workspace_bytes");
-  REFUSE_WHILE_CAPTURING("w2a_imitation_gradient_mlp", stream);
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_imitation_gradient_mlp_workspace_bytes", fn);
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   ImMlpArgs ia;
   memset(&ia, 0, sizeof(ia));
   MlpGradArgs &ga = ia.g;
@@ -1380,7 +1407,7 @@ int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
   for (int j = 0; j < env->tb.n_obs; ++j) {
     const int sl = env->obs_slot_host[j];
     if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_imitation_gradient_mlp: an observation column sits on slot 30 or 31 of the feature row");
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
     obs_mask |= 1u << sl;
     ma.slot_obs[sl] = (int8_t)j;
   }
@@ -1413,10 +1440,11 @@ int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
   ga.partial = reinterpret_cast<double *>(ws + L.partial);
   ga.grad = grad;
   ia.im.alert_mask = alert_mask; ia.im.mask_words = mask_words; ia.im.env_weight = env_weight;
+  ia.im.day_weight = day_weight;
   ia.im.loglik = loglik; ia.im.days = days;
   hipStream_t s = (hipStream_t)stream;
   // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, "w2a_imitation_gradient_mlp")) return W2A_ERR_STATE;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
   switch (policy->width * 4 + policy->n_layers) {
     case 16 * 4 + 1: launch_im<16, 1>(ia, g64, s); break;
@@ -1425,6 +1453,203 @@ int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
     case 32 * 4 + 2: launch_im<32, 2>(ia, g64, s); break;
     case 64 * 4 + 1: launch_im<64, 1>(ia, g64, s); break;
     default: launch_im<64, 2>(ia, g64, s); break;
+  }
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                               float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+  return imitation_gradient_mlp("w2a_imitation_gradient_mlp", env, policy, alert_mask, mask_words, env_weight, nullptr,
+                                0, n_steps, obs, grad, loglik, days, workspace, workspace_bytes, stream);
+}
+
+int w2a_imitation_gradient_mlp_weighted(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                                        int32_t mask_words, const float *env_weight, const float *day_weight,
+                                        int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                        float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+  return imitation_gradient_mlp("w2a_imitation_gradient_mlp_weighted", env, policy, alert_mask, mask_words, env_weight,
+                                day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
+                                workspace_bytes, stream);
+}
+
+// the checks w2a_value_gradient_linear and _mlp share once the network's own have passed (same order in both)
+static int check_value(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
+                       const float *sq_error, const int32_t *days, const float *ret) {
+  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to follow)", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!grad || !sq_error || !days || !ret) return fail(W2A_ERR_ARG, "%s: NULL grad, sq_error, days or ret", fn);
+  return W2A_OK;
+}
+
+// scratch of w2a_value_gradient_linear: y_s (fp64) and the alert issued, per (call-day, env) -- 9 B, as the policy gradient's
+size_t w2a_value_gradient_linear_workspace_bytes(int64_t num_envs, int32_t n_steps) {
+  return w2a_policy_gradient_workspace_bytes(num_envs, n_steps);
+}
+
+int w2a_value_gradient_linear(w2a_env *env, const w2a_linear_policy *value, const uint32_t *alert_mask,
+                              int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                              float *grad, float *sq_error, int32_t *days, float *ret, float *advantage,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
+  if (!value) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL value");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: n_steps must be positive");
+  if (!value->weight || !value->bias) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL weight or bias");
+  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: n_groups must be positive");
+  if ((uintptr_t)value->weight & 15) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: weight must be 16-B aligned");
+  const int rc = check_value("w2a_value_gradient_linear", alert_mask, obs, grad, sq_error, days, ret);
+  if (rc != W2A_OK) return rc;
+  if (!workspace) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL workspace");
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: workspace must be 256-B aligned");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL handle");
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: alert_mask needs ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: not available with corrected-semantics flags (they change what "
+                             "the observation and the reward are)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  if (workspace_bytes < w2a_value_gradient_linear_workspace_bytes(env->n, n_steps))
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: workspace smaller than w2a_value_gradient_linear_workspace_bytes");
+  REFUSE_WHILE_CAPTURING("w2a_value_gradient_linear", stream);
+  VgLinearArgs va;
+  memset(&va, 0, sizeof(va));
+  LinearRolloutArgs &la = va.l;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_value_gradient_linear: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    la.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = la.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.n_steps = n_steps;
+  a.order = env->order;
+  la.weight = reinterpret_cast<const float4 *>(value->weight);
+  la.bias = value->bias;
+  la.group = value->group;
+  la.n_groups = value->n_groups;
+  la.n_obs = env->tb.n_obs;
+  la.obs_mask = obs_mask;
+  la.obs = const_cast<float *>(obs);  // the kernel only reads it
+  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
+  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
+  va.day_y = reinterpret_cast<double *>(workspace);
+  va.day_alert = reinterpret_cast<uint8_t *>(workspace) + align256(sizeof(double) * (size_t)env->n * (size_t)n_steps);
+  va.grad = grad;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, "w2a_value_gradient_linear")) return W2A_ERR_STATE;
+  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  hipLaunchKernelGGL(k_value_gradient_linear, dim3(g64), dim3(BLOCK), 0, s, va);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
+size_t w2a_value_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                              int32_t n_layers) {
+  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
+}
+
+int w2a_value_gradient_mlp(w2a_env *env, const w2a_mlp_policy *value, const uint32_t *alert_mask, int32_t mask_words,
+                           const float *env_weight, int32_t n_steps, const float *obs, float *grad, float *sq_error,
+                           int32_t *days, float *ret, float *advantage, void *workspace, size_t workspace_bytes,
+                           void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
+  if (!value) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL value");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_steps must be positive");
+  if (!value->params) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL params");
+  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_groups must be positive");
+  if (value->n_layers != 1 && value->n_layers != 2)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_layers must be 1 or 2");
+  if (value->width != 16 && value->width != 32 && value->width != 64)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: width must be 16, 32 or 64");
+  if (value->activation != W2A_MLP_TANH && value->activation != W2A_MLP_RELU)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
+  if ((uintptr_t)value->params & 15) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: params must be 16-B aligned");
+  const int rc = check_value("w2a_value_gradient_mlp", alert_mask, obs, grad, sq_error, days, ret);
+  if (rc != W2A_OK) return rc;
+  if (!workspace) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL workspace");
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: workspace must be 256-B aligned");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL handle");
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: alert_mask needs ceil(T/32) words per env");
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: not available with corrected-semantics flags (they change what "
+                             "the observation and the reward are)");
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+  const int64_t stride = W2A_MLP_STRIDE((int64_t)value->width, value->n_layers);
+  if ((int64_t)value->n_groups * stride >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_groups * block size must stay below 2^31 floats");
+  const PgmLayout L = pgm_layout(env->n, n_steps, value->n_groups, value->width, value->n_layers);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: workspace smaller than w2a_value_gradient_mlp_workspace_bytes");
+  REFUSE_WHILE_CAPTURING("w2a_value_gradient_mlp", stream);
+  VgMlpArgs va;
+  memset(&va, 0, sizeof(va));
+  MlpGradArgs &ga = va.g;
+  MlpRolloutArgs &ma = ga.m;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "w2a_value_gradient_mlp: an observation column sits on slot 30 or 31 of the feature row");
+    obs_mask |= 1u << sl;
+    ma.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = ma.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.n_steps = n_steps;
+  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the network's (group-major) or identity
+  a.order = reinterpret_cast<const uint32_t *>(value->order);
+  ma.params = value->params;
+  ma.group = value->group;
+  ma.n_groups = value->n_groups;
+  ma.stride = (int32_t)stride;
+  ma.activation = value->activation;
+  ma.n_obs = env->tb.n_obs;
+  ma.obs_mask = obs_mask;
+  ma.obs = const_cast<float *>(obs);  // the kernels only read it
+  char *ws = reinterpret_cast<char *>(workspace);
+  ga.day = reinterpret_cast<float2 *>(ws + L.day);
+  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
+  ga.total = reinterpret_cast<double *>(ws + L.total);
+  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
+  ga.tiles = L.tiles;
+  ga.n_chunks = L.n_chunks;
+  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
+  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
+  ga.capacity = L.capacity;
+  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
+  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
+  ga.partial = reinterpret_cast<double *>(ws + L.partial);
+  ga.grad = grad;
+  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
+  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, "w2a_value_gradient_mlp")) return W2A_ERR_STATE;
+  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  switch (value->width * 4 + value->n_layers) {
+    case 16 * 4 + 1: launch_vg<16, 1>(va, g64, s); break;
+    case 16 * 4 + 2: launch_vg<16, 2>(va, g64, s); break;
+    case 32 * 4 + 1: launch_vg<32, 1>(va, g64, s); break;
+    case 32 * 4 + 2: launch_vg<32, 2>(va, g64, s); break;
+    case 64 * 4 + 1: launch_vg<64, 1>(va, g64, s); break;
+    default: launch_vg<64, 2>(va, g64, s); break;
   }
   HIP_TRY(hipGetLastError());
   end_call(env, s);

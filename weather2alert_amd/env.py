@@ -1128,7 +1128,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return out
 
     # ------------------------------------------------------------------ imitation: likelihood of a given schedule
-    def imitation_gradient(self, policy: dict, alert_days, env_weight=None, n_steps: int | None = None) -> dict:
+    def imitation_gradient(self, policy: dict, alert_days, env_weight=None, n_steps: int | None = None,
+                           day_weight=None) -> dict:
         """The gradient of the log-likelihood of a GIVEN alert schedule under a linear or MLP policy: the supervised
         counterpart of rollout(policy_gradient=...). Every env is forced along its own schedule from its current state
         and the policy is evaluated on the rows it would have held (teacher forcing), all inside the kernel: behaviour
@@ -1141,6 +1142,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
           env_weight  optional float [N], finite (default 1)
           n_steps     days from every env's current day (default: to the end of every episode; an env stops after its
                       terminal day, as in rollout())
+          day_weight  optional device float [S >= n_steps, N], finite (ValueError), by call-day and ENV ID, the layout of
+                      value_gradient()'s "advantage": the estimator becomes
+                      g_e = w_e sum_s d_{s,e} delta_s dz_s/dtheta ("log_likelihood" and "days" are unchanged; None is
+                      today's result bit for bit). With the schedule a sampled
+                      rollout(alert_mask=True) issued and day_weight an advantage this is the score-function gradient
+                      of that rollout with a learned baseline -- exactly so only under require_budget=True, where
+                      attempts and issued alerts agree on every scored day; without it rollout(policy_gradient=...)
+                      scores an attempt at the budget as a_s = 1 while "alert_days" holds 0 there
         Returns
           "policy_gradient"       linear: {"weight" f32 [G, n_obs], "bias" f32 [G]}; mlp: {"layers": [(dW, db), ...]}: the
                                   gradient of "group_log_likelihood" (shapes, column order and NaN for a group without
@@ -1159,6 +1168,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes)
         check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
         pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        dw = _policy.check_day_weight(day_weight, min(steps, 2**31 - 1), n, dev)
         if self._needs_reset:
             raise RuntimeError("call reset() before imitation_gradient()")
         if not self._obs_current:
@@ -1176,10 +1186,16 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 lp.group = None if pol.group is None else pol.group.data_ptr()
                 lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
                 rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
-                _ffi.check(self._lib.w2a_imitation_gradient_linear(
-                    self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
-                    out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream()),
-                    "w2a_imitation_gradient_linear")
+                if dw is None:
+                    _ffi.check(self._lib.w2a_imitation_gradient_linear(
+                        self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
+                        out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream()),
+                        "w2a_imitation_gradient_linear")
+                else:
+                    _ffi.check(self._lib.w2a_imitation_gradient_linear_weighted(
+                        self._h, C.byref(lp), mask.data_ptr(), words, wp, dw.data_ptr(), int(dw.shape[0]), steps,
+                        self._obs.data_ptr(), rows.data_ptr(), out["log_likelihood"].data_ptr(), out["days"].data_ptr(),
+                        self._stream()), "w2a_imitation_gradient_linear_weighted")
                 # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
                 g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
                 out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
@@ -1197,10 +1213,17 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                      device=dev)
                 ws = torch.empty(self._lib.w2a_imitation_gradient_mlp_workspace_bytes(
                     n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
-                _ffi.check(self._lib.w2a_imitation_gradient_mlp(
-                    self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
-                    out["log_likelihood"].data_ptr(), out["days"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                    "w2a_imitation_gradient_mlp")
+                if dw is None:
+                    _ffi.check(self._lib.w2a_imitation_gradient_mlp(
+                        self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
+                        out["log_likelihood"].data_ptr(), out["days"].data_ptr(), ws.data_ptr(), ws.numel(),
+                        self._stream()), "w2a_imitation_gradient_mlp")
+                else:
+                    _ffi.check(self._lib.w2a_imitation_gradient_mlp_weighted(
+                        self._h, C.byref(mp), mask.data_ptr(), words, wp, dw.data_ptr(), int(dw.shape[0]), steps,
+                        self._obs.data_ptr(), blocks.data_ptr(), out["log_likelihood"].data_ptr(),
+                        out["days"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                        "w2a_imitation_gradient_mlp_weighted")
                 out["policy_gradient"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden,
                                                                             pol.n_out)}
             wll = out["log_likelihood"].double() if w is None else (w.double() * out["log_likelihood"].double())
@@ -1208,6 +1231,101 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 out["group_log_likelihood"] = wll.mean().to(torch.float32).reshape(1)
             else:
                 out["group_log_likelihood"] = _policy.group_mean(wll, pol.group, pol.n_groups)
+        return out
+
+    # ------------------------------------------------------------------ critic: value regression along a schedule
+    def value_gradient(self, value: dict, alert_days, env_weight=None, n_steps: int | None = None,
+                       advantage: bool = False) -> dict:
+        """The gradient of a least-squares fit of a learned state-value function to the reward-to-go along a GIVEN
+        alert schedule, and the advantages it leaves -- the critic of an on-device actor-critic loop, with no
+        observation row recorded. `value` is a kind="linear" or kind="mlp" dict as rollout() takes it (groups, padding,
+        the two-row output and policy.mlp_from_module included) whose logit is read as a state value,
+        V_theta(o) = z(o): no sigmoid, nothing sampled; "sample", "seed" and "require_budget" are ignored.
+        Every env is forced along its own schedule from its current state and observation rows exactly as in
+        imitation_gradient(): alert_days bool [N, T] by day of the episode holds the actions ATTEMPTED, an attempt
+        with used == budget issues no alert, o_s is the row step() would have returned. env_weight and n_steps as there.
+        Per env e over the call-days s = 0 .. S_e - 1 it steps:
+          r_s  the reward step() pays for that day under the env's own posterior draw
+          Q_s  = sum_{s' >= s} r_s'  (undiscounted, truncated at the end of the call: nothing is bootstrapped)
+          V_s  = z(o_s)  (mlp: the f32 logit k_rollout_mlp forms on that row; linear: k_rollout_linear's fp64 chain)
+          g_e  = w_e sum_s (Q_s - V_s) dV_s/dtheta
+        and per group the mean of g_e over its envs (envs finished on entry give zero and count; NaN for a group
+        without envs), so ``theta += lr * grad`` DESCENDS 1/2 mean_e w_e sum_s (V_s - Q_s)^2. Returns
+          "value_gradient"  in the shapes of rollout()'s "policy_gradient": linear {"weight" f32 [G, n_obs], "bias" f32
+                            [G]}; mlp {"layers": [(dW, db), ...]}, usable with policy.mlp_grad_to_module
+          "sq_error"        f32 [N]  sum_s (Q_s - V_s)^2
+          "days"            i32 [N]  S_e
+          "return"          f32 [N]  Q_0
+          "group_loss"      f32 [G]  mean over the group's envs of 1/2 env_weight * sq_error
+          "advantage"       (advantage=True) f32 [S, N] by call-day and ENV ID: Q_s - V_s on stepped days, 0 elsewhere
+                            -- the day_weight of imitation_gradient(), which along a sampled rollout's schedule gives
+                            the policy gradient with this critic as baseline
+        No side effects: the state, the tables, the schedule, the observation buffer and the RNG are only read. No
+        floating-point atomics: two identical calls give identical bits. Needs the observation buffer current
+        (RuntimeError as rollout(kind="linear")), reward_mode="sampled" and faithful semantics (ValueError for what
+        rollout(policy_gradient=...) refuses: rewards enter here). Discounting, GAE(lambda), bootstrapping past the call
+        and clipped ratios are not offered. w2a_value_gradient_linear / _mlp (include/w2a.h)."""
+        kind = value.get("kind") if isinstance(value, dict) else None
+        ct, n, dev = self.ct, self.num_envs, self.device
+        mask, w, steps = _policy.check_value_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.reward_mode,
+                                                  self.fixes)
+        check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
+        pol = check(value, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        if self._needs_reset:
+            raise RuntimeError("call reset() before value_gradient()")
+        if not self._obs_current:
+            raise RuntimeError(f"value_gradient(kind={kind!r}) reads the observation buffer, which does not hold the "
+                               "agents' current rows (write_obs=False, a built-in rollout or load_state_dict since the "
+                               "last step()/reset()): call step() or reset() first")
+        words = mask.shape[1]
+        out = {"sq_error": torch.empty(n, dtype=torch.float32, device=dev),
+               "days": torch.empty(n, dtype=torch.int32, device=dev),
+               "return": torch.empty(n, dtype=torch.float32, device=dev)}
+        if advantage:
+            out["advantage"] = torch.empty((steps, n), dtype=torch.float32, device=dev)  # zero-filled by the library
+        ap = out["advantage"].data_ptr() if advantage else None
+        wp = None if w is None else w.data_ptr()
+        with torch.cuda.device(dev):
+            if kind == "linear":
+                lp = _ffi.LinearPolicy()
+                lp.weight, lp.bias = pol.weight_slots.data_ptr(), pol.bias.data_ptr()
+                lp.group = None if pol.group is None else pol.group.data_ptr()
+                lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, 0, 0
+                rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
+                ws = torch.empty(self._lib.w2a_value_gradient_linear_workspace_bytes(n, steps), dtype=torch.uint8,
+                                 device=dev)
+                _ffi.check(self._lib.w2a_value_gradient_linear(
+                    self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
+                    out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, ws.data_ptr(),
+                    ws.numel(), self._stream()), "w2a_value_gradient_linear")
+                # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
+                g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
+                out["value_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
+            else:
+                mp = _ffi.MlpPolicy()
+                mp.params = pol.params.data_ptr()
+                mp.group = None if pol.group is None else pol.group.data_ptr()
+                # always group-major (the partial blocks are sized for it), whatever "order" a rollout would use
+                gorder = None if pol.group is None else (pol.order if pol.group_major else _policy.group_order(pol.group))
+                mp.order = None if gorder is None else gorder.data_ptr()
+                mp.n_groups, mp.n_layers, mp.width = pol.n_groups, pol.n_layers, pol.width
+                mp.activation = _ffi.MLP_ACTIVATIONS[pol.activation]
+                mp.sample, mp.require_budget, mp.seed = 0, 0, 0
+                blocks = torch.empty((pol.n_groups, _policy.mlp_stride(pol.width, pol.n_layers)), dtype=torch.float32,
+                                     device=dev)
+                ws = torch.empty(self._lib.w2a_value_gradient_mlp_workspace_bytes(
+                    n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
+                _ffi.check(self._lib.w2a_value_gradient_mlp(
+                    self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
+                    out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, ws.data_ptr(),
+                    ws.numel(), self._stream()), "w2a_value_gradient_mlp")
+                out["value_gradient"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden,
+                                                                           pol.n_out)}
+            half = 0.5 * (out["sq_error"].double() if w is None else (w.double() * out["sq_error"].double()))
+            if pol.group is None:  # one group: the fp64 mean, rounded once
+                out["group_loss"] = half.mean().to(torch.float32).reshape(1)
+            else:
+                out["group_loss"] = _policy.group_mean(half, pol.group, pol.n_groups)
         return out
 
     # ------------------------------------------------------------------ hindsight optimum

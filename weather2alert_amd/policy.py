@@ -158,42 +158,73 @@ def pack_alert_days(alert_days: torch.Tensor, words: int) -> torch.Tensor:
     return (a32 << shifts).sum(-1, dtype=torch.int32).contiguous()
 
 
-def check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: int, device, fixes=()):
+def check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: int, device, fixes=(),
+                         who: str = "imitation_gradient()"):
     """The arguments of ``imitation_gradient()`` that are not the policy itself: ValueError for a kind other than linear
     or mlp, fixes other than "budget" (they change what the observation is), an alert_days that is not bool
     [num_envs, T], an env_weight that is not a finite float [num_envs], and n_steps <= 0. Returns (packed schedule int32
-    [num_envs, ceil(T / 32)], env_weight f32 [num_envs] or None, days to run) on `device`."""
+    [num_envs, ceil(T / 32)], env_weight f32 [num_envs] or None, days to run) on `device`. `who` names the caller in the
+    messages (value_gradient() takes the same arguments)."""
     if kind not in IMITATION_KINDS:
-        raise ValueError(f"imitation_gradient() needs kind {' or '.join(repr(k) for k in IMITATION_KINDS)}, got {kind!r}")
+        raise ValueError(f"{who} needs kind {' or '.join(repr(k) for k in IMITATION_KINDS)}, got {kind!r}")
     extra = set(fixes) - {"budget"}
     if extra:
-        raise ValueError(f"imitation_gradient() needs faithful observations; fixes {sorted(extra)} change what the "
+        raise ValueError(f"{who} needs faithful observations; fixes {sorted(extra)} change what the "
                          "observation is")
     if n_steps is not None:
         if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)):
-            raise ValueError(f"imitation_gradient(): n_steps must be an int, got {n_steps!r}")
+            raise ValueError(f"{who}: n_steps must be an int, got {n_steps!r}")
         if n_steps <= 0:
-            raise ValueError("imitation_gradient(): n_steps must be positive")
+            raise ValueError(f"{who}: n_steps must be positive")
     if alert_days is None:
-        raise ValueError("imitation_gradient(): alert_days is required")
+        raise ValueError(f"{who}: alert_days is required")
     ad = alert_days if torch.is_tensor(alert_days) else torch.as_tensor(np.asarray(alert_days))
     if ad.dtype != torch.bool:
-        raise ValueError(f"imitation_gradient(): alert_days must be bool, got {ad.dtype}")
+        raise ValueError(f"{who}: alert_days must be bool, got {ad.dtype}")
     if ad.dim() != 2 or tuple(ad.shape) != (num_envs, T):
-        raise ValueError(f"imitation_gradient(): alert_days must be bool [{num_envs}, {T}] (by day of the episode), "
+        raise ValueError(f"{who}: alert_days must be bool [{num_envs}, {T}] (by day of the episode), "
                          f"got {tuple(ad.shape)}")
     w = None
     if env_weight is not None:
         w = env_weight if torch.is_tensor(env_weight) else torch.as_tensor(np.asarray(env_weight))
         if not w.is_floating_point():
-            raise ValueError(f"imitation_gradient(): env_weight must be float, got {w.dtype}")
+            raise ValueError(f"{who}: env_weight must be float, got {w.dtype}")
         if tuple(w.shape) != (num_envs,):
-            raise ValueError(f"imitation_gradient(): env_weight must be [{num_envs}], got {tuple(w.shape)}")
+            raise ValueError(f"{who}: env_weight must be [{num_envs}], got {tuple(w.shape)}")
         w = w.detach().to(device=device, dtype=torch.float32).contiguous()
         if not bool(torch.isfinite(w).all()):
-            raise ValueError("imitation_gradient(): env_weight must be finite (as float32)")
+            raise ValueError(f"{who}: env_weight must be finite (as float32)")
     words = (T + 31) // 32
     return pack_alert_days(ad.to(device), words), w, (int(n_steps) if n_steps is not None else T)
+
+
+def check_day_weight(day_weight, n_steps: int, num_envs: int, device):
+    """``imitation_gradient(day_weight=...)``: None, or a float [S >= n_steps, num_envs] by call-day and env id (the
+    layout of value_gradient()'s "advantage"), finite, returned as contiguous f32 on `device`. ValueError otherwise
+    (every entry is checked, those of days an env does not step included: "advantage" holds zeros there)."""
+    if day_weight is None:
+        return None
+    d = day_weight if torch.is_tensor(day_weight) else torch.as_tensor(np.asarray(day_weight))
+    if not d.is_floating_point():
+        raise ValueError(f"imitation_gradient(): day_weight must be float, got {d.dtype}")
+    if d.dim() != 2 or d.shape[1] != num_envs:
+        raise ValueError(f"imitation_gradient(): day_weight must be [S, {num_envs}] (call-day, env id), got {tuple(d.shape)}")
+    if d.shape[0] < n_steps:
+        raise ValueError(f"imitation_gradient(): day_weight holds {d.shape[0]} call-days, the call runs {n_steps}")
+    d = d.detach().to(device=device, dtype=torch.float32).contiguous()
+    if not bool(torch.isfinite(d).all()):  # one pass over the weights and a sync, as for env_weight
+        raise ValueError("imitation_gradient(): day_weight must be finite (as float32)")
+    return d
+
+
+def check_value_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: int, device, reward_mode="sampled",
+                     fixes=()):
+    """The arguments of ``value_gradient()`` that are not the network itself: those of imitation_gradient(), and -- because
+    rewards enter -- what rollout(policy_gradient=...) refuses: reward_mode other than "sampled"."""
+    out = check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs, T, device, fixes, who="value_gradient()")
+    if reward_mode != "sampled":
+        raise ValueError("value_gradient() needs reward_mode='sampled'")
+    return out
 
 
 def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) -> torch.Tensor:
