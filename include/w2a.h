@@ -633,6 +633,76 @@ int w2a_imitation_gradient_mlp_weighted(w2a_env *env, const w2a_mlp_policy *poli
                                         int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
                                         float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
                                         void *stream);
+/* The gradient of the PPO-clip surrogate along a GIVEN alert schedule under a linear policy: what K epochs on the same
+ * episodes need, the clipped importance ratio formed inside the kernel. Every env is forced along its own schedule from
+ * the handle's CURRENT state and observation rows exactly as in w2a_imitation_gradient_linear: the same alert_mask, the
+ * same attempted-versus-issued rule, the same o_s and the same require_budget rule for m_s. It reads the state, the
+ * tables, the schedule, obs, advantage and old_log_prob and modifies none of them, nor the RNG, nor the handle's
+ * bookkeeping beyond making the canonical state words current: epochs over the same episodes need no reset in between.
+ * The estimator, for env e of group g on every scored call-day s (m_s = 1):
+ *   z_s      the policy's logit on o_s;  a_s the schedule's bit (the action ATTEMPTED);  p_s = sigmoid(z_s)
+ *   delta_s  = a_s - p_s
+ *   lp_s     = log pi(a_s | z_s): -softplus(-z_s) (a_s = 1) or -softplus(z_s) (a_s = 0)
+ *   rho_s    = exp(lp_s - old_log_prob[s * num_envs + e]); exactly 1 when old_log_prob is NULL
+ *   A_s      = advantage[s * num_envs + e]
+ *   lo, hi   = 1 - clip, 1 + clip
+ *   live_s   = !((A_s > 0 && rho_s > hi) || (A_s < 0 && rho_s < lo)): the gradient of min(rho A, clamp(rho, lo, hi) A)
+ *   H_s      = -p_s log p_s - (1 - p_s) log(1 - p_s), the Bernoulli entropy;  dH_s/dz = -z_s p_s (1 - p_s)
+ *   L_e      = sum_s min(rho_s A_s, clamp(rho_s, lo, hi) A_s)
+ *   g_e      = w_e sum_s [ live_s rho_s A_s delta_s + beta dH_s/dz ] (o_s, 1),  beta = entropy_coef,
+ *              w_e = env_weight[e] (NULL: 1); envs finished on entry get zeros
+ * The mean of g_e over a group's envs is the gradient of that group's mean w_e (L_e + beta sum_s H_s), so
+ * theta += lr * mean is an ascent step on the clipped surrogate with an entropy bonus. With old_log_prob = NULL and
+ * entropy_coef = 0 the estimator is w2a_imitation_gradient_linear_weighted's with day_weight = advantage.
+ *   advantage      device f32 [advantage_days >= n_steps][num_envs] by CALL-DAY and ENV ID (the layout of
+ *                  w2a_value_gradient_*'s advantage and of day_weight); entries of days that are not scored are not read.
+ *                  Read as given: a NaN or infinite entry on a scored day goes into the outputs
+ *   old_log_prob   nullable; device f32 [old_log_prob_days >= n_steps][num_envs], same layout: lp_s under the policy that
+ *                  collected the schedule -- the log_prob output of an earlier call
+ *   grad           device f32 [n_obs + 1][num_envs], column-major as w2a_imitation_gradient_linear: g_e
+ *   surrogate      f32 [num_envs]: L_e (unweighted)
+ *   clipped_days   i32 [num_envs]: the scored days with live_s = 0
+ *   approx_kl      f32 [num_envs]: sum_s ((rho_s - 1) - log rho_s), summed and not averaged
+ *   entropy        f32 [num_envs]: sum_s H_s
+ *   days           i32 [num_envs]: sum_s m_s, as w2a_imitation_gradient_linear
+ *   log_prob       nullable; device f32 [n_steps][num_envs] by call-day and env id: lp_s on scored days, 0 elsewhere (the
+ *                  library zero-fills it on `stream` first). This is how the first epoch obtains old_log_prob
+ * Numerics contract: z_s by the statements of k_rollout_linear (the fp64 FMA chain), delta_s in f32 from its f32 sigmoid,
+ * as w2a_imitation_gradient_linear; lp_s, rho_s, the clip test, p_s and 1 - p_s of the entropy, the coefficient
+ * (w_e delta_s) (rho_s A_s) + w_e beta dH_s/dz, its products with o_s and every sum over s are fp64; g_e, surrogate,
+ * approx_kl, entropy and log_prob are rounded to f32 once. An env's outputs do not depend on the other envs, the group
+ * layout or the visiting order (bit for bit). No scratch memory, no atomics: identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_imitation_gradient_linear_weighted refuses (checked in the same order; a NULL surrogate,
+ * clipped_days, approx_kl or entropy counts as a NULL output), and -- where that call checks day_weight_days -- for a
+ * NULL advantage, advantage_days < n_steps, old_log_prob != NULL with old_log_prob_days < n_steps, clip < 0 and a clip
+ * or entropy_coef that is not finite; W2A_ERR_STATE while `stream` is recording a hipGraph. */
+int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, const float *advantage,
+                                  int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                  double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                                  float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                                  int32_t *days, float *log_prob, void *stream);
+/* The same estimator for an MLP policy, already reduced per group: z_s is the f32 logit k_rollout_mlp computes for o_s,
+ * (o_s, 1) becomes dz_s/dtheta, the backward pass of the f32 network as in w2a_policy_gradient_mlp, and
+ *     grad[g] = (1 / N_g) sum over the envs e of group g of  w_e sum_s [ live_s rho_s A_s delta_s + beta dH_s/dz ] dz_s/dtheta
+ * (envs finished on entry contribute zero and count; a group without envs gives a block of NaN). grad, policy->order, the
+ * workspace and the partial-block rule are those of w2a_policy_gradient_mlp; the workspace size is
+ * w2a_surrogate_gradient_mlp_workspace_bytes(...), equal to w2a_imitation_gradient_mlp_workspace_bytes(...). The other
+ * outputs as above, per env.
+ * Numerics contract: delta_s in f32 as w2a_imitation_gradient_mlp; lp_s, rho_s, the clip test, the entropy terms and the
+ * coefficient c_s are formed in fp64 from the f32 logit and c_s is rounded to f32 once; from there on the second pass,
+ * the fp64 sums over tiles and the reduction are the kernels of w2a_policy_gradient_mlp, run unchanged (day = (c_s, 0),
+ * total = 1). No atomics: two identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_imitation_gradient_mlp_weighted refuses (same order) and for the arguments listed above;
+ * W2A_ERR_STATE while `stream` is recording a hipGraph. */
+size_t w2a_surrogate_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                  int32_t n_layers);
+int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, const float *advantage,
+                               int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                               double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                               float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                               int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes, void *stream);
 /* The gradient of a least-squares fit of a state-value function to the reward-to-go along a GIVEN alert schedule: the
  * critic's counterpart of w2a_imitation_gradient_linear. `value` is a linear policy struct whose logit is read as a
  * value, V(o) = weight[g] . o + bias[g]: no sigmoid, nothing drawn; value->sample, ->seed and ->require_budget are

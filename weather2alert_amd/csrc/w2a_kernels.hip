@@ -30,6 +30,7 @@
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -51,6 +52,7 @@
 #include "w2a_policy_gradient.hip.h"
 #include "w2a_policy_gradient_mlp.hip.h"
 #include "w2a_imitation.hip.h"
+#include "w2a_surrogate.hip.h"
 #include "w2a_value.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
@@ -1475,6 +1477,219 @@ int w2a_imitation_gradient_mlp_weighted(w2a_env *env, const w2a_mlp_policy *poli
   return imitation_gradient_mlp("w2a_imitation_gradient_mlp_weighted", env, policy, alert_mask, mask_words, env_weight,
                                 day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
                                 workspace_bytes, stream);
+}
+
+// the checks w2a_surrogate_gradient_linear and _mlp share once the policy's own have passed (same order in both)
+static int check_surrogate_outputs(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
+                                   const float *surrogate, const int32_t *clipped_days, const float *approx_kl,
+                                   const float *entropy, const int32_t *days) {
+  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to score)", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!grad || !surrogate || !clipped_days || !approx_kl || !entropy || !days)
+    return fail(W2A_ERR_ARG, "%s: NULL grad, surrogate, clipped_days, approx_kl, entropy or days", fn);
+  return W2A_OK;
+}
+
+// ... and what the surrogate adds to the weighted imitation calls' checks, where they check day_weight_days
+static int check_surrogate_inputs(const char *fn, const float *advantage, int32_t advantage_days,
+                                  const float *old_log_prob, int32_t old_log_prob_days, double clip,
+                                  double entropy_coef, int32_t n_steps) {
+  if (!advantage) return fail(W2A_ERR_ARG, "%s: NULL advantage", fn);
+  if (advantage_days < n_steps) return fail(W2A_ERR_ARG, "%s: advantage holds fewer call-days than n_steps", fn);
+  if (old_log_prob && old_log_prob_days < n_steps)
+    return fail(W2A_ERR_ARG, "%s: old_log_prob holds fewer call-days than n_steps", fn);
+  if (!isfinite(clip) || clip < 0.0) return fail(W2A_ERR_ARG, "%s: clip must be finite and not negative", fn);
+  if (!isfinite(entropy_coef)) return fail(W2A_ERR_ARG, "%s: entropy_coef must be finite", fn);
+  return W2A_OK;
+}
+
+int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, const float *advantage,
+                                  int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                  double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                                  float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                                  int32_t *days, float *log_prob, void *stream) {
+  const char *fn = "w2a_surrogate_gradient_linear";
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
+  if (policy->sample != 0 && policy->sample != 1)
+    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
+  int rc = check_surrogate_outputs(fn, alert_mask, obs, grad, surrogate, clipped_days, approx_kl, entropy, days);
+  if (rc != W2A_OK) return rc;
+  rc = check_surrogate_inputs(fn, advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps);
+  if (rc != W2A_OK) return rc;
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change "
+                             "what the observation is)", fn);
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  SgLinearArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  LinearRolloutArgs &la = sa.l;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
+    obs_mask |= 1u << sl;
+    la.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = la.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.n_steps = n_steps;
+  a.order = env->order;
+  la.weight = reinterpret_cast<const float4 *>(policy->weight);
+  la.bias = policy->bias;
+  la.group = policy->group;
+  la.n_groups = policy->n_groups;
+  la.n_obs = env->tb.n_obs;
+  la.obs_mask = obs_mask;
+  la.obs = const_cast<float *>(obs);  // the kernel only reads it
+  sa.sg.alert_mask = alert_mask; sa.sg.mask_words = mask_words; sa.sg.env_weight = env_weight;
+  sa.sg.advantage = advantage; sa.sg.old_log_prob = old_log_prob;
+  sa.sg.lo = 1.0 - clip; sa.sg.hi = 1.0 + clip; sa.sg.beta = entropy_coef;
+  sa.sg.log_prob = log_prob; sa.sg.surrogate = surrogate; sa.sg.clipped = clipped_days; sa.sg.approx_kl = approx_kl;
+  sa.sg.entropy = entropy; sa.sg.days = days;
+  sa.grad = grad;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  if (log_prob) HIP_TRY(hipMemsetAsync(log_prob, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  hipLaunchKernelGGL(k_surrogate_linear, dim3(g64), dim3(BLOCK), 0, s, sa);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// the workspace of w2a_imitation_gradient_mlp: the same scratch and partial blocks serve the same second pass
+size_t w2a_surrogate_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                  int32_t n_layers) {
+  return w2a_imitation_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
+}
+
+int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, const float *advantage,
+                               int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                               double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                               float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                               int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes, void *stream) {
+  const char *fn = "w2a_surrogate_gradient_mlp";
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
+  if (policy->n_layers != 1 && policy->n_layers != 2)
+    return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
+  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
+    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
+  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
+    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
+  if (policy->sample != 0 && policy->sample != 1)
+    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
+  if (policy->require_budget != 0 && policy->require_budget != 1)
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
+  int rc = check_surrogate_outputs(fn, alert_mask, obs, grad, surrogate, clipped_days, approx_kl, entropy, days);
+  if (rc != W2A_OK) return rc;
+  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
+  rc = check_surrogate_inputs(fn, advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps);
+  if (rc != W2A_OK) return rc;
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
+                             "the observation is)", fn);
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
+  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
+  const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_surrogate_gradient_mlp_workspace_bytes", fn);
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  SgMlpArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  MlpGradArgs &ga = sa.g;
+  MlpRolloutArgs &ma = ga.m;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
+    obs_mask |= 1u << sl;
+    ma.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = ma.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.pol.require_budget = policy->require_budget;
+  a.n_steps = n_steps;
+  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the policy's (group-major) or identity
+  a.order = reinterpret_cast<const uint32_t *>(policy->order);
+  ma.params = policy->params;
+  ma.group = policy->group;
+  ma.n_groups = policy->n_groups;
+  ma.stride = (int32_t)stride;
+  ma.activation = policy->activation;
+  ma.n_obs = env->tb.n_obs;
+  ma.obs_mask = obs_mask;
+  ma.obs = const_cast<float *>(obs);  // the kernels only read it
+  char *ws = reinterpret_cast<char *>(workspace);
+  ga.day = reinterpret_cast<float2 *>(ws + L.day);
+  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
+  ga.total = reinterpret_cast<double *>(ws + L.total);
+  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
+  ga.tiles = L.tiles;
+  ga.n_chunks = L.n_chunks;
+  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
+  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
+  ga.capacity = L.capacity;
+  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
+  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
+  ga.partial = reinterpret_cast<double *>(ws + L.partial);
+  ga.grad = grad;
+  sa.sg.alert_mask = alert_mask; sa.sg.mask_words = mask_words; sa.sg.env_weight = env_weight;
+  sa.sg.advantage = advantage; sa.sg.old_log_prob = old_log_prob;
+  sa.sg.lo = 1.0 - clip; sa.sg.hi = 1.0 + clip; sa.sg.beta = entropy_coef;
+  sa.sg.log_prob = log_prob; sa.sg.surrogate = surrogate; sa.sg.clipped = clipped_days; sa.sg.approx_kl = approx_kl;
+  sa.sg.entropy = entropy; sa.sg.days = days;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  if (log_prob) HIP_TRY(hipMemsetAsync(log_prob, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  switch (policy->width * 4 + policy->n_layers) {
+    case 16 * 4 + 1: launch_sg<16, 1>(sa, g64, s); break;
+    case 16 * 4 + 2: launch_sg<16, 2>(sa, g64, s); break;
+    case 32 * 4 + 1: launch_sg<32, 1>(sa, g64, s); break;
+    case 32 * 4 + 2: launch_sg<32, 2>(sa, g64, s); break;
+    case 64 * 4 + 1: launch_sg<64, 1>(sa, g64, s); break;
+    default: launch_sg<64, 2>(sa, g64, s); break;
+  }
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
 }
 
 // the checks w2a_value_gradient_linear and _mlp share once the network's own have passed (same order in both)

@@ -1233,6 +1233,112 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 out["group_log_likelihood"] = _policy.group_mean(wll, pol.group, pol.n_groups)
         return out
 
+    # ------------------------------------------------------------------ PPO-clip: K epochs along a given schedule
+    def surrogate_gradient(self, policy: dict, alert_days, advantage, old_log_prob=None, clip: float = 0.2,
+                           entropy_coef: float = 0.0, env_weight=None, n_steps: int | None = None,
+                           log_prob: bool = False) -> dict:
+        """The gradient of the PPO-clip surrogate along a GIVEN alert schedule under a linear or MLP policy: what K
+        epochs on the same episodes need, with the clipped importance ratio formed inside the kernel and no observation
+        row recorded. Every env is forced along its own schedule exactly as in imitation_gradient() (alert_days holds
+        the actions ATTEMPTED; the same rows o_s, the same require_budget rule for the scored days). On every scored
+        call-day s of env e, with z_s the logit, a_s the schedule's bit and p_s = sigmoid(z_s):
+          lp_s   = log pi(a_s | z_s);   rho_s = exp(lp_s - old_log_prob[s, e])  (exactly 1 for old_log_prob=None)
+          live_s = not ((A_s > 0 and rho_s > 1 + clip) or (A_s < 0 and rho_s < 1 - clip)),   A_s = advantage[s, e]
+          L_e    = sum_s min(rho_s A_s, clamp(rho_s, 1 - clip, 1 + clip) A_s)
+          g_e    = w_e sum_s [live_s rho_s A_s (a_s - p_s) + entropy_coef dH_s/dz] dz_s/dtheta,  H_s the Bernoulli entropy
+        and per group the mean of g_e over its envs, so ``theta += lr * grad`` ascends
+        mean_e w_e (L_e + entropy_coef sum_s H_s).
+          policy        a kind="linear" or kind="mlp" dict, as imitation_gradient() takes it
+          alert_days    bool [N, T] by day of the episode (rollout(alert_mask=True)["alert_days"])
+          advantage     float [S >= n_steps, N], finite (ValueError), by call-day and ENV ID: value_gradient()'s
+                        "advantage", or any other (GAE, discounting and normalisation are the caller's)
+          old_log_prob  optional float [S >= n_steps, N], same layout, <= 0 (ValueError): the "log_prob" of an earlier
+                        call under the policy that collected the schedule
+          clip          >= 0, finite; entropy_coef finite (ValueError)
+          env_weight, n_steps  as imitation_gradient()
+          log_prob      True: also return lp_s -- how the first epoch obtains old_log_prob without a recorded rollout
+        Returns
+          "policy_gradient"  as imitation_gradient() (NaN for a group without envs)
+          "surrogate"        f32 [N]  L_e (unweighted)
+          "clipped_days"     i32 [N]  scored days with live_s = 0
+          "approx_kl"        f32 [N]  sum_s ((rho_s - 1) - log rho_s): SB3's estimator, summed and not averaged
+          "entropy"          f32 [N]  sum_s H_s
+          "days"             i32 [N]  scored days, as imitation_gradient()
+          "group_surrogate"  f32 [G]  mean over the group's envs of env_weight * surrogate
+          "log_prob"         (log_prob=True) f32 [S, N] by call-day and env id: lp_s on scored days, 0 elsewhere
+        With old_log_prob=None and entropy_coef=0 this is imitation_gradient(day_weight=advantage). No side effects: the
+        state, the tables, the observation buffer and the RNG are only read. No floating-point atomics: two identical
+        calls give identical bits. Needs the observation buffer current (RuntimeError as imitation_gradient()) and
+        faithful observations. Value-loss clipping and minibatches inside a call are not offered.
+        w2a_surrogate_gradient_linear / _mlp (include/w2a.h)."""
+        kind = policy.get("kind") if isinstance(policy, dict) else None
+        ct, n, dev = self.ct, self.num_envs, self.device
+        mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,
+                                                      who="surrogate_gradient()")
+        check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
+        pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        adv, old, clip, beta = _policy.check_surrogate_args(advantage, old_log_prob, clip, entropy_coef,
+                                                            min(steps, 2**31 - 1), n, dev)
+        if self._needs_reset:
+            raise RuntimeError("call reset() before surrogate_gradient()")
+        if not self._obs_current:
+            raise RuntimeError(f"surrogate_gradient(kind={kind!r}) reads the observation buffer, which does not hold the "
+                               "agents' current rows (write_obs=False, a built-in rollout or load_state_dict since the "
+                               "last step()/reset()): call step() or reset() first")
+        words = mask.shape[1]
+        out = {"surrogate": torch.empty(n, dtype=torch.float32, device=dev),
+               "clipped_days": torch.empty(n, dtype=torch.int32, device=dev),
+               "approx_kl": torch.empty(n, dtype=torch.float32, device=dev),
+               "entropy": torch.empty(n, dtype=torch.float32, device=dev),
+               "days": torch.empty(n, dtype=torch.int32, device=dev)}
+        if log_prob:
+            out["log_prob"] = torch.empty((steps, n), dtype=torch.float32, device=dev)  # zero-filled by the library
+        lpp = out["log_prob"].data_ptr() if log_prob else None
+        wp = None if w is None else w.data_ptr()
+        oldp, old_days = (None, 0) if old is None else (old.data_ptr(), int(min(old.shape[0], 2**31 - 1)))
+        front = (mask.data_ptr(), words, wp, adv.data_ptr(), int(min(adv.shape[0], 2**31 - 1)), oldp, old_days, clip, beta,
+                 steps, self._obs.data_ptr())
+        outs = (out["surrogate"].data_ptr(), out["clipped_days"].data_ptr(), out["approx_kl"].data_ptr(),
+                out["entropy"].data_ptr(), out["days"].data_ptr(), lpp)
+        with torch.cuda.device(dev):
+            if kind == "linear":
+                lp = _ffi.LinearPolicy()
+                lp.weight, lp.bias = pol.weight_slots.data_ptr(), pol.bias.data_ptr()
+                lp.group = None if pol.group is None else pol.group.data_ptr()
+                lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
+                rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
+                _ffi.check(self._lib.w2a_surrogate_gradient_linear(
+                    self._h, C.byref(lp), *front, rows.data_ptr(), *outs, self._stream()),
+                    "w2a_surrogate_gradient_linear")
+                # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
+                g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
+                out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
+            else:
+                mp = _ffi.MlpPolicy()
+                mp.params = pol.params.data_ptr()
+                mp.group = None if pol.group is None else pol.group.data_ptr()
+                # always group-major (the partial blocks are sized for it), whatever "order" a rollout would use
+                gorder = None if pol.group is None else (pol.order if pol.group_major else _policy.group_order(pol.group))
+                mp.order = None if gorder is None else gorder.data_ptr()
+                mp.n_groups, mp.n_layers, mp.width = pol.n_groups, pol.n_layers, pol.width
+                mp.activation = _ffi.MLP_ACTIVATIONS[pol.activation]
+                mp.sample, mp.require_budget, mp.seed = 0, int(pol.require_budget), 0
+                blocks = torch.empty((pol.n_groups, _policy.mlp_stride(pol.width, pol.n_layers)), dtype=torch.float32,
+                                     device=dev)
+                ws = torch.empty(self._lib.w2a_surrogate_gradient_mlp_workspace_bytes(
+                    n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
+                _ffi.check(self._lib.w2a_surrogate_gradient_mlp(
+                    self._h, C.byref(mp), *front, blocks.data_ptr(), *outs, ws.data_ptr(), ws.numel(), self._stream()),
+                    "w2a_surrogate_gradient_mlp")
+                out["policy_gradient"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden,
+                                                                            pol.n_out)}
+            ws_ = out["surrogate"].double() if w is None else (w.double() * out["surrogate"].double())
+            if pol.group is None:  # one group: the fp64 mean, rounded once
+                out["group_surrogate"] = ws_.mean().to(torch.float32).reshape(1)
+            else:
+                out["group_surrogate"] = _policy.group_mean(ws_, pol.group, pol.n_groups)
+        return out
+
     # ------------------------------------------------------------------ critic: value regression along a schedule
     def value_gradient(self, value: dict, alert_days, env_weight=None, n_steps: int | None = None,
                        advantage: bool = False) -> dict:
@@ -1263,8 +1369,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         No side effects: the state, the tables, the schedule, the observation buffer and the RNG are only read. No
         floating-point atomics: two identical calls give identical bits. Needs the observation buffer current
         (RuntimeError as rollout(kind="linear")), reward_mode="sampled" and faithful semantics (ValueError for what
-        rollout(policy_gradient=...) refuses: rewards enter here). Discounting, GAE(lambda), bootstrapping past the call
-        and clipped ratios are not offered. w2a_value_gradient_linear / _mlp (include/w2a.h)."""
+        rollout(policy_gradient=...) refuses: rewards enter here). Discounting, GAE(lambda) and bootstrapping past the
+        call are not offered (clipped ratios: surrogate_gradient()). w2a_value_gradient_linear / _mlp (include/w2a.h)."""
         kind = value.get("kind") if isinstance(value, dict) else None
         ct, n, dev = self.ct, self.num_envs, self.device
         mask, w, steps = _policy.check_value_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.reward_mode,

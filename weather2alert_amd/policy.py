@@ -198,23 +198,45 @@ def check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs: int, T
     return pack_alert_days(ad.to(device), words), w, (int(n_steps) if n_steps is not None else T)
 
 
-def check_day_weight(day_weight, n_steps: int, num_envs: int, device):
+def check_day_weight(day_weight, n_steps: int, num_envs: int, device, who: str = "imitation_gradient()",
+                     name: str = "day_weight"):
     """``imitation_gradient(day_weight=...)``: None, or a float [S >= n_steps, num_envs] by call-day and env id (the
     layout of value_gradient()'s "advantage"), finite, returned as contiguous f32 on `device`. ValueError otherwise
-    (every entry is checked, those of days an env does not step included: "advantage" holds zeros there)."""
+    (every entry is checked, those of days an env does not step included: "advantage" holds zeros there). `who` and
+    `name` name the caller and the argument in the messages (surrogate_gradient() checks its two [S, N] arrays here)."""
     if day_weight is None:
         return None
     d = day_weight if torch.is_tensor(day_weight) else torch.as_tensor(np.asarray(day_weight))
     if not d.is_floating_point():
-        raise ValueError(f"imitation_gradient(): day_weight must be float, got {d.dtype}")
+        raise ValueError(f"{who}: {name} must be float, got {d.dtype}")
     if d.dim() != 2 or d.shape[1] != num_envs:
-        raise ValueError(f"imitation_gradient(): day_weight must be [S, {num_envs}] (call-day, env id), got {tuple(d.shape)}")
+        raise ValueError(f"{who}: {name} must be [S, {num_envs}] (call-day, env id), got {tuple(d.shape)}")
     if d.shape[0] < n_steps:
-        raise ValueError(f"imitation_gradient(): day_weight holds {d.shape[0]} call-days, the call runs {n_steps}")
+        raise ValueError(f"{who}: {name} holds {d.shape[0]} call-days, the call runs {n_steps}")
     d = d.detach().to(device=device, dtype=torch.float32).contiguous()
     if not bool(torch.isfinite(d).all()):  # one pass over the weights and a sync, as for env_weight
-        raise ValueError("imitation_gradient(): day_weight must be finite (as float32)")
+        raise ValueError(f"{who}: {name} must be finite (as float32)")
     return d
+
+
+def check_surrogate_args(advantage, old_log_prob, clip, entropy_coef, n_steps: int, num_envs: int, device):
+    """The arguments of ``surrogate_gradient()`` beyond those of imitation_gradient(): advantage (required) and
+    old_log_prob (optional), both through check_day_weight, a log-probability above zero, a clip that is negative or not
+    finite and an entropy_coef that is not finite: ValueError. Returns (advantage, old_log_prob or None, clip,
+    entropy_coef), the arrays contiguous f32 [S, num_envs] on `device`."""
+    who = "surrogate_gradient()"
+    if advantage is None:
+        raise ValueError(f"{who}: advantage is required")
+    adv = check_day_weight(advantage, n_steps, num_envs, device, who=who, name="advantage")
+    old = check_day_weight(old_log_prob, n_steps, num_envs, device, who=who, name="old_log_prob")
+    if old is not None and bool((old > 0).any()):
+        raise ValueError(f"{who}: old_log_prob holds a log-probability above zero")
+    for nm, v in (("clip", clip), ("entropy_coef", entropy_coef)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{who}: {nm} must be a finite number, got {v!r}")
+    if clip < 0:
+        raise ValueError(f"{who}: clip must not be negative, got {clip!r}")
+    return adv, old, float(clip), float(entropy_coef)
 
 
 def check_value_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: int, device, reward_mode="sampled",
