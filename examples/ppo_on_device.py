@@ -5,7 +5,9 @@ record=True: no observation row leaves the device code. Per iteration, on a fres
   1. rollout(actor | sample, require_budget, alert_mask=True) samples the actor and returns the schedule it issued;
   2. on a twin env reset to the same episodes (the gradient calls read its state and change nothing, so every call and
      every epoch runs on the same episodes): value_gradient(critic, alert_days, advantage=True) fits a [64, 64] tanh
-     critic to the reward-to-go along that schedule and returns the advantages Q_s - V_s;
+     critic to the reward-to-go along that schedule and returns the advantages Q_s - V_s (--gamma / --gae-lambda:
+     GAE(lambda) advantages and lambda-returns instead; --fixed-targets: the later critic epochs regress on the first
+     epoch's lambda-returns through target=, as PPO's critic epochs do);
   3. surrogate_gradient(actor, alert_days, advantage, log_prob=True) once: epoch 0's gradient (rho = 1) and the
      log-probabilities of the collecting policy;
   4. K more epochs of surrogate_gradient(actor, alert_days, advantage, old_log_prob=lp0): the clipped importance ratio
@@ -14,7 +16,7 @@ record=True: no observation row leaves the device code. Per iteration, on a fres
 Prints, per iteration, the surrogate per scored day, approx_kl per scored day and the clipped share of the last epoch,
 and the mean return next to the built-in `never` and `threshold` policies.
 
-    python examples/ppo_on_device.py [--iters 12] [--envs 65536] [--epochs 4] [--clip 0.2]      # needs one ROCm GPU
+    python examples/ppo_on_device.py [--iters 12] [--envs 65536] [--epochs 4] [--clip 0.2] [--gamma 0.99 --gae-lambda 0.95 --fixed-targets]      # needs one ROCm GPU
 """
 import argparse
 import os
@@ -34,6 +36,10 @@ ap.add_argument("--epochs", type=int, default=4, help="PPO epochs after epoch 0,
 ap.add_argument("--clip", type=float, default=0.2)
 ap.add_argument("--entropy-coef", type=float, default=0.0)
 ap.add_argument("--lr", type=float, default=3e-3)
+ap.add_argument("--gamma", type=float, default=1.0, help="discount of the advantages (1: the Monte-Carlo residual)")
+ap.add_argument("--gae-lambda", type=float, default=1.0, help="GAE(lambda) of the advantages")
+ap.add_argument("--fixed-targets", action="store_true",
+                help="critic epochs after the first regress on the first epoch's lambda-returns (target=), as PPO does")
 args = ap.parse_args()
 
 data = synth.make_synth("linear", n_fips=64, years=[2006, 2007, 2008], n_samples=20, seed=0, extra_confounder_fips=6)
@@ -90,9 +96,13 @@ for it in range(args.iters):
     ro = env.rollout(exported(actor, sample=True, seed=it, require_budget=True), alert_mask=True)
     sched = ro["alert_days"]
     for ep in range(args.epochs):  # the same episodes every epoch: no reset in between
-        vg = twin.value_gradient(exported(critic), sched, advantage=(ep == 0))
+        if ep > 0 and args.fixed_targets:  # targets fixed at collection time: returns = advantage + old values
+            vg = twin.value_gradient(exported(critic), sched, target=returns)
+        else:
+            vg = twin.value_gradient(exported(critic), sched, advantage=(ep == 0), gamma=args.gamma,
+                                     gae_lambda=args.gae_lambda, value_target=(ep == 0 and args.fixed_targets))
         if ep == 0:  # the advantages the actor is updated with come from the critic BEFORE this iteration's fit
-            adv, days = vg["advantage"], vg["days"]
+            adv, days, returns = vg["advantage"], vg["days"], vg.get("value_target")
         apply(critic, opt_c, vg["value_gradient"])
     valid = torch.arange(adv.shape[0], device=adv.device)[:, None] < days[None, :]
     a = adv[valid]

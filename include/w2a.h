@@ -713,6 +713,7 @@ int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
  * The estimator, for env e of group g over the call-days s = 0 .. S_e - 1 on which the env takes a step:
  *   r_s      the reward w2a_step pays for that day under the env's own posterior draw
  *   Q_s      = sum over s' >= s of r_s': undiscounted, truncated at the call's last day, nothing is bootstrapped
+ *              (discounting, GAE(lambda), a bootstrap and fixed targets: w2a_value_gradient_linear_gae below)
  *   V_s      = V(o_s)
  *   g_e      = w_e sum_s (Q_s - V_s) (o_s, 1), w_e = env_weight[e] (NULL: 1); envs finished on entry get zeros
  * grad (device f32 [n_obs + 1][num_envs], column-major, as w2a_policy_gradient_linear) receives g_e; the mean of g_e
@@ -760,6 +761,58 @@ int w2a_value_gradient_mlp(w2a_env *env, const w2a_mlp_policy *value, const uint
                            const float *env_weight, int32_t n_steps, const float *obs, float *grad, float *sq_error,
                            int32_t *days, float *ret, float *advantage, void *workspace, size_t workspace_bytes,
                            void *stream);
+/* w2a_value_gradient_linear with GAE(lambda), discounting, a bootstrap past the call, and targets fixed by an earlier
+ * call. The env is forced along its schedule exactly as in w2a_value_gradient_linear (the same bitmap, the same
+ * attempted-versus-issued rule, the same rows o_s, the same reward statements). The estimator, for env e over the
+ * call-days s = 0 .. S_e - 1 on which it takes a step:
+ *   V_s      = V(o_s)
+ *   Vn_s     the value of the row after day s: V(o_{s+1}) when the env holds a row after day s inside the call; 0 when
+ *            day s is the episode's last day; on the call's last day (s + 1 == n_steps) with the episode not finished,
+ *            V(o_{s+1}) when bootstrap = 1 and 0 when bootstrap = 0 (w2a_value_gradient_linear's convention)
+ *   delta_s  = r_s + gamma Vn_s - V_s
+ *   A_s      = delta_s + gamma lambda A_{s+1},  A_{S_e} = 0
+ *   R_s      = A_s + V_s  (the lambda-return)
+ *   c_s      = A_s (the semi-gradient: the target R_s is held fixed);  with target given, c_s = target[s][e] - V_s
+ *   g_e      = w_e sum_s c_s (o_s, 1)
+ * gamma = lambda = 1 with bootstrap = 0 is the estimator of w2a_value_gradient_linear.
+ *   sq_error      sum_s c_s^2
+ *   ret           the UNDISCOUNTED sum_s r_s (zeros when target is given: no reward is formed then)
+ *   advantage     nullable; A_s at [call-day][env id], 0 elsewhere (zero-filled on `stream` first)
+ *   value_target  nullable; R_s in the same layout (zero-filled on `stream` first)
+ *   target        nullable; device f32 [target_days >= n_steps][num_envs], the layout of value_target; entries of days
+ *                 an env does not step are not read. With target given no reward enters.
+ *   workspace     w2a_value_gradient_linear_gae_workspace_bytes(num_envs, n_steps) bytes, 256-B aligned: 17 B per env-day
+ * Numerics contract: r_s and V_s as w2a_value_gradient_linear; delta_s is formed and kept in fp64; the recursion, c_s,
+ * the products with w_e and o_s and the sums over s are fp64; g_e, sq_error, ret, advantage and value_target are rounded
+ * to f32 once. An env's outputs do not depend on the other envs, the group layout or the visiting order (bit for bit).
+ * No atomics: two identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_value_gradient_linear refuses (same order), and, after its NULL-output check: gamma or lambda
+ * outside [0, 1] (NaN included), bootstrap other than 0 or 1, target_days < n_steps, and target combined with advantage,
+ * value_target, a gamma or lambda other than 1, or bootstrap. W2A_ERR_STATE while `stream` is recording a hipGraph. */
+size_t w2a_value_gradient_linear_gae_workspace_bytes(int64_t num_envs, int32_t n_steps);
+int w2a_value_gradient_linear_gae(w2a_env *env, const w2a_linear_policy *value, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                                  float *grad, float *sq_error, int32_t *days, float *ret, float *advantage,
+                                  double gamma, double lambda, int32_t bootstrap, float *value_target,
+                                  const float *target, int32_t target_days, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+/* The same estimator for an MLP, reduced per group as w2a_value_gradient_mlp: (o_s, 1) becomes dV_s/dtheta. The
+ * workspace is that of w2a_value_gradient_mlp (w2a_value_gradient_mlp_gae_workspace_bytes(...) returns the same size).
+ * Numerics contract: V_s and Vn_s are the f32 logits; delta_s is formed in fp64 from them and the f32 reward and rounded
+ * to f32 once (the scratch holds (f32(delta_s), V_s)); the recursion runs in fp64 over the stored delta_s, backwards from
+ * the env's last day, so A_s differs from the recursion on unrounded residuals by at most
+ * 2^-24 sum_{s' >= s} (gamma lambda)^(s' - s) |delta_s'|. w_e c_s is formed in fp64 and rounded to f32 once; it replaces
+ * the day's record (day = (f32(w_e c_s), 0), total = 1), and from there on the second pass, the fp64 sums over tiles and
+ * the reduction are the kernels of w2a_policy_gradient_mlp, run unchanged. sq_error, advantage and value_target come from
+ * the same fp64 values, each rounded to f32 once. No atomics: two identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_value_gradient_mlp refuses (same order) and for the arguments listed above. */
+size_t w2a_value_gradient_mlp_gae_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                  int32_t n_layers);
+int w2a_value_gradient_mlp_gae(w2a_env *env, const w2a_mlp_policy *value, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                               float *grad, float *sq_error, int32_t *days, float *ret, float *advantage, double gamma,
+                               double lambda, int32_t bootstrap, float *value_target, const float *target,
+                               int32_t target_days, void *workspace, size_t workspace_bytes, void *stream);
 /* Optional, speed only: let w2a_rollout visit the envs in the order of their feature rows (envs that share a
  * (county, year) sit in the same wave and read the same table lines every day). Results are those of any other
  * order -- per-env outputs, RNG streams and state stay indexed by env id. Call after a reset (the order of an

@@ -31,6 +31,8 @@ SYMBOLS = [
     "w2a_imitation_gradient_linear_weighted", "w2a_imitation_gradient_mlp_weighted",
     "w2a_value_gradient_linear_workspace_bytes", "w2a_value_gradient_linear",
     "w2a_value_gradient_mlp_workspace_bytes", "w2a_value_gradient_mlp",
+    "w2a_value_gradient_linear_gae_workspace_bytes", "w2a_value_gradient_linear_gae",
+    "w2a_value_gradient_mlp_gae_workspace_bytes", "w2a_value_gradient_mlp_gae",
     "w2a_surrogate_gradient_linear", "w2a_surrogate_gradient_mlp_workspace_bytes", "w2a_surrogate_gradient_mlp",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
@@ -216,6 +218,15 @@ def load(build_if_missing: bool = True):
     lib.w2a_value_gradient_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
     lib.w2a_value_gradient_mlp.restype = C.c_int
     lib.w2a_value_gradient_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    gae = [C.c_double, C.c_double, i32, vp, vp, i32]  # gamma, lambda, bootstrap, value_target, target, target_days
+    lib.w2a_value_gradient_linear_gae_workspace_bytes.restype = C.c_size_t
+    lib.w2a_value_gradient_linear_gae_workspace_bytes.argtypes = [i64, i32]
+    lib.w2a_value_gradient_linear_gae.restype = C.c_int
+    lib.w2a_value_gradient_linear_gae.argtypes = [vp, C.POINTER(LinearPolicy), vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, *gae, vp, C.c_size_t, vp]
+    lib.w2a_value_gradient_mlp_gae_workspace_bytes.restype = C.c_size_t
+    lib.w2a_value_gradient_mlp_gae_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.w2a_value_gradient_mlp_gae.restype = C.c_int
+    lib.w2a_value_gradient_mlp_gae.argtypes = [vp, C.POINTER(MlpPolicy), vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, *gae, vp, C.c_size_t, vp]
     lib.w2a_surrogate_gradient_linear.restype = C.c_int
     lib.w2a_surrogate_gradient_linear.argtypes = [vp, C.POINTER(LinearPolicy), vp, i32, vp, vp, i32, vp, i32, C.c_double,
                                                   C.c_double, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]

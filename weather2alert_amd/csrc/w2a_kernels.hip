@@ -54,6 +54,7 @@
 #include "w2a_imitation.hip.h"
 #include "w2a_surrogate.hip.h"
 #include "w2a_value.hip.h"
+#include "w2a_gae.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1865,6 +1866,213 @@ int w2a_value_gradient_mlp(w2a_env *env, const w2a_mlp_policy *value, const uint
     case 32 * 4 + 2: launch_vg<32, 2>(va, g64, s); break;
     case 64 * 4 + 1: launch_vg<64, 1>(va, g64, s); break;
     default: launch_vg<64, 2>(va, g64, s); break;
+  }
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// what w2a_value_gradient_linear_gae and _mlp_gae check beyond check_value (same order in both)
+static int check_gae(const char *fn, double gamma, double lambda, int32_t bootstrap, const float *advantage,
+                     const float *value_target, const float *target, int32_t target_days, int32_t n_steps) {
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(W2A_ERR_ARG, "%s: gamma must lie in [0, 1]", fn);
+  if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(W2A_ERR_ARG, "%s: lambda must lie in [0, 1]", fn);
+  if (bootstrap != 0 && bootstrap != 1) return fail(W2A_ERR_ARG, "%s: bootstrap must be 0 or 1", fn);
+  if (target) {
+    if (target_days < n_steps) return fail(W2A_ERR_ARG, "%s: target holds fewer call-days than n_steps", fn);
+    if (advantage || value_target)
+      return fail(W2A_ERR_ARG, "%s: advantage and value_target are not formed when target is given", fn);
+    if (gamma != 1.0 || lambda != 1.0 || bootstrap)
+      return fail(W2A_ERR_ARG, "%s: gamma, lambda and bootstrap have no meaning when target is given", fn);
+  }
+  return W2A_OK;
+}
+
+// scratch of w2a_value_gradient_linear_gae: delta_s / c_s and V_s (fp64) and the alert issued, per (call-day, env) -- 17 B
+size_t w2a_value_gradient_linear_gae_workspace_bytes(int64_t num_envs, int32_t n_steps) {
+  if (num_envs <= 0 || n_steps <= 0) return 0;
+  const size_t days = (size_t)num_envs * (size_t)n_steps;
+  return 2 * align256(sizeof(double) * days) + align256(days);
+}
+
+int w2a_value_gradient_linear_gae(w2a_env *env, const w2a_linear_policy *value, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                                  float *grad, float *sq_error, int32_t *days, float *ret, float *advantage,
+                                  double gamma, double lambda, int32_t bootstrap, float *value_target,
+                                  const float *target, int32_t target_days, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+  const char *fn = "w2a_value_gradient_linear_gae";
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_value_gradient_linear's checks
+  if (!value) return fail(W2A_ERR_ARG, "%s: NULL value", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!value->weight || !value->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
+  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
+  if ((uintptr_t)value->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
+  int rc = check_value(fn, alert_mask, obs, grad, sq_error, days, ret);
+  if (rc != W2A_OK) return rc;
+  rc = check_gae(fn, gamma, lambda, bootstrap, advantage, value_target, target, target_days, n_steps);
+  if (rc != W2A_OK) return rc;
+  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if ((int64_t)mask_words * 32 < env->tb.T) return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the observation and "
+                             "the reward are)", fn);
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  if (workspace_bytes < w2a_value_gradient_linear_gae_workspace_bytes(env->n, n_steps))
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_value_gradient_linear_gae_workspace_bytes", fn);
+  REFUSE_WHILE_CAPTURING("w2a_value_gradient_linear_gae", stream);
+  GaeLinearArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  VgLinearArgs &va = xa.v;
+  LinearRolloutArgs &la = va.l;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
+    obs_mask |= 1u << sl;
+    la.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = la.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.n_steps = n_steps;
+  a.order = env->order;
+  la.weight = reinterpret_cast<const float4 *>(value->weight);
+  la.bias = value->bias;
+  la.group = value->group;
+  la.n_groups = value->n_groups;
+  la.n_obs = env->tb.n_obs;
+  la.obs_mask = obs_mask;
+  la.obs = const_cast<float *>(obs);  // the kernel only reads it
+  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
+  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
+  const size_t col = align256(sizeof(double) * (size_t)env->n * (size_t)n_steps);
+  va.day_y = reinterpret_cast<double *>(workspace);
+  xa.day_v = reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + col);
+  va.day_alert = reinterpret_cast<uint8_t *>(workspace) + 2 * col;
+  va.grad = grad;
+  xa.g.gamma = gamma; xa.g.gl = gamma * lambda; xa.g.bootstrap = bootstrap;
+  xa.g.value_target = value_target; xa.g.target = target;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  const size_t rows = sizeof(float) * (size_t)env->n * (size_t)n_steps;
+  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, rows, s));
+  if (value_target) HIP_TRY(hipMemsetAsync(value_target, 0, rows, s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  if (target) hipLaunchKernelGGL(k_value_gradient_linear_gae<true>, dim3(g64), dim3(BLOCK), 0, s, xa);
+  else hipLaunchKernelGGL(k_value_gradient_linear_gae<false>, dim3(g64), dim3(BLOCK), 0, s, xa);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
+size_t w2a_value_gradient_mlp_gae_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                  int32_t n_layers) {
+  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
+}
+
+int w2a_value_gradient_mlp_gae(w2a_env *env, const w2a_mlp_policy *value, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
+                               float *grad, float *sq_error, int32_t *days, float *ret, float *advantage, double gamma,
+                               double lambda, int32_t bootstrap, float *value_target, const float *target,
+                               int32_t target_days, void *workspace, size_t workspace_bytes, void *stream) {
+  const char *fn = "w2a_value_gradient_mlp_gae";
+  // what can be checked without the handle first (so that it is checked on any machine): w2a_value_gradient_mlp's checks
+  if (!value) return fail(W2A_ERR_ARG, "%s: NULL value", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!value->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
+  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
+  if (value->n_layers != 1 && value->n_layers != 2) return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
+  if (value->width != 16 && value->width != 32 && value->width != 64)
+    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
+  if (value->activation != W2A_MLP_TANH && value->activation != W2A_MLP_RELU)
+    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
+  if ((uintptr_t)value->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
+  int rc = check_value(fn, alert_mask, obs, grad, sq_error, days, ret);
+  if (rc != W2A_OK) return rc;
+  rc = check_gae(fn, gamma, lambda, bootstrap, advantage, value_target, target, target_days, n_steps);
+  if (rc != W2A_OK) return rc;
+  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if ((int64_t)mask_words * 32 < env->tb.T) return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the observation and "
+                             "the reward are)", fn);
+  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  const int64_t stride = W2A_MLP_STRIDE((int64_t)value->width, value->n_layers);
+  if ((int64_t)value->n_groups * stride >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
+  const PgmLayout L = pgm_layout(env->n, n_steps, value->n_groups, value->width, value->n_layers);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_value_gradient_mlp_gae_workspace_bytes", fn);
+  REFUSE_WHILE_CAPTURING("w2a_value_gradient_mlp_gae", stream);
+  GaeMlpArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  VgMlpArgs &va = xa.v;
+  MlpGradArgs &ga = va.g;
+  MlpRolloutArgs &ma = ga.m;
+  uint32_t obs_mask = 0;
+  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
+  for (int j = 0; j < env->tb.n_obs; ++j) {
+    const int sl = env->obs_slot_host[j];
+    if (sl < 0 || sl >= RO64_SLOTS)
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
+    obs_mask |= 1u << sl;
+    ma.slot_obs[sl] = (int8_t)j;
+  }
+  RolloutArgs &a = ma.r;
+  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
+  a.n_steps = n_steps;
+  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the network's (group-major) or identity
+  a.order = reinterpret_cast<const uint32_t *>(value->order);
+  ma.params = value->params;
+  ma.group = value->group;
+  ma.n_groups = value->n_groups;
+  ma.stride = (int32_t)stride;
+  ma.activation = value->activation;
+  ma.n_obs = env->tb.n_obs;
+  ma.obs_mask = obs_mask;
+  ma.obs = const_cast<float *>(obs);  // the kernels only read it
+  char *ws = reinterpret_cast<char *>(workspace);
+  ga.day = reinterpret_cast<float2 *>(ws + L.day);
+  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
+  ga.total = reinterpret_cast<double *>(ws + L.total);
+  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
+  ga.tiles = L.tiles;
+  ga.n_chunks = L.n_chunks;
+  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
+  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
+  ga.capacity = L.capacity;
+  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
+  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
+  ga.partial = reinterpret_cast<double *>(ws + L.partial);
+  ga.grad = grad;
+  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
+  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
+  xa.g.gamma = gamma; xa.g.gl = gamma * lambda; xa.g.bootstrap = bootstrap;
+  xa.g.value_target = value_target; xa.g.target = target;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; changes nothing else
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  const size_t rows = sizeof(float) * (size_t)env->n * (size_t)n_steps;
+  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, rows, s));
+  if (value_target) HIP_TRY(hipMemsetAsync(value_target, 0, rows, s));
+  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
+  switch (value->width * 4 + value->n_layers) {
+    case 16 * 4 + 1: launch_gae<16, 1>(xa, g64, s); break;
+    case 16 * 4 + 2: launch_gae<16, 2>(xa, g64, s); break;
+    case 32 * 4 + 1: launch_gae<32, 1>(xa, g64, s); break;
+    case 32 * 4 + 2: launch_gae<32, 2>(xa, g64, s); break;
+    case 64 * 4 + 1: launch_gae<64, 1>(xa, g64, s); break;
+    default: launch_gae<64, 2>(xa, g64, s); break;
   }
   HIP_TRY(hipGetLastError());
   end_call(env, s);

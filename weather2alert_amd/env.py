@@ -1341,7 +1341,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
 
     # ------------------------------------------------------------------ critic: value regression along a schedule
     def value_gradient(self, value: dict, alert_days, env_weight=None, n_steps: int | None = None,
-                       advantage: bool = False) -> dict:
+                       advantage: bool = False, gamma: float = 1.0, gae_lambda: float = 1.0, bootstrap: bool = False,
+                       value_target: bool = False, target=None) -> dict:
         """The gradient of a least-squares fit of a learned state-value function to the reward-to-go along a GIVEN
         alert schedule, and the advantages it leaves -- the critic of an on-device actor-critic loop, with no
         observation row recorded. `value` is a kind="linear" or kind="mlp" dict as rollout() takes it (groups, padding,
@@ -1369,14 +1370,36 @@ class HeatAlertVecEnv(_VectorEnvBase):
         No side effects: the state, the tables, the schedule, the observation buffer and the RNG are only read. No
         floating-point atomics: two identical calls give identical bits. Needs the observation buffer current
         (RuntimeError as rollout(kind="linear")), reward_mode="sampled" and faithful semantics (ValueError for what
-        rollout(policy_gradient=...) refuses: rewards enter here). Discounting, GAE(lambda) and bootstrapping past the
-        call are not offered (clipped ratios: surrogate_gradient()). w2a_value_gradient_linear / _mlp (include/w2a.h)."""
+        rollout(policy_gradient=...) refuses: rewards enter here). w2a_value_gradient_linear / _mlp (include/w2a.h).
+
+        GAE(lambda), discounting, a bootstrap past the call and fixed targets. With every argument below at its
+        default the call is the one above, bit for bit. Otherwise, with Vn_s the value of the row after day s --
+        z(o_{s+1}) while the env holds one inside the call, 0 on the episode's last day, and on the call's last day
+        (s + 1 == n_steps) of an unfinished episode z(o_{s+1}) if `bootstrap` else 0:
+          delta_s = r_s + gamma Vn_s - V_s;   A_s = delta_s + gamma gae_lambda A_{s+1}, A_{S_e} = 0;   R_s = A_s + V_s
+          g_e     = w_e sum_s c_s dV_s/dtheta,  c_s = A_s (the semi-gradient: the target R_s is held fixed, as SB3 does)
+          gamma, gae_lambda  finite, in [0, 1] (ValueError); 1, 1 with bootstrap=False is the estimator above, computed
+                             by the GAE kernels whenever any of these arguments is not at its default
+          bootstrap          plain bool: what makes n_steps < T usable for training on truncated chunks
+          value_target       plain bool; True adds "value_target" f32 [S, N]: R_s in the layout of "advantage"
+          target             float [S >= n_steps, N] by call-day and ENV ID, finite (checked as surrogate_gradient()'s
+                             advantage): c_s = target[s, e] - V_s, PPO's critic epochs on targets fixed at collection
+                             time (the "value_target" of the first call). No reward is needed then, so the call also
+                             works with reward_mode="posterior_mean", and "return" is left out. Combined with
+                             advantage=True, value_target=True, bootstrap=True or a gamma / gae_lambda other than 1:
+                             ValueError.
+        "sq_error" is sum_s c_s^2, "advantage" holds A_s, "return" stays the UNDISCOUNTED sum_s r_s, "days" and
+        "group_loss" as above. Advantage normalisation and a clipped value loss stay with the caller (clipped ratios:
+        surrogate_gradient()). w2a_value_gradient_linear_gae / _mlp_gae (include/w2a.h)."""
         kind = value.get("kind") if isinstance(value, dict) else None
         ct, n, dev = self.ct, self.num_envs, self.device
-        mask, w, steps = _policy.check_value_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.reward_mode,
-                                                  self.fixes)
+        # with targets given no reward enters: the reward mode does not matter then (as for imitation_gradient())
+        mask, w, steps = _policy.check_value_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev,
+                                                  "sampled" if target is not None else self.reward_mode, self.fixes)
         check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
         pol = check(value, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        gamma, lam, tg, gae = _policy.check_gae_args(gamma, gae_lambda, bootstrap, value_target, advantage, target,
+                                                     min(steps, 2**31 - 1), n, dev)
         if self._needs_reset:
             raise RuntimeError("call reset() before value_gradient()")
         if not self._obs_current:
@@ -1389,8 +1412,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
                "return": torch.empty(n, dtype=torch.float32, device=dev)}
         if advantage:
             out["advantage"] = torch.empty((steps, n), dtype=torch.float32, device=dev)  # zero-filled by the library
+        if value_target:
+            out["value_target"] = torch.empty((steps, n), dtype=torch.float32, device=dev)  # zero-filled by the library
         ap = out["advantage"].data_ptr() if advantage else None
         wp = None if w is None else w.data_ptr()
+        # what the *_gae entry points take after `advantage`
+        tail = (gamma, lam, int(bootstrap), out["value_target"].data_ptr() if value_target else None,
+                None if tg is None else tg.data_ptr(), 0 if tg is None else int(min(tg.shape[0], 2**31 - 1)))
         with torch.cuda.device(dev):
             if kind == "linear":
                 lp = _ffi.LinearPolicy()
@@ -1398,12 +1426,20 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 lp.group = None if pol.group is None else pol.group.data_ptr()
                 lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, 0, 0
                 rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
-                ws = torch.empty(self._lib.w2a_value_gradient_linear_workspace_bytes(n, steps), dtype=torch.uint8,
-                                 device=dev)
-                _ffi.check(self._lib.w2a_value_gradient_linear(
-                    self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
-                    out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, ws.data_ptr(),
-                    ws.numel(), self._stream()), "w2a_value_gradient_linear")
+                if gae:
+                    ws = torch.empty(self._lib.w2a_value_gradient_linear_gae_workspace_bytes(n, steps),
+                                     dtype=torch.uint8, device=dev)
+                    _ffi.check(self._lib.w2a_value_gradient_linear_gae(
+                        self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
+                        out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, *tail,
+                        ws.data_ptr(), ws.numel(), self._stream()), "w2a_value_gradient_linear_gae")
+                else:
+                    ws = torch.empty(self._lib.w2a_value_gradient_linear_workspace_bytes(n, steps), dtype=torch.uint8,
+                                     device=dev)
+                    _ffi.check(self._lib.w2a_value_gradient_linear(
+                        self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
+                        out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, ws.data_ptr(),
+                        ws.numel(), self._stream()), "w2a_value_gradient_linear")
                 # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
                 g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
                 out["value_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
@@ -1420,11 +1456,17 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 blocks = torch.empty((pol.n_groups, _policy.mlp_stride(pol.width, pol.n_layers)), dtype=torch.float32,
                                      device=dev)
                 ws = torch.empty(self._lib.w2a_value_gradient_mlp_workspace_bytes(
-                    n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
-                _ffi.check(self._lib.w2a_value_gradient_mlp(
-                    self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
-                    out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, ws.data_ptr(),
-                    ws.numel(), self._stream()), "w2a_value_gradient_mlp")
+                    n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)  # both routes
+                if gae:
+                    _ffi.check(self._lib.w2a_value_gradient_mlp_gae(
+                        self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
+                        out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, *tail,
+                        ws.data_ptr(), ws.numel(), self._stream()), "w2a_value_gradient_mlp_gae")
+                else:
+                    _ffi.check(self._lib.w2a_value_gradient_mlp(
+                        self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
+                        out["sq_error"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), ap, ws.data_ptr(),
+                        ws.numel(), self._stream()), "w2a_value_gradient_mlp")
                 out["value_gradient"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden,
                                                                            pol.n_out)}
             half = 0.5 * (out["sq_error"].double() if w is None else (w.double() * out["sq_error"].double()))
@@ -1432,6 +1474,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 out["group_loss"] = half.mean().to(torch.float32).reshape(1)
             else:
                 out["group_loss"] = _policy.group_mean(half, pol.group, pol.n_groups)
+        if tg is not None:
+            del out["return"]  # no reward was formed
         return out
 
     # ------------------------------------------------------------------ hindsight optimum

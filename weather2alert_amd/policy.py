@@ -249,6 +249,32 @@ def check_value_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: in
     return out
 
 
+def check_gae_args(gamma, gae_lambda, bootstrap, value_target, advantage, target, n_steps: int, num_envs: int, device):
+    """The arguments of ``value_gradient()`` beyond those of check_value_args: gamma and gae_lambda finite numbers in
+    [0, 1], bootstrap and value_target plain bools, target None or an [S >= n_steps, num_envs] float array
+    (through check_day_weight) that is combined with none of advantage=True, value_target=True, bootstrap=True or a
+    gamma / gae_lambda other than 1: ValueError otherwise. Returns (gamma, gae_lambda, target or None, new) with `new`
+    true when any of them leaves its default (the call then takes the *_gae entry points)."""
+    who = "value_gradient()"
+    for nm, v in (("gamma", gamma), ("gae_lambda", gae_lambda)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{who}: {nm} must be a finite number in [0, 1], got {v!r}")
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{who}: {nm} must lie in [0, 1], got {v!r}")
+    for nm, v in (("bootstrap", bootstrap), ("value_target", value_target)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{who}: {nm} must be a bool, got {v!r}")
+    tg = check_day_weight(target, n_steps, num_envs, device, who=who, name="target")
+    gamma, gae_lambda = float(gamma), float(gae_lambda)
+    if tg is not None:
+        if advantage or value_target:
+            raise ValueError(f"{who}: advantage and value_target are not formed when target is given")
+        if gamma != 1.0 or gae_lambda != 1.0 or bootstrap:
+            raise ValueError(f"{who}: gamma, gae_lambda and bootstrap have no meaning when target is given")
+    new = tg is not None or gamma != 1.0 or gae_lambda != 1.0 or bootstrap or value_target
+    return gamma, gae_lambda, tg, new
+
+
 def group_mean(values: torch.Tensor, group: torch.Tensor | None, n_groups: int) -> torch.Tensor:
     """f32 [n_groups] (values [N]) or [n_groups, K] (values [N, K], e.g. returns under K posterior draws): the mean of
     `values` over each group's envs, per column (NaN for a group without envs), on the device of `values`: the groups'
