@@ -16,7 +16,11 @@ record=True: no observation row leaves the device code. Per iteration, on a fres
 Prints, per iteration, the surrogate per scored day, approx_kl per scored day and the clipped share of the last epoch,
 and the mean return next to the built-in `never` and `threshold` policies.
 
-    python examples/ppo_on_device.py [--iters 12] [--envs 65536] [--epochs 4] [--clip 0.2] [--gamma 0.99 --gae-lambda 0.95 --fixed-targets]      # needs one ROCm GPU
+--min-heat-qi TAU restricts the actor to hot days, the older reference env's HI_restriction: alert_gate() builds the mask
+once per batch of episodes (packed, so nothing is packed again per call) and the sampling rollout and every surrogate
+epoch take it as "allowed_days"; gated days are forced choices and carry no ratio.
+
+    python examples/ppo_on_device.py [--iters 12] [--envs 65536] [--epochs 4] [--clip 0.2] [--gamma 0.99 --gae-lambda 0.95 --fixed-targets] [--min-heat-qi 0.8]      # needs one ROCm GPU
 """
 import argparse
 import os
@@ -40,6 +44,8 @@ ap.add_argument("--gamma", type=float, default=1.0, help="discount of the advant
 ap.add_argument("--gae-lambda", type=float, default=1.0, help="GAE(lambda) of the advantages")
 ap.add_argument("--fixed-targets", action="store_true",
                 help="critic epochs after the first regress on the first epoch's lambda-returns (target=), as PPO does")
+ap.add_argument("--min-heat-qi", type=float, default=None,
+                help="alerts only on days whose observed heat_qi is >= this (alert_gate -> \"allowed_days\")")
 args = ap.parse_args()
 
 data = synth.make_synth("linear", n_fips=64, years=[2006, 2007, 2008], n_samples=20, seed=0, extra_confounder_fips=6)
@@ -93,7 +99,8 @@ print(f"threshold {thr:9.3f}   (heat_qi > 0.9 while budget is left)")
 for it in range(args.iters):
     env.reset(seed=it)
     twin.reset(seed=it)  # the same episodes, left at their first day
-    ro = env.rollout(exported(actor, sample=True, seed=it, require_budget=True), alert_mask=True)
+    gate = {} if args.min_heat_qi is None else {"allowed_days": env.alert_gate("heat_qi", args.min_heat_qi, packed=True)}
+    ro = env.rollout(exported(actor, sample=True, seed=it, require_budget=True, **gate), alert_mask=True)
     sched = ro["alert_days"]
     for ep in range(args.epochs):  # the same episodes every epoch: no reset in between
         if ep > 0 and args.fixed_targets:  # targets fixed at collection time: returns = advantage + old values
@@ -108,11 +115,11 @@ for it in range(args.iters):
     a = adv[valid]
     A = torch.where(valid, (adv - a.mean()) / (a.std() + 1e-8), torch.zeros_like(adv))
     kw = dict(clip=args.clip, entropy_coef=args.entropy_coef)
-    sg = twin.surrogate_gradient(exported(actor, require_budget=True), sched, A, log_prob=True, **kw)  # epoch 0: rho = 1
+    sg = twin.surrogate_gradient(exported(actor, require_budget=True, **gate), sched, A, log_prob=True, **kw)  # epoch 0: rho = 1
     lp0 = sg["log_prob"]
     apply(actor, opt_a, sg["policy_gradient"])
     for ep in range(args.epochs):
-        sg = twin.surrogate_gradient(exported(actor, require_budget=True), sched, A, old_log_prob=lp0, **kw)
+        sg = twin.surrogate_gradient(exported(actor, require_budget=True, **gate), sched, A, old_log_prob=lp0, **kw)
         apply(actor, opt_a, sg["policy_gradient"])
     scored = float(sg["days"].double().sum().clamp_min(1))
     print(f"iter {it:2d}   mean return {float(ro['return'].mean()):9.3f}   alerts/env "

@@ -888,6 +888,82 @@ int w2a_invalidate(w2a_env *env, void *stream);
 /* Synchronise `stream`, read and clear the device status word (host int out). */
 int w2a_read_status(w2a_env *env, int32_t *status_out, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------
+ * Alert gates: learned policies restricted to allowed days (the older reference env's restrict_alerts / HI_restriction).
+ *
+ * allowed_days is a per-env bitmap over the days of the episode in the layout of alert_mask: uint32 [num_envs]
+ * [allowed_words], bit (t & 31) of word t >> 5, allowed_words * 32 >= T. On a day whose bit is clear the attempted
+ * action is forced to 0 BEFORE the attempt is recorded and before the budget test: such a day never counts as an
+ * over-budget attempt, and it is a forced choice like a day on which require_budget forces the action -- it carries no
+ * score, no log-likelihood, no ratio, no entropy, and the `days` outputs do not count it. The Bernoulli uniform of a day
+ * is a function of (env, episode, day): a gated day moves no other day's draw. A NULL allowed_days is refused (the entry
+ * points without _gated take no gate); an all-ones bitmap gives the bits of the ungated call. The gate is an argument of
+ * the call and is not kept on the handle; w2a_step and the built-in policy kinds know nothing of it.
+ *
+ * w2a_alert_gate builds the bitmap the reference's restriction stands for: bit t of env e is set iff the value of
+ * observation column obs_col in the row the agent holds when it chooses day t's action is >= the threshold
+ * (thresholds[e] when thresholds is not NULL, else threshold; >= as in the reference, not the > of the threshold policy
+ * kind). That row is the one w2a_step would have returned: the table row of day max(t - 1, 0) under the faithful
+ * semantics (the lagging observation), the row of day t with W2A_FIX_OBS. It covers the days the env would still step
+ * from its current state (n_steps of them, or to its terminal day); days before, days after and finished envs are 0.
+ * obs_col must be table-sourced (slots 24..27, and the 'alerts_2wks' column under W2A_FIX_ALERTS_2WKS, hold the agent's
+ * own history: W2A_ERR_ARG). Reads the tables and the state, writes allowed_days only; asynchronous on `stream`.
+ *
+ * The *_gated entry points take the arguments of the entry point they are named after, then allowed_days and
+ * allowed_words. w2a_rollout_linear_gated takes w2a_rollout_linear_record's arguments with traj nullable (NULL: no
+ * trajectory; recorded `action` is 0 on a gated day, `logit` is still the policy's). w2a_imitation_gradient_linear_gated
+ * takes w2a_imitation_gradient_linear_weighted's with day_weight nullable: an alert the schedule asks for on a
+ * disallowed day is attempted as 0. w2a_hindsight_optimum_gated: the DP may alert only on allowed days, so the result is
+ * the best schedule under the restriction, its return the bits the env pays for that schedule. */
+int w2a_alert_gate(w2a_env *env, int32_t obs_col, float threshold, const float *thresholds, int32_t n_steps,
+                   uint32_t *allowed_days, int32_t allowed_words, void *stream);
+int w2a_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                             int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                             uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                             void *stream, const w2a_trajectory *traj, const uint32_t *allowed_days,
+                             int32_t allowed_words);
+int w2a_policy_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
+                                     const float *obs, float *grad, void *workspace, size_t workspace_bytes,
+                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words);
+int w2a_imitation_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                        int32_t mask_words, const float *env_weight, const float *day_weight,
+                                        int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                        float *loglik, int32_t *days, void *stream, const uint32_t *allowed_days,
+                                        int32_t allowed_words);
+int w2a_surrogate_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                        int32_t mask_words, const float *env_weight, const float *advantage,
+                                        int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                        double clip, double entropy_coef, int32_t n_steps, const float *obs,
+                                        float *grad, float *surrogate, int32_t *clipped_days, float *approx_kl,
+                                        float *entropy, int32_t *days, float *log_prob, void *stream,
+                                        const uint32_t *allowed_days, int32_t allowed_words);
+/* the MLP kind: w2a_rollout_mlp_record's arguments with traj nullable, w2a_policy_gradient_mlp's,
+ * w2a_imitation_gradient_mlp_weighted's with day_weight nullable, w2a_surrogate_gradient_mlp's -- then the bitmap. The
+ * workspaces are those of the ungated calls. */
+int w2a_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                          int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                          uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                          void *stream, const w2a_trajectory *traj, const uint32_t *allowed_days, int32_t allowed_words);
+int w2a_policy_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
+                                  const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
+                                  const uint32_t *allowed_days, int32_t allowed_words);
+int w2a_imitation_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                                     int32_t mask_words, const float *env_weight, const float *day_weight,
+                                     int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                     float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words);
+int w2a_surrogate_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                                     int32_t mask_words, const float *env_weight, const float *advantage,
+                                     int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                     double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                                     float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                                     int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes,
+                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words);
+int w2a_hindsight_optimum_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                                uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                                size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                                int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,10 @@ SYMBOLS = [
     "w2a_value_gradient_linear_gae_workspace_bytes", "w2a_value_gradient_linear_gae",
     "w2a_value_gradient_mlp_gae_workspace_bytes", "w2a_value_gradient_mlp_gae",
     "w2a_surrogate_gradient_linear", "w2a_surrogate_gradient_mlp_workspace_bytes", "w2a_surrogate_gradient_mlp",
+    "w2a_alert_gate", "w2a_rollout_linear_gated", "w2a_policy_gradient_linear_gated",
+    "w2a_imitation_gradient_linear_gated", "w2a_surrogate_gradient_linear_gated", "w2a_hindsight_optimum_gated",
+    "w2a_rollout_mlp_gated", "w2a_policy_gradient_mlp_gated", "w2a_imitation_gradient_mlp_gated",
+    "w2a_surrogate_gradient_mlp_gated",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
@@ -235,6 +239,28 @@ def load(build_if_missing: bool = True):
     lib.w2a_surrogate_gradient_mlp.restype = C.c_int
     lib.w2a_surrogate_gradient_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, i32, vp, vp, i32, vp, i32, C.c_double,
                                                C.c_double, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    # alert gates: the arguments of the entry point each is named after, then the allowed-days bitmap and its word count
+    gate = [vp, i32]
+    lib.w2a_alert_gate.restype = C.c_int
+    lib.w2a_alert_gate.argtypes = [vp, i32, C.c_float, vp, i32, vp, i32, vp]
+    lib.w2a_rollout_linear_gated.restype = C.c_int
+    lib.w2a_rollout_linear_gated.argtypes = lib.w2a_rollout_linear.argtypes + [C.POINTER(Trajectory)] + gate
+    lib.w2a_policy_gradient_linear_gated.restype = C.c_int
+    lib.w2a_policy_gradient_linear_gated.argtypes = lib.w2a_policy_gradient_linear.argtypes + gate
+    lib.w2a_imitation_gradient_linear_gated.restype = C.c_int
+    lib.w2a_imitation_gradient_linear_gated.argtypes = lib.w2a_imitation_gradient_linear_weighted.argtypes + gate
+    lib.w2a_surrogate_gradient_linear_gated.restype = C.c_int
+    lib.w2a_surrogate_gradient_linear_gated.argtypes = lib.w2a_surrogate_gradient_linear.argtypes + gate
+    lib.w2a_rollout_mlp_gated.restype = C.c_int
+    lib.w2a_rollout_mlp_gated.argtypes = lib.w2a_rollout_mlp.argtypes + [C.POINTER(Trajectory)] + gate
+    lib.w2a_policy_gradient_mlp_gated.restype = C.c_int
+    lib.w2a_policy_gradient_mlp_gated.argtypes = lib.w2a_policy_gradient_mlp.argtypes + gate
+    lib.w2a_imitation_gradient_mlp_gated.restype = C.c_int
+    lib.w2a_imitation_gradient_mlp_gated.argtypes = lib.w2a_imitation_gradient_mlp_weighted.argtypes + gate
+    lib.w2a_surrogate_gradient_mlp_gated.restype = C.c_int
+    lib.w2a_surrogate_gradient_mlp_gated.argtypes = lib.w2a_surrogate_gradient_mlp.argtypes + gate
+    lib.w2a_hindsight_optimum_gated.restype = C.c_int
+    lib.w2a_hindsight_optimum_gated.argtypes = lib.w2a_hindsight_optimum.argtypes + gate
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     if lib.w2a_abi_version() != ABI_VERSION:

@@ -55,6 +55,9 @@ struct HsArgs {
   uint32_t *hist;          // [HS_BINS] workspace: envs per U
   uint32_t *cursor;        // [HS_BINS] workspace: first position of every bin in `order`, advanced by k_hs_scatter
   uint32_t *order;         // [n] workspace: env ids by U
+  const uint32_t *gate;    // [n][gate_words] allowed days, the layout of `mask` (w2a_hindsight_optimum_gated; read by the
+                           // GATE = true instantiations only): the DP may alert only on a day whose bit is set
+  int32_t gate_words;
 };
 #define HS_NONE 0xFFFFFFFFu  // nothing to choose (finished, or t >= n_days): return 0
 #define HS_BAD 0xFFFFFFFEu   // a start outside the tables: return NaN
@@ -165,7 +168,9 @@ __device__ __forceinline__ uint32_t hs_row(uint32_t idx) {  // j of state idx: j
 
 // one env per 64-lane workgroup; envs list[0 .. gridDim.x) all have this U. GLOBAL: V and the decision words live in
 // `pool` (pool_stride bytes per workgroup) instead of LDS.
-template <bool GLOBAL>
+// GATE: the alert transition exists only on the days a.gate allows (the best schedule UNDER the restriction); the word
+// of a day is wave-uniform and loaded once per 32 days. GATE = false compiles from the statements it had before.
+template <bool GLOBAL, bool GATE>
 __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32_t *list, uint32_t U, char *pool,
                                                     size_t pool_stride) {
   extern __shared__ __attribute__((aligned(16))) char hs_lds[];
@@ -212,7 +217,9 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
 
   // ---- backward DP: V_{d+1} in vn, V_d into vc
   double *vn = V1, *vc = V0;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   for (int32_t d = (int32_t)H - 1; d >= 0; --d) {
+    const bool open = !GATE || gate_allows(a.gate, a.gate_words, e, h.t0 + (uint32_t)d, gate_word, gate_idx);
     const uint32_t J = min((uint32_t)d, U);
     const uint32_t nsd = hs_ns(J);
     const double2 p = pz[d];
@@ -226,7 +233,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
         const uint32_t j = hs_row(idx), k = idx - j * (j + 3u) / 2u;
         const float s = (float)(k == j + 1u ? h.s0 + j : k);
         const int32_t rem = h.budget - (int32_t)(h.used + j);
-        const bool allowed = (int32_t)j < rem0;
+        const bool allowed = (int32_t)j < rem0 && open;
         const float r0 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem, 0u);
         const double q0 = (double)r0 + vn[j * (j + 3u) / 2u];
         double best = q0;

@@ -71,6 +71,9 @@ __device__ __forceinline__ double im_log_pi(double z, uint32_t a) {
 }
 
 // Registers: the policy row (32 f32), xv[] and 31 fp64 accumulators; two waves per SIMD leave 256 VGPRs.
+// GATE (w2a_imitation_gradient_linear_gated): ia.l.gate restricts the attempts; an alert the schedule asks for on a
+// disallowed day is attempted as 0 and the day is not scored. GATE = false compiles from the statements it had before.
+template <bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArgs ia) {
   const LinearRolloutArgs &la = ia.l;
   const RolloutArgs &a = la.r;
@@ -103,6 +106,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
   }
   const double w_e = ia.im.env_weight ? (double)ia.im.env_weight[e] : 1.0;
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   double g[32];
 #pragma unroll
   for (int k = 0; k < 32; ++k) g[k] = 0.0;  // slot k's column; the bias rides in slot 31, as in the policy row
@@ -119,6 +123,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
       if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
     lab = im_label(ia.im, e, t, lab_word, lab_idx);
     scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
+    if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
     if (scores) {
       const float delta = (float)lab - sigmoid_f32((float)z);
       const double c = im_coef(ia.im, w_e, delta, e);
@@ -169,6 +174,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
       if (active && s + 1 < a.n_steps) {
         lab = im_label(ia.im, e, t, lab_word, lab_idx);
         scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
+        if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
         if (scores) {
           const float delta = (float)lab - sigmoid_f32((float)zp);
           const double c = im_coef(ia.im, w_e, delta, (size_t)(s + 1) * n + e);
@@ -193,7 +199,9 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
 }
 
 // ------------------------------------------------------------------------------------------------ MLP: pass 1
-template <int WIDTH, int LAYERS>
+// GATE (w2a_imitation_gradient_mlp_gated): as k_imitation_linear<GATE>; GATE = false compiles from the statements it
+// had before the gate existed
+template <int WIDTH, int LAYERS, bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
   const MlpGradArgs &ga = ia.g;
@@ -221,6 +229,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
   double ll = 0.0;
   int32_t scored = 0, n_valid = 0;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   bool active = D1_FIN(hot.y) == 0 && valid;
 #pragma unroll
   for (int k = 0; k < ROWF; ++k)
@@ -235,6 +244,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
     float delta = (float)act - p;
     bool scores = true;
     if (a.pol.require_budget && budget - (int32_t)used <= 0) { act = 0; delta = 0.0f; scores = false; }  // m_s = 0: forced
+    if (GATE && active && !gate_allows(ma.gate, ma.gate_words, e, t, gate_word, gate_idx)) { act = 0; delta = 0.0f; scores = false; }
     const uint32_t atb_s = ((int32_t)used == budget) ? 1u : 0u;
     const uint32_t actual = (act == 1 && atb_s) ? 0u : (uint32_t)act;
     const uint32_t used2 = used + actual;
@@ -292,7 +302,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
 template <int WIDTH, int LAYERS>
 static void launch_im(const ImMlpArgs &ia, unsigned grid1, hipStream_t s) {
   const MlpGradArgs &ga = ia.g;
-  hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS>), dim3(grid1), dim3(BLOCK), 0, s, ia);
+  if (ga.m.gate) hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, true>), dim3(grid1), dim3(BLOCK), 0, s, ia);
+  else hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, false>), dim3(grid1), dim3(BLOCK), 0, s, ia);
   hipLaunchKernelGGL(k_pgm_count, dim3(ga.n_chunks), dim3(64), 0, s, ga);
   hipLaunchKernelGGL(k_pgm_scan, dim3(1), dim3(1024), 0, s, ga);
   hipLaunchKernelGGL((k_pgm_pass2<WIDTH, LAYERS>), dim3(ga.n_chunks), dim3(64), 0, s, ga);

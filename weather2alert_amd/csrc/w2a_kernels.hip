@@ -56,6 +56,7 @@
 #include "w2a_value.hip.h"
 #include "w2a_gae.hip.h"
 #include "w2a_hindsight.hip.h"
+#include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"
 
 // ----------------------------------------------------------------------------------------
@@ -842,31 +843,48 @@ static int clear_trajectory_flags(const w2a_env *env, int32_t n_steps, const w2a
   return W2A_OK;
 }
 
-static int rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+// the allowed-days bitmap of the *_gated entry points: checked where the schedule's bitmap is
+static int check_gate(const char *fn, const w2a_env *env, const uint32_t *gate, int32_t gate_words) {
+  if (!gate) return fail(W2A_ERR_ARG, "%s: NULL allowed_days (the entry point without _gated takes no gate)", fn);
+  if ((int64_t)gate_words * 32 < env->tb.T) return fail(W2A_ERR_ARG, "%s: allowed_days needs ceil(T/32) words per env", fn);
+  return W2A_OK;
+}
+
+// gated: the call came through w2a_rollout_linear_gated (gate is then checked, and the GATE instantiations run)
+static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                           int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
                           uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
-                          void *stream, const w2a_trajectory *traj) {
+                          void *stream, const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
+                          int32_t gate_words = 0) {
   // what can be checked without the handle first (so that it is checked on any machine)
-  if (!policy) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL policy");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_linear: n_steps must be positive");
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL weight or bias");
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_linear: n_groups must be positive");
-  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "w2a_rollout_linear: sample must be 0 or 1");
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
+  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
   if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "w2a_rollout_linear: require_budget must be 0 or 1");
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "w2a_rollout_linear: weight must be 16-B aligned");
-  if (!obs) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL obs (the rows the agent holds are the first day's input)");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_rollout_linear: NULL handle");
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if ((alert_mask || attempt_mask) && mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_rollout_linear: alert_mask / attempt_mask need ceil(T/32) words per env");
+    return fail(W2A_ERR_ARG, "%s: alert_mask / attempt_mask need ceil(T/32) words per env", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_rollout_linear: not available with corrected-semantics flags (they change what the "
-                             "observation is)");
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the "
+                             "observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_rollout_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
-  REFUSE_WHILE_CAPTURING("w2a_rollout_linear", stream);
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  if (gated) {
+    const int rc = check_gate(fn, env, gate, gate_words);
+    if (rc != W2A_OK) return rc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   LinearRolloutArgs la;
   memset(&la, 0, sizeof(la));
+  la.gate = gated ? gate : nullptr;
+  la.gate_words = gated ? gate_words : 0;
   // every observation column must sit on a slot the day loop multiplies (0..RO64_SLOTS-1): then slot 31, which carries
   // the bias, is provably none of them
   uint32_t obs_mask = 0;
@@ -874,7 +892,7 @@ static int rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t
   for (int j = 0; j < env->tb.n_obs; ++j) {
     const int sl = env->obs_slot_host[j];
     if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_rollout_linear: an observation column sits on slot 30 or 31 of the feature row");
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
     obs_mask |= 1u << sl;
     la.slot_obs[sl] = (int8_t)j;
   }
@@ -909,7 +927,11 @@ static int rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t
     const int rc = clear_trajectory_flags(env, n_steps, traj, s);
     if (rc != W2A_OK) return rc;
   }
-#define W2A_LAUNCH_LINEAR(M, S, R) hipLaunchKernelGGL((k_rollout_linear<M, S, R>), dim3(g64), dim3(BLOCK), 0, s, la, tr)
+#define W2A_LAUNCH_LINEAR(M, S, R)                                                                        \
+  do {                                                                                                    \
+    if (gated) hipLaunchKernelGGL((k_rollout_linear<M, S, R, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr); \
+    else hipLaunchKernelGGL((k_rollout_linear<M, S, R, false>), dim3(g64), dim3(BLOCK), 0, s, la, tr);      \
+  } while (0)
   if (traj) {
     if (masks && policy->sample) W2A_LAUNCH_LINEAR(true, true, true);
     else if (masks) W2A_LAUNCH_LINEAR(true, false, true);
@@ -930,7 +952,7 @@ static int rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t
 int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                        int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                        int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
-  return rollout_linear(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+  return rollout_linear("w2a_rollout_linear", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
                         mask_words, last_return, ret_snapshot, stream, nullptr);
 }
 
@@ -940,52 +962,74 @@ int w2a_rollout_linear_record(w2a_env *env, const w2a_linear_policy *policy, int
                               void *stream, const w2a_trajectory *traj) {
   const int rc = check_trajectory(traj, "w2a_rollout_linear_record");
   if (rc != W2A_OK) return rc;
-  return rollout_linear(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+  return rollout_linear("w2a_rollout_linear_record", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
                         mask_words, last_return, ret_snapshot, stream, traj);
+}
+
+int w2a_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                             int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                             uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                             void *stream, const w2a_trajectory *traj, const uint32_t *allowed_days,
+                             int32_t allowed_words) {
+  if (traj) {
+    const int rc = check_trajectory(traj, "w2a_rollout_linear_gated");
+    if (rc != W2A_OK) return rc;
+  }
+  return rollout_linear("w2a_rollout_linear_gated", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+                        mask_words, last_return, ret_snapshot, stream, traj, true, allowed_days, allowed_words);
 }
 
 // what W2A_Q_LAST_ROLLOUT_KERNEL reports after w2a_rollout_mlp
 #define W2A_ROLLOUT_KERNEL_MLP 4
 
-static int rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                        int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                        int32_t mask_words, float *last_return, float *ret_snapshot, void *stream,
-                       const w2a_trajectory *traj) {
+                       const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
+                       int32_t gate_words = 0) {
   // what can be checked without the handle first (so that it is checked on any machine)
-  if (!policy) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL policy");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_steps must be positive");
-  if (!policy->params) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL params");
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_groups must be positive");
-  if (policy->n_layers != 1 && policy->n_layers != 2) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_layers must be 1 or 2");
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
+  if (policy->n_layers != 1 && policy->n_layers != 2) return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
   if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: width must be 16, 32 or 64");
+    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
   if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
-  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: sample must be 0 or 1");
+    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
+  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
   if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: require_budget must be 0 or 1");
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: params must be 16-B aligned");
-  if (!obs) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL obs (the rows the agent holds are the first day's input)");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_rollout_mlp: NULL handle");
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if ((alert_mask || attempt_mask) && mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: alert_mask / attempt_mask need ceil(T/32) words per env");
+    return fail(W2A_ERR_ARG, "%s: alert_mask / attempt_mask need ceil(T/32) words per env", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: not available with corrected-semantics flags (they change what the "
-                             "observation is)");
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the "
+                             "observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
   const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
   if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_rollout_mlp: n_groups * block size must stay below 2^31 floats");
-  REFUSE_WHILE_CAPTURING("w2a_rollout_mlp", stream);
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   MlpRolloutArgs ma;
   memset(&ma, 0, sizeof(ma));
+  ma.gate = gated ? gate : nullptr;
+  ma.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
     const int sl = env->obs_slot_host[j];
     if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_rollout_mlp: an observation column sits on slot 30 or 31 of the feature row");
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
     obs_mask |= 1u << sl;
     ma.slot_obs[sl] = (int8_t)j;
   }
@@ -1037,7 +1081,7 @@ static int rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_ste
 int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                     int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                     int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
-  return rollout_mlp(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+  return rollout_mlp("w2a_rollout_mlp", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
                      mask_words, last_return, ret_snapshot, stream, nullptr);
 }
 
@@ -1047,8 +1091,20 @@ int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n
                            void *stream, const w2a_trajectory *traj) {
   const int rc = check_trajectory(traj, "w2a_rollout_mlp_record");
   if (rc != W2A_OK) return rc;
-  return rollout_mlp(env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+  return rollout_mlp("w2a_rollout_mlp_record", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
                      mask_words, last_return, ret_snapshot, stream, traj);
+}
+
+int w2a_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                          int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                          uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                          void *stream, const w2a_trajectory *traj, const uint32_t *allowed_days, int32_t allowed_words) {
+  if (traj) {
+    const int rc = check_trajectory(traj, "w2a_rollout_mlp_gated");
+    if (rc != W2A_OK) return rc;
+  }
+  return rollout_mlp("w2a_rollout_mlp_gated", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
+                     mask_words, last_return, ret_snapshot, stream, traj, true, allowed_days, allowed_words);
 }
 
 // scratch of w2a_policy_gradient_linear: (delta_s, A_s) and the alert issued, per (call-day, env)
@@ -1058,41 +1114,50 @@ size_t w2a_policy_gradient_workspace_bytes(int64_t num_envs, int32_t n_steps) {
   return align256(sizeof(float2) * days) + align256(days);
 }
 
-int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
-                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
+static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
+                                  const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
+                                  bool gated, const uint32_t *gate, int32_t gate_words) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
-  if (!policy) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL policy");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: n_steps must be positive");
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL weight or bias");
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: n_groups must be positive");
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
   if (policy->sample != 1)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: sample must be 1 (a deterministic policy has no score function)");
+    return fail(W2A_ERR_ARG, "%s: sample must be 1 (a deterministic policy has no score function)", fn);
   if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: require_budget must be 0 or 1");
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: weight must be 16-B aligned");
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
   if (baseline != W2A_PG_BASELINE_NONE && baseline != W2A_PG_BASELINE_NO_ALERT)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT");
-  if (!obs) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL obs (the rows the agent holds are the first day's input)");
-  if (!grad || !workspace) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL grad or workspace");
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: workspace must be 256-B aligned");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: NULL handle");
+    return fail(W2A_ERR_ARG, "%s: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!grad || !workspace) return fail(W2A_ERR_ARG, "%s: NULL grad or workspace", fn);
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: not available with corrected-semantics flags (they change what "
-                             "the observation is)");
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
+                             "the observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
   if (workspace_bytes < w2a_policy_gradient_workspace_bytes(env->n, n_steps))
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_linear: workspace smaller than w2a_policy_gradient_workspace_bytes");
-  REFUSE_WHILE_CAPTURING("w2a_policy_gradient_linear", stream);
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_gradient_workspace_bytes", fn);
+  if (gated) {
+    const int rc = check_gate(fn, env, gate, gate_words);
+    if (rc != W2A_OK) return rc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   PolicyGradArgs ga;
   memset(&ga, 0, sizeof(ga));
   LinearRolloutArgs &la = ga.l;
+  la.gate = gated ? gate : nullptr;
+  la.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
     const int sl = env->obs_slot_host[j];
     if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_policy_gradient_linear: an observation column sits on slot 30 or 31 of the feature row");
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
     obs_mask |= 1u << sl;
     la.slot_obs[sl] = (int8_t)j;
   }
@@ -1115,11 +1180,25 @@ int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, in
   ga.grad = grad;
   hipStream_t s = (hipStream_t)stream;
   // reads the canonical state words (the rollout that follows would make them current itself); changes nothing else
-  if (!ensure_canonical(env, s, "w2a_policy_gradient_linear")) return W2A_ERR_STATE;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  hipLaunchKernelGGL(k_policy_gradient_linear, dim3(g64), dim3(BLOCK), 0, s, ga);
+  if (gated) hipLaunchKernelGGL(k_policy_gradient_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ga);
+  else hipLaunchKernelGGL(k_policy_gradient_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ga);
   HIP_TRY(hipGetLastError());
   return W2A_OK;
+}
+
+int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
+                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
+  return policy_gradient_linear("w2a_policy_gradient_linear", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, false,
+                                nullptr, 0);
+}
+
+int w2a_policy_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
+                                     const float *obs, float *grad, void *workspace, size_t workspace_bytes,
+                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
+  return policy_gradient_linear("w2a_policy_gradient_linear_gated", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, true,
+                                allowed_days, allowed_words);
 }
 
 // the workspace of w2a_policy_gradient_mlp: pass 1's scratch (9 B per env-day, 12 B per env) and the partial blocks
@@ -1165,51 +1244,60 @@ size_t w2a_policy_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps
   return pgm_layout(num_envs, n_steps, n_groups, width, n_layers).bytes;
 }
 
-int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
-                            const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
+static int policy_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
+                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
+                               bool gated, const uint32_t *gate, int32_t gate_words) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
-  if (!policy) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL policy");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_steps must be positive");
-  if (!policy->params) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL params");
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_groups must be positive");
+  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
+  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
   if (policy->n_layers != 1 && policy->n_layers != 2)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_layers must be 1 or 2");
+    return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
   if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: width must be 16, 32 or 64");
+    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
   if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
+    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
   if (policy->sample != 1)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: sample must be 1 (a deterministic policy has no score function)");
+    return fail(W2A_ERR_ARG, "%s: sample must be 1 (a deterministic policy has no score function)", fn);
   if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: require_budget must be 0 or 1");
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: params must be 16-B aligned");
+    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
   if (baseline != W2A_PG_BASELINE_NONE && baseline != W2A_PG_BASELINE_NO_ALERT)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT");
-  if (!obs) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL obs (the rows the agent holds are the first day's input)");
-  if (!grad || !workspace) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL grad or workspace");
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: workspace must be 256-B aligned");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: NULL handle");
+    return fail(W2A_ERR_ARG, "%s: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT", fn);
+  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
+  if (!grad || !workspace) return fail(W2A_ERR_ARG, "%s: NULL grad or workspace", fn);
+  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: not available with corrected-semantics flags (they change what "
-                             "the observation is)");
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
+                             "the observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
+    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
   const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
   if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: n_groups * block size must stay below 2^31 floats");
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
   const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
   if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "w2a_policy_gradient_mlp: workspace smaller than w2a_policy_gradient_mlp_workspace_bytes");
-  REFUSE_WHILE_CAPTURING("w2a_policy_gradient_mlp", stream);
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_gradient_mlp_workspace_bytes", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   MlpGradArgs ga;
   memset(&ga, 0, sizeof(ga));
   MlpRolloutArgs &ma = ga.m;
+  ma.gate = gated ? gate : nullptr;
+  ma.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
     const int sl = env->obs_slot_host[j];
     if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_policy_gradient_mlp: an observation column sits on slot 30 or 31 of the feature row");
+      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
     obs_mask |= 1u << sl;
     ma.slot_obs[sl] = (int8_t)j;
   }
@@ -1246,7 +1334,7 @@ int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t 
   ga.grad = grad;
   hipStream_t s = (hipStream_t)stream;
   // reads the canonical state words (the rollout that follows would make them current itself); changes nothing else
-  if (!ensure_canonical(env, s, "w2a_policy_gradient_mlp")) return W2A_ERR_STATE;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
   switch (policy->width * 4 + policy->n_layers) {
     case 16 * 4 + 1: launch_pgm<16, 1>(ga, g64, s); break;
@@ -1258,6 +1346,19 @@ int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t 
   }
   HIP_TRY(hipGetLastError());
   return W2A_OK;
+}
+
+int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
+                            const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
+  return policy_gradient_mlp("w2a_policy_gradient_mlp", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, false,
+                             nullptr, 0);
+}
+
+int w2a_policy_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
+                                  const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
+                                  const uint32_t *allowed_days, int32_t allowed_words) {
+  return policy_gradient_mlp("w2a_policy_gradient_mlp_gated", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, true,
+                             allowed_days, allowed_words);
 }
 
 // the checks w2a_imitation_gradient_linear and _mlp share once the policy's own have passed (same order in both)
@@ -1272,7 +1373,8 @@ static int check_imitation(const char *fn, const uint32_t *alert_mask, const flo
 static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy,
                                      const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
                                      const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
-                                     float *grad, float *loglik, int32_t *days, void *stream) {
+                                     float *grad, float *loglik, int32_t *days, void *stream, bool gated = false,
+                                     const uint32_t *gate = nullptr, int32_t gate_words = 0) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
   if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
   if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
@@ -1295,12 +1397,18 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
                              "what the observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
     return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
   if (stream_is_capturing((hipStream_t)stream))
     return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
                                "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   ImLinearArgs ia;
   memset(&ia, 0, sizeof(ia));
   LinearRolloutArgs &la = ia.l;
+  la.gate = gated ? gate : nullptr;
+  la.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
@@ -1330,7 +1438,8 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
   // reads the canonical state words; changes nothing else
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  hipLaunchKernelGGL(k_imitation_linear, dim3(g64), dim3(BLOCK), 0, s, ia);
+  if (gated) hipLaunchKernelGGL(k_imitation_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ia);
+  else hipLaunchKernelGGL(k_imitation_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ia);
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
@@ -1351,6 +1460,17 @@ int w2a_imitation_gradient_linear_weighted(w2a_env *env, const w2a_linear_policy
                                    env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream);
 }
 
+// day_weight nullable (= 1), as w2a_imitation_gradient_linear
+int w2a_imitation_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                        int32_t mask_words, const float *env_weight, const float *day_weight,
+                                        int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                        float *loglik, int32_t *days, void *stream, const uint32_t *allowed_days,
+                                        int32_t allowed_words) {
+  return imitation_gradient_linear("w2a_imitation_gradient_linear_gated", env, policy, alert_mask, mask_words,
+                                   env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
+                                   true, allowed_days, allowed_words);
+}
+
 // the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
 size_t w2a_imitation_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
                                                   int32_t n_layers) {
@@ -1361,7 +1481,8 @@ static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_po
                                   const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
                                   const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
                                   float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
-                                  void *stream) {
+                                  void *stream, bool gated = false, const uint32_t *gate = nullptr,
+                                  int32_t gate_words = 0) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
   if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
   if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
@@ -1398,6 +1519,10 @@ static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_po
   const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
   if (workspace_bytes < L.bytes)
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_imitation_gradient_mlp_workspace_bytes", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
   if (stream_is_capturing((hipStream_t)stream))
     return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
                                "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
@@ -1405,6 +1530,8 @@ static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_po
   memset(&ia, 0, sizeof(ia));
   MlpGradArgs &ga = ia.g;
   MlpRolloutArgs &ma = ga.m;
+  ma.gate = gated ? gate : nullptr;
+  ma.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
@@ -1480,6 +1607,17 @@ int w2a_imitation_gradient_mlp_weighted(w2a_env *env, const w2a_mlp_policy *poli
                                 workspace_bytes, stream);
 }
 
+// day_weight nullable (= 1), as w2a_imitation_gradient_mlp
+int w2a_imitation_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                                     int32_t mask_words, const float *env_weight, const float *day_weight,
+                                     int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                     float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
+  return imitation_gradient_mlp("w2a_imitation_gradient_mlp_gated", env, policy, alert_mask, mask_words, env_weight,
+                                day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
+                                workspace_bytes, stream, true, allowed_days, allowed_words);
+}
+
 // the checks w2a_surrogate_gradient_linear and _mlp share once the policy's own have passed (same order in both)
 static int check_surrogate_outputs(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
                                    const float *surrogate, const int32_t *clipped_days, const float *approx_kl,
@@ -1504,13 +1642,13 @@ static int check_surrogate_inputs(const char *fn, const float *advantage, int32_
   return W2A_OK;
 }
 
-int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                  int32_t mask_words, const float *env_weight, const float *advantage,
-                                  int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
-                                  double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
-                                  float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
-                                  int32_t *days, float *log_prob, void *stream) {
-  const char *fn = "w2a_surrogate_gradient_linear";
+static int surrogate_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy,
+                                     const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                                     const float *advantage, int32_t advantage_days, const float *old_log_prob,
+                                     int32_t old_log_prob_days, double clip, double entropy_coef, int32_t n_steps,
+                                     const float *obs, float *grad, float *surrogate, int32_t *clipped_days,
+                                     float *approx_kl, float *entropy, int32_t *days, float *log_prob, void *stream,
+                                     bool gated, const uint32_t *gate, int32_t gate_words) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
   if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
   if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
@@ -1533,12 +1671,18 @@ int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy,
                              "what the observation is)", fn);
   if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
     return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
   if (stream_is_capturing((hipStream_t)stream))
     return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
                                "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   SgLinearArgs sa;
   memset(&sa, 0, sizeof(sa));
   LinearRolloutArgs &la = sa.l;
+  la.gate = gated ? gate : nullptr;
+  la.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
@@ -1571,10 +1715,36 @@ int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy,
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   if (log_prob) HIP_TRY(hipMemsetAsync(log_prob, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
   const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  hipLaunchKernelGGL(k_surrogate_linear, dim3(g64), dim3(BLOCK), 0, s, sa);
+  if (gated) hipLaunchKernelGGL(k_surrogate_linear<true>, dim3(g64), dim3(BLOCK), 0, s, sa);
+  else hipLaunchKernelGGL(k_surrogate_linear<false>, dim3(g64), dim3(BLOCK), 0, s, sa);
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
+}
+
+int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                  int32_t mask_words, const float *env_weight, const float *advantage,
+                                  int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                  double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                                  float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                                  int32_t *days, float *log_prob, void *stream) {
+  return surrogate_gradient_linear("w2a_surrogate_gradient_linear", env, policy, alert_mask, mask_words, env_weight,
+                                   advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef,
+                                   n_steps, obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob,
+                                   stream, false, nullptr, 0);
+}
+
+int w2a_surrogate_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                        int32_t mask_words, const float *env_weight, const float *advantage,
+                                        int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                        double clip, double entropy_coef, int32_t n_steps, const float *obs,
+                                        float *grad, float *surrogate, int32_t *clipped_days, float *approx_kl,
+                                        float *entropy, int32_t *days, float *log_prob, void *stream,
+                                        const uint32_t *allowed_days, int32_t allowed_words) {
+  return surrogate_gradient_linear("w2a_surrogate_gradient_linear_gated", env, policy, alert_mask, mask_words,
+                                   env_weight, advantage, advantage_days, old_log_prob, old_log_prob_days, clip,
+                                   entropy_coef, n_steps, obs, grad, surrogate, clipped_days, approx_kl, entropy, days,
+                                   log_prob, stream, true, allowed_days, allowed_words);
 }
 
 // the workspace of w2a_imitation_gradient_mlp: the same scratch and partial blocks serve the same second pass
@@ -1583,13 +1753,14 @@ size_t w2a_surrogate_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_st
   return w2a_imitation_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
 }
 
-int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                               int32_t mask_words, const float *env_weight, const float *advantage,
-                               int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
-                               double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
-                               float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
-                               int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes, void *stream) {
-  const char *fn = "w2a_surrogate_gradient_mlp";
+static int surrogate_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy,
+                                  const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                                  const float *advantage, int32_t advantage_days, const float *old_log_prob,
+                                  int32_t old_log_prob_days, double clip, double entropy_coef, int32_t n_steps,
+                                  const float *obs, float *grad, float *surrogate, int32_t *clipped_days,
+                                  float *approx_kl, float *entropy, int32_t *days, float *log_prob, void *workspace,
+                                  size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate,
+                                  int32_t gate_words) {
   // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
   if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
   if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
@@ -1626,6 +1797,10 @@ int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
   const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
   if (workspace_bytes < L.bytes)
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_surrogate_gradient_mlp_workspace_bytes", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
   if (stream_is_capturing((hipStream_t)stream))
     return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
                                "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
@@ -1633,6 +1808,8 @@ int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
   memset(&sa, 0, sizeof(sa));
   MlpGradArgs &ga = sa.g;
   MlpRolloutArgs &ma = ga.m;
+  ma.gate = gated ? gate : nullptr;
+  ma.gate_words = gated ? gate_words : 0;
   uint32_t obs_mask = 0;
   for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
   for (int j = 0; j < env->tb.n_obs; ++j) {
@@ -1691,6 +1868,31 @@ int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
+}
+
+int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                               int32_t mask_words, const float *env_weight, const float *advantage,
+                               int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                               double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                               float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                               int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes, void *stream) {
+  return surrogate_gradient_mlp("w2a_surrogate_gradient_mlp", env, policy, alert_mask, mask_words, env_weight,
+                                advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps,
+                                obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob, workspace,
+                                workspace_bytes, stream, false, nullptr, 0);
+}
+
+int w2a_surrogate_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                                     int32_t mask_words, const float *env_weight, const float *advantage,
+                                     int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
+                                     double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
+                                     float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
+                                     int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes,
+                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
+  return surrogate_gradient_mlp("w2a_surrogate_gradient_mlp_gated", env, policy, alert_mask, mask_words, env_weight,
+                                advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps,
+                                obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob, workspace,
+                                workspace_bytes, stream, true, allowed_days, allowed_words);
 }
 
 // the checks w2a_value_gradient_linear and _mlp share once the network's own have passed (same order in both)
@@ -2122,31 +2324,37 @@ size_t w2a_hindsight_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_
   return hs_fixed_bytes(env->n) + (pool ? (size_t)big_envs * align256(hs_dp_bytes(u, hb)) : 0);
 }
 
-int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
-                          uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
-                          size_t workspace_bytes, void *stream) {
+static int hindsight_optimum(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                             uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                             size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words) {
   // what can be checked without the handle first (so that it is checked on any machine)
   if (!start || !ret_out || !alert_mask || !alerts_out || !workspace)
-    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: NULL argument");
+    return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
   if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
       !start->year_i || !start->coef_col || !start->sample || !start->finished)
-    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: NULL start-state array (t, used, streak, budget, n_days, county_w, "
-                             "year_i, coef_col, sample and finished are read)");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: n_steps must be positive");
-  if (mask_words <= 0) return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: mask_words must be positive");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: NULL handle");
+    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
+                             "year_i, coef_col, sample and finished are read)", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
   if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: alert_mask needs ceil(T/32) words per env");
+    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
   if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: not available with corrected-semantics flags (the reward then "
-                             "depends on attempts and on the 14-day window)");
-  REFUSE_WHILE_CAPTURING("w2a_hindsight_optimum", stream);
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
+                             "depends on attempts and on the 14-day window)", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
   const hipStream_t s = (hipStream_t)stream;
   const int64_t n = env->n;
   const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
   if (workspace_bytes < hs_fixed_bytes(n))
-    return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: workspace smaller than w2a_hindsight_workspace_bytes(env, n_steps, "
-                             "0, 1)");
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_workspace_bytes(env, n_steps, "
+                             "0, 1)", fn);
   char *ws = reinterpret_cast<char *>(workspace);
   {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
     int32_t *flag = reinterpret_cast<int32_t *>(ws);
@@ -2158,13 +2366,14 @@ int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_s
     HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (used27)
-      return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
-                               "agent): the (alerts, streak) DP would not be exact");
+      return fail(W2A_ERR_ARG, "%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
+                               "agent): the (alerts, streak) DP would not be exact", fn);
   }
   HsArgs a;
   memset(&a, 0, sizeof(a));
   a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.mask_words = mask_words; a.n = n;
   a.ret = ret_out; a.mask = alert_mask; a.alerts = alerts_out;
+  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
   a.u_env = reinterpret_cast<uint32_t *>(ws);
   a.order = reinterpret_cast<uint32_t *>(ws + align256(4 * (size_t)n));
   a.hist = reinterpret_cast<uint32_t *>(ws + 2 * align256(4 * (size_t)n));
@@ -2184,8 +2393,8 @@ int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_s
   // written: k_hs_plan writes none)
   for (uint32_t u = 0; u <= hb; ++u)
     if (hist[u] && hs_day_bytes(hb) + hs_dp_bytes(u, hb) > HS_LDS_CAP && pool_bytes < align256(hs_dp_bytes(u, hb)))
-      return fail(W2A_ERR_ARG, "w2a_hindsight_optimum: workspace too small for the largest budget in the batch "
-                               "(w2a_hindsight_workspace_bytes(env, n_steps, max(budget - used), 1) suffices)");
+      return fail(W2A_ERR_ARG, "%s: workspace too small for the largest budget in the batch "
+                               "(w2a_hindsight_workspace_bytes(env, n_steps, max(budget - used), 1) suffices)", fn);
   HIP_TRY(hipMemcpyAsync(a.cursor, off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
@@ -2193,7 +2402,10 @@ int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_s
     if (!hist[u]) continue;
     const size_t need = hs_day_bytes(hb) + hs_dp_bytes(u, hb);
     if (need <= HS_LDS_CAP) {
-      hipLaunchKernelGGL(k_hs_dp<false>, dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
+      if (gated)
+        hipLaunchKernelGGL((k_hs_dp<false, true>), dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
+      else
+        hipLaunchKernelGGL((k_hs_dp<false, false>), dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
       HIP_TRY(hipGetLastError());
     } else {
       const size_t stride = align256(hs_dp_bytes(u, hb));
@@ -2201,14 +2413,65 @@ int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_s
       const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
       for (uint32_t i = 0; i < hist[u]; i += per) {
         const uint32_t cnt = min(per, hist[u] - i);
-        hipLaunchKernelGGL(k_hs_dp<true>, dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, a, a.order + off[u] + i, u,
-                           pool, stride);
+        if (gated)
+          hipLaunchKernelGGL((k_hs_dp<true, true>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, a, a.order + off[u] + i, u,
+                             pool, stride);
+        else
+          hipLaunchKernelGGL((k_hs_dp<true, false>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, a, a.order + off[u] + i, u,
+                             pool, stride);
         HIP_TRY(hipGetLastError());
       }
     }
   }
   // the cursor upload reads `off` from this frame: it must have left before the function returns
   HIP_TRY(hipStreamSynchronize(s));
+  return W2A_OK;
+}
+
+int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                          uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  return hindsight_optimum("w2a_hindsight_optimum", env, start, n_steps, ret_out, alert_mask, mask_words, alerts_out, workspace, workspace_bytes,
+                           stream, false, nullptr, 0);
+}
+
+int w2a_hindsight_optimum_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                                uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                                size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                                int32_t allowed_words) {
+  return hindsight_optimum("w2a_hindsight_optimum_gated", env, start, n_steps, ret_out, alert_mask, mask_words, alerts_out, workspace, workspace_bytes,
+                           stream, true, allowed_days, allowed_words);
+}
+
+int w2a_alert_gate(w2a_env *env, int32_t obs_col, float threshold, const float *thresholds, int32_t n_steps,
+                   uint32_t *allowed_days, int32_t allowed_words, void *stream) {
+  // what can be checked without the handle first (so that it is checked on any machine)
+  if (!allowed_days) return fail(W2A_ERR_ARG, "w2a_alert_gate: NULL allowed_days");
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_alert_gate: n_steps must be positive");
+  if (!thresholds && threshold != threshold) return fail(W2A_ERR_ARG, "w2a_alert_gate: threshold is NaN");
+  if (!env) return fail(W2A_ERR_ARG, "w2a_alert_gate: NULL handle");
+  if (allowed_words <= 0 || (int64_t)allowed_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "w2a_alert_gate: allowed_days needs ceil(T/32) words per env");
+  if (obs_col < 0 || obs_col >= env->tb.n_obs) return fail(W2A_ERR_ARG, "w2a_alert_gate: obs_col outside the observation");
+  const int slot = env->obs_slot_host[obs_col];
+  if (slot < 0 || slot >= ROWF) return fail(W2A_ERR_SCHEMA, "w2a_alert_gate: the column has no slot in the feature row");
+  if (slot >= 24 && slot <= 27) return fail(W2A_ERR_ARG, "w2a_alert_gate: threshold policies read table-sourced columns only");
+  if ((env->tb.fixes & W2A_FIX_ALERTS_2WKS) && slot == env->tb.slot_hist2w)
+    return fail(W2A_ERR_ARG, "w2a_alert_gate: with W2A_FIX_ALERTS_2WKS this column holds the agent's own count: threshold "
+                             "policies read table-sourced columns only");
+  REFUSE_WHILE_CAPTURING("w2a_alert_gate", stream);
+  GateArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tb = env->tb; a.st = env->st; a.n = env->n;
+  a.slot = slot;
+  a.lag = (env->tb.fixes & W2A_FIX_OBS) ? 0 : 1;
+  a.n_steps = n_steps; a.words = allowed_words;
+  a.threshold = threshold; a.thresholds = thresholds; a.out = allowed_days;
+  hipStream_t s = (hipStream_t)stream;
+  // reads the canonical state words; writes nothing but the bitmap
+  if (!ensure_canonical(env, s, "w2a_alert_gate")) return W2A_ERR_STATE;
+  hipLaunchKernelGGL(k_alert_gate, dim3((unsigned)((env->n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, a);
+  HIP_TRY(hipGetLastError());
   return W2A_OK;
 }
 

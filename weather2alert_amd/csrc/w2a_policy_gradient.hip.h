@@ -26,6 +26,9 @@ struct PolicyGradArgs {
   float *grad;           // [n_obs + 1][n] per-env gradient: observation column j of env e at j * n + e, bias last
 };
 
+// GATE (w2a_policy_gradient_linear_gated): ga.l.gate restricts the attempts, as in k_rollout_linear<.., GATE>; a
+// disallowed day is a forced choice, m_s = 0. GATE = false compiles from the statements it had before the gate existed.
+template <bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const PolicyGradArgs ga) {
   const LinearRolloutArgs &la = ga.l;
   const RolloutArgs &a = la.r;
@@ -70,6 +73,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
     // the start state's on the first day and 0 after it, and the 14-day window only decays
     uint32_t streak_f = streak0, hist_f = hist0;
     bool active = D1_FIN(hot.y) == 0;
+    uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
     double z = (double)wp[31];
     if (active) {
 #pragma unroll
@@ -83,6 +87,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
       int32_t act = ((float)u * 2.3283064365386963e-10f < p) ? 1 : 0;  // a_s: the policy's own draw
       float delta = (float)act - p;
       if (a.pol.require_budget && budget - (int32_t)used <= 0) { act = 0; delta = 0.0f; }  // m_s = 0: forced, off-policy
+      if (GATE && active && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) { act = 0; delta = 0.0f; }
       const uint32_t atb_s = ((int32_t)used == budget) ? 1u : 0u;
       const uint32_t actual = (act == 1 && atb_s) ? 0u : (uint32_t)act;
       const uint32_t used2 = used + actual;

@@ -73,7 +73,9 @@ __device__ __forceinline__ int32_t pgm_group(const MlpRolloutArgs &ma, uint32_t 
 }
 
 // ------------------------------------------------------------------------------------------------ pass 1
-template <int WIDTH, int LAYERS>
+// GATE (w2a_policy_gradient_mlp_gated): a day ga.m.gate closes is a forced choice, m_s = 0: it reaches pass 2 as a zero
+// coefficient. GATE = false compiles from the statements it had before the gate existed
+template <int WIDTH, int LAYERS, bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_pgm_pass1(const MlpGradArgs ga) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
   const MlpRolloutArgs &ma = ga.m;
@@ -114,6 +116,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_pgm_pass1(const MlpGradArgs ga) {
   const size_t n = (size_t)a.n;
   double total = 0.0;
   int32_t n_valid = 0;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   bool active = D1_FIN(hot.y) == 0 && valid;
 #pragma unroll
   for (int k = 0; k < ROWF; ++k)
@@ -127,6 +130,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_pgm_pass1(const MlpGradArgs ga) {
     int32_t act = ((float)u * 2.3283064365386963e-10f < p) ? 1 : 0;  // a_s: the policy's own draw
     float delta = (float)act - p;
     if (a.pol.require_budget && budget - (int32_t)used <= 0) { act = 0; delta = 0.0f; }  // m_s = 0: forced, off-policy
+    if (GATE && active && !gate_allows(ma.gate, ma.gate_words, e, t, gate_word, gate_idx)) { act = 0; delta = 0.0f; }
     const uint32_t atb_s = ((int32_t)used == budget) ? 1u : 0u;
     const uint32_t actual = (act == 1 && atb_s) ? 0u : (uint32_t)act;
     const uint32_t used2 = used + actual;
@@ -625,7 +629,8 @@ __global__ __launch_bounds__(256) void k_pgm_reduce(const MlpGradArgs ga) {
 
 template <int WIDTH, int LAYERS>
 static void launch_pgm(const MlpGradArgs &ga, unsigned grid1, hipStream_t s) {
-  hipLaunchKernelGGL((k_pgm_pass1<WIDTH, LAYERS>), dim3(grid1), dim3(BLOCK), 0, s, ga);
+  if (ga.m.gate) hipLaunchKernelGGL((k_pgm_pass1<WIDTH, LAYERS, true>), dim3(grid1), dim3(BLOCK), 0, s, ga);
+  else hipLaunchKernelGGL((k_pgm_pass1<WIDTH, LAYERS, false>), dim3(grid1), dim3(BLOCK), 0, s, ga);
   hipLaunchKernelGGL(k_pgm_count, dim3(ga.n_chunks), dim3(64), 0, s, ga);
   hipLaunchKernelGGL(k_pgm_scan, dim3(1), dim3(1024), 0, s, ga);
   hipLaunchKernelGGL((k_pgm_pass2<WIDTH, LAYERS>), dim3(ga.n_chunks), dim3(64), 0, s, ga);

@@ -27,7 +27,23 @@ struct LinearRolloutArgs {
   uint32_t obs_mask;       // bit k: slot k is an observation column (others get a zero coefficient)
   float *obs;              // [n][n_obs] in: the row every env holds; out: the row it holds when the call ends
   int8_t slot_obs[RO64_SLOTS];  // slot -> observation column, -1 = none (kernel argument: scalar loads, no table)
+  const uint32_t *gate;    // [n][gate_words] allowed days (policy["allowed_days"]): bit (t & 31) of word t >> 5, the layout
+                           // of alert_mask. Read by the GATE = true instantiations only (the *_gated entry points)
+  int32_t gate_words;
 };
+
+// the gate's bit of day t: on a day whose bit is clear the attempted action is forced to 0 before the budget test, and
+// the day carries no score (as a day on which require_budget forces the action). One plain 32-bit load per env per 32
+// days; a day past the bitmap is not allowed (the host checks that gate_words covers T)
+__device__ __forceinline__ bool gate_allows(const uint32_t *gate, int32_t gate_words, uint32_t e, uint32_t t,
+                                            uint32_t &word, uint32_t &idx) {
+  const uint32_t wi = t >> 5;
+  if (wi != idx) {
+    idx = wi;
+    word = wi < (uint32_t)gate_words ? gate[(size_t)e * gate_words + wi] : 0u;
+  }
+  return ((word >> (t & 31)) & 1u) != 0u;
+}
 
 // RECORD (w2a_rollout_linear_record / w2a_rollout_mlp_record): every active day also stores the trajectory entry of
 // (call-day s, env e) -- action, logit, reward, flags and the observation row the env holds after the step -- with
@@ -113,7 +129,9 @@ __device__ __forceinline__ void traj_store_tile(const Args &pa, const w2a_trajec
 // 169-189 (2 waves/SIMD, no spill); held to 3 waves/SIMD (168) it spills 14-89 B per lane to scratch and runs faster:
 // 1.50 ms against 1.71 ms per 1 M-env episode (profiles/r07/kernel_trace_linear.txt).
 // RECORD = false compiles to the kernel without a trajectory (same registers, scratch and LDS).
-template <bool MASKS, bool SAMPLE, bool RECORD>
+// GATE (w2a_rollout_linear_gated / _record_gated): la.gate restricts the attempts; GATE = false compiles from the
+// statements it had before the gate existed.
+template <bool MASKS, bool SAMPLE, bool RECORD, bool GATE>
 __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRolloutArgs la, const w2a_trajectory tr) {
   const RolloutArgs &a = la.r;
   const int64_t slot64 = (int64_t)logical_block(blockIdx.x, gridDim.x >> 3) * BLOCK + threadIdx.x;
@@ -165,6 +183,7 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
   float snap = 0.0f;
   bool snapped = false;
   bool active = !fin && valid;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   // first day: the logit of the observation row the agent holds
   double z = (double)wp[31];
   if (active) {
@@ -184,6 +203,7 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
       act = z > 0.0 ? 1 : 0;
     }
     if (a.pol.require_budget && budget - (int32_t)used <= 0) act = 0;
+    if (GATE && active && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) act = 0;  // not attempted
     // ---- env.py:242-250
     const uint32_t atb_s = ((int32_t)used == budget) ? 1u : 0u;
     const uint32_t actual = (act == 1 && atb_s) ? 0u : (uint32_t)act;

@@ -37,6 +37,9 @@ struct MlpRolloutArgs {
   uint32_t obs_mask;       // bit k: slot k is an observation column (the others feed zeros)
   float *obs;              // [n][n_obs] in: the row every env holds; out: the row it holds when the call ends
   int8_t slot_obs[RO64_SLOTS];  // slot -> observation column, -1 = none
+  const uint32_t *gate;    // [n][gate_words] allowed days, as LinearRolloutArgs::gate: read by the GATE = true
+                           // instantiations only (the *_gated entry points); NULL selects GATE = false on the host
+  int32_t gate_words;
 };
 
 #define MLP_XS 36  // LDS row of one env's input vector, in floats: 16-B aligned rows, conflict-free B-operand reads
@@ -153,7 +156,9 @@ __device__ __forceinline__ float mlp_logit_groups(const MlpRolloutArgs &ma, int3
 // Registers: see DESIGN.md (k_rollout_mlp); held to 2 waves/SIMD like the other large day loops
 // RECORD: the trajectory of w2a_rollout_mlp_record (k_rollout_linear's traj_record_day); RECORD = false compiles to the
 // kernel without one
-template <int WIDTH, int LAYERS, bool MASKS, bool RECORD>
+// GATE (w2a_rollout_mlp_gated): ma.gate restricts the attempts, as in k_rollout_linear; GATE = false compiles from the
+// statements it had before the gate existed
+template <int WIDTH, int LAYERS, bool MASKS, bool RECORD, bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs ma, const int32_t sample,
                                                           const w2a_trajectory tr) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
@@ -204,6 +209,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
   uint32_t att_word = 0, att_idx = 0xFFFFFFFFu;
   float snap = 0.0f;
   bool snapped = false;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   bool active = !fin && valid;
   // first day: the logit of the observation row the agent holds (zeros for lanes with no live env)
 #pragma unroll
@@ -222,6 +228,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
       act = z > 0.0f ? 1 : 0;
     }
     if (a.pol.require_budget && budget - (int32_t)used <= 0) act = 0;
+    if (GATE && active && !gate_allows(ma.gate, ma.gate_words, e, t, gate_word, gate_idx)) act = 0;  // not attempted
     // ---- env.py:242-250
     const uint32_t atb_s = ((int32_t)used == budget) ? 1u : 0u;
     const uint32_t actual = (act == 1 && atb_s) ? 0u : (uint32_t)act;
@@ -334,10 +341,16 @@ static void launch_rollout_mlp(const MlpRolloutArgs &ma, bool masks, int32_t sam
   w2a_trajectory tr;
   memset(&tr, 0, sizeof(tr));
   if (traj) tr = *traj;
-  if (traj && masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
-  else if (traj) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
-  else if (masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
-  else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+#define W2A_LAUNCH_MLP(M, R)                                                                                             \
+  do {                                                                                                                   \
+    if (ma.gate) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, M, R, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr); \
+    else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, M, R, false>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);   \
+  } while (0)
+  if (traj && masks) W2A_LAUNCH_MLP(true, true);
+  else if (traj) W2A_LAUNCH_MLP(false, true);
+  else if (masks) W2A_LAUNCH_MLP(true, false);
+  else W2A_LAUNCH_MLP(false, false);
+#undef W2A_LAUNCH_MLP
 }
 
 #endif  // W2A_ROLLOUT_MLP_HIP_H

@@ -81,6 +81,9 @@ __device__ __forceinline__ double sg_day(const SurrogateArgs &sg, double w_e, do
 
 // Registers: as k_imitation_linear (the policy row, xv[] and 31 fp64 accumulators) plus the three fp64 sums and the
 // temporaries of the fp64 exponentials; at two waves per SIMD it spills (DESIGN.md has the figures).
+// GATE (w2a_surrogate_gradient_linear_gated): sa.l.gate restricts the attempts, as in k_imitation_linear<GATE>: a
+// disallowed day is attempted as 0 and adds nothing to any sum. GATE = false compiles from the statements it had before.
+template <bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_surrogate_linear(const SgLinearArgs sa) {
   const LinearRolloutArgs &la = sa.l;
   const RolloutArgs &a = la.r;
@@ -113,6 +116,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_surrogate_linear(const SgLinearArg
   }
   const double w_e = sa.sg.env_weight ? (double)sa.sg.env_weight[e] : 1.0;
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   double g[32];
 #pragma unroll
   for (int k = 0; k < 32; ++k) g[k] = 0.0;  // slot k's column; the bias rides in slot 31, as in the policy row
@@ -128,6 +132,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_surrogate_linear(const SgLinearArg
       if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
     lab = im_label_bits(sa.sg.alert_mask, sa.sg.mask_words, e, t, lab_word, lab_idx);
     scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
+    if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
     if (scores) {
       const float delta = (float)lab - sigmoid_f32((float)z);
       const double c = sg_day(sa.sg, w_e, z, delta, lab, e, sum);
@@ -173,6 +178,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_surrogate_linear(const SgLinearArg
       if (active && s + 1 < a.n_steps) {
         lab = im_label_bits(sa.sg.alert_mask, sa.sg.mask_words, e, t, lab_word, lab_idx);
         scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
+        if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
         if (scores) {
           const float delta = (float)lab - sigmoid_f32((float)zp);
           const double c = sg_day(sa.sg, w_e, zp, delta, lab, (size_t)(s + 1) * n + e, sum);
@@ -198,7 +204,9 @@ __global__ __launch_bounds__(BLOCK, 2) void k_surrogate_linear(const SgLinearArg
 }
 
 // ------------------------------------------------------------------------------------------------ MLP: pass 1
-template <int WIDTH, int LAYERS>
+// GATE (w2a_surrogate_gradient_mlp_gated): as k_surrogate_linear<GATE>; GATE = false compiles from the statements it
+// had before the gate existed
+template <int WIDTH, int LAYERS, bool GATE>
 __global__ __launch_bounds__(BLOCK, 2) void k_sg_pass1(const SgMlpArgs sa) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
   const MlpGradArgs &ga = sa.g;
@@ -224,6 +232,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_sg_pass1(const SgMlpArgs sa) {
   const size_t n = (size_t)a.n;
   const double w_e = sa.sg.env_weight ? (double)sa.sg.env_weight[e] : 1.0;
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   SgSums sum = {0.0, 0.0, 0.0, 0, 0};
   int32_t n_valid = 0;
   bool active = D1_FIN(hot.y) == 0 && valid;
@@ -240,6 +249,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_sg_pass1(const SgMlpArgs sa) {
     const float delta = (float)act - p;
     bool scores = true;
     if (a.pol.require_budget && budget - (int32_t)used <= 0) { act = 0; scores = false; }  // m_s = 0: forced
+    if (GATE && active && !gate_allows(ma.gate, ma.gate_words, e, t, gate_word, gate_idx)) { act = 0; scores = false; }
     const uint32_t atb_s = ((int32_t)used == budget) ? 1u : 0u;
     const uint32_t actual = (act == 1 && atb_s) ? 0u : (uint32_t)act;
     const uint32_t used2 = used + actual;
@@ -300,7 +310,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_sg_pass1(const SgMlpArgs sa) {
 template <int WIDTH, int LAYERS>
 static void launch_sg(const SgMlpArgs &sa, unsigned grid1, hipStream_t s) {
   const MlpGradArgs &ga = sa.g;
-  hipLaunchKernelGGL((k_sg_pass1<WIDTH, LAYERS>), dim3(grid1), dim3(BLOCK), 0, s, sa);
+  if (ga.m.gate) hipLaunchKernelGGL((k_sg_pass1<WIDTH, LAYERS, true>), dim3(grid1), dim3(BLOCK), 0, s, sa);
+  else hipLaunchKernelGGL((k_sg_pass1<WIDTH, LAYERS, false>), dim3(grid1), dim3(BLOCK), 0, s, sa);
   hipLaunchKernelGGL(k_pgm_count, dim3(ga.n_chunks), dim3(64), 0, s, ga);
   hipLaunchKernelGGL(k_pgm_scan, dim3(1), dim3(1024), 0, s, ga);
   hipLaunchKernelGGL((k_pgm_pass2<WIDTH, LAYERS>), dim3(ga.n_chunks), dim3(64), 0, s, ga);

@@ -794,7 +794,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
                  omitted when G == 1), "sample": False, "seed": 0}   (weather2alert_amd/policy.py) |
                 {"kind": "mlp", "layers": [(W1, b1), [(W2, b2),] (Wo, bo)] (torch Linear convention, optionally with
                  a leading G dim), "activation": "tanh" | "relu", "group", "order", "sample", "seed"}
-                plus optional "require_budget": True (never attempt an alert with no budget left).
+                plus optional "require_budget": True (never attempt an alert with no budget left), and for the linear
+                and mlp kinds optional "allowed_days": bool [num_envs, T] by day of the episode (alert_gate(), or any
+                other mask; or the packed int32 [num_envs, ceil(T / 32)] of alert_gate(packed=True)): on a day whose bit is clear the attempted action is 0 -- before the attempt is recorded and
+                before the budget test, so it never counts as an over-budget attempt -- and the day is a forced choice:
+                no score under policy_gradient (m_s = 0, as for require_budget), a recorded "action" of 0 next to the
+                policy's own "logit", and under hindsight=True the optimum is the best schedule on allowed days. The
+                uniform u of a day does not depend on the gate. ValueError for a wrong dtype or shape and for a kind
+                that takes no gate. An all-ones mask gives the bits of the call without the key.
         The linear policy acts on logit = weight[g] . obs + bias[g] (fp64 over the f32 values) for the env's group g,
         where obs is exactly the row step() would have returned before that decision -- so rollout(linear, k) is
         indistinguishable from k iterations of `a = policy(obs); obs = env.step(a)`, observation buffer included.
@@ -878,6 +885,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         ct = self.ct
         kind = policy.get("kind")
         lin = None
+        gate = _policy.check_allowed_days(policy, self.num_envs, ct.T, self.device, "rollout()")
         if record and kind not in ("linear", "mlp"):
             raise ValueError(f"rollout(record=True) needs kind 'linear' or 'mlp', got {kind!r}")
         if posterior_returns and self.fixes - {"budget"}:
@@ -903,9 +911,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                "step()/reset()): call step() or reset() first")
         pr, hs = bool(posterior_returns), bool(hindsight)
         if kind == "mlp":
-            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr, hs, pg)
+            return self._rollout_mlp(lin, n_steps, alert_mask, bool(record), pr, hs, pg, gate)
         if lin is not None:
-            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr, hs, pg)
+            return self._rollout_linear(lin, n_steps, alert_mask, bool(record), pr, hs, pg, gate)
         p = _ffi.Policy()
         p.kind = _ffi.POLICY_KINDS[kind]
         p.p = float(policy.get("p", 0.0))
@@ -926,13 +934,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return self._rollout_run(p, None, n_steps, alert_mask, keep, posterior_returns=pr, hindsight=hs)
 
     def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
-                        policy_gradient=None) -> dict:
+                        policy_gradient=None, gate=None) -> dict:
         """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
         lp = _ffi.LinearPolicy()
         lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
         lp.group = None if lin.group is None else lin.group.data_ptr()
         lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
-        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns, hindsight, policy_gradient)
+        out = self._rollout_run(None, lp, n_steps, alert_mask, lin, record, posterior_returns, hindsight, policy_gradient,
+                                gate)
         out["group_mean_return"] = _policy.group_mean(out["return"], lin.group, lin.n_groups)
         if posterior_returns:
             out["group_posterior_returns"] = _policy.group_mean(out["posterior_returns"], lin.group, lin.n_groups)
@@ -945,7 +954,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return out
 
     def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
-                     policy_gradient=None) -> dict:
+                     policy_gradient=None, gate=None) -> dict:
         """rollout(kind="mlp"): w2a_rollout_mlp on the checked, packed policy (weather2alert_amd/policy.py)."""
         mp = _ffi.MlpPolicy()
         mp.params = mlp.params.data_ptr()
@@ -954,7 +963,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         mp.n_groups, mp.n_layers, mp.width = mlp.n_groups, mlp.n_layers, mlp.width
         mp.activation = _ffi.MLP_ACTIVATIONS[mlp.activation]
         mp.sample, mp.require_budget, mp.seed = int(mlp.sample), int(mlp.require_budget), mlp.seed
-        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns, hindsight, policy_gradient)
+        out = self._rollout_run(None, mp, n_steps, alert_mask, mlp, record, posterior_returns, hindsight, policy_gradient,
+                                gate)
         if policy_gradient is not None:
             out["policy_gradient"] = {"layers": _policy.unpack_mlp_grad(
                 out.pop("_policy_gradient_blocks"), self.ct.obs_slot, self.ct.n_obs, mlp.hidden, mlp.n_out)}
@@ -966,7 +976,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return out
 
     def _rollout_run(self, p, lp, n_steps, alert_mask, keep, record=False, posterior_returns=False,
-                     hindsight=False, policy_gradient=None) -> dict:
+                     hindsight=False, policy_gradient=None, gate=None) -> dict:
         """The launch and the outputs shared by every policy kind: built-in (p, w2a_rollout / the posterior-mean path) or
         linear / mlp (lp, w2a_rollout_linear / w2a_rollout_mlp, or their *_record forms with record=True).
         posterior_returns: the alert bitmap is taken in any case (the rollout kernels' results do not depend on it) and
@@ -974,7 +984,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         the same start state and days. policy_gradient ("none" / "no_alert"): w2a_policy_gradient_linear /
         w2a_policy_gradient_mlp right before the rollout, on the state and the rows the rollout starts from; the linear
         kind's per-env rows come back as "_policy_gradient_env" f32 [n_obs + 1, N], the mlp kind's per-group blocks as
-        "_policy_gradient_blocks" f32 [G, stride] (the layout of the packed parameters)."""
+        "_policy_gradient_blocks" f32 [G, stride] (the layout of the packed parameters). gate: the packed
+        "allowed_days" of a linear or mlp policy (int32 [N, words]); the gradient, the rollout and the hindsight optimum then
+        take their *_gated entry points."""
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
@@ -1021,18 +1033,32 @@ class HeatAlertVecEnv(_VectorEnvBase):
                     (keep.n_groups, _policy.mlp_stride(keep.width, keep.n_layers)), dtype=torch.float32, device=dev)
                 ws = torch.empty(self._lib.w2a_policy_gradient_mlp_workspace_bytes(
                     n, steps, keep.n_groups, keep.width, keep.n_layers), dtype=torch.uint8, device=dev)
-                _ffi.check(self._lib.w2a_policy_gradient_mlp(
-                    self._h, C.byref(gp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
-                    out["_policy_gradient_blocks"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                    "w2a_policy_gradient_mlp")
+                pgm_args = (self._h, C.byref(gp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
+                            out["_policy_gradient_blocks"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+                if gate is None:
+                    _ffi.check(self._lib.w2a_policy_gradient_mlp(*pgm_args), "w2a_policy_gradient_mlp")
+                else:
+                    _ffi.check(self._lib.w2a_policy_gradient_mlp_gated(*pgm_args, gate.data_ptr(), int(gate.shape[1])),
+                               "w2a_policy_gradient_mlp_gated")
             elif policy_gradient is not None:
                 out["_policy_gradient_env"] = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
                 ws = torch.empty(self._lib.w2a_policy_gradient_workspace_bytes(n, steps), dtype=torch.uint8, device=dev)
-                _ffi.check(self._lib.w2a_policy_gradient_linear(
-                    self._h, C.byref(lp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
-                    out["_policy_gradient_env"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                    "w2a_policy_gradient_linear")
-            if lp is not None:
+                pg_args = (self._h, C.byref(lp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
+                           out["_policy_gradient_env"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+                if gate is None:
+                    _ffi.check(self._lib.w2a_policy_gradient_linear(*pg_args), "w2a_policy_gradient_linear")
+                else:
+                    _ffi.check(self._lib.w2a_policy_gradient_linear_gated(*pg_args, gate.data_ptr(), int(gate.shape[1])),
+                               "w2a_policy_gradient_linear_gated")
+            if lp is not None and gate is not None:
+                fn = "w2a_rollout_mlp_gated" if isinstance(lp, _ffi.MlpPolicy) else "w2a_rollout_linear_gated"
+                _ffi.check(getattr(self._lib, fn)(
+                    self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
+                    out["alerts"].data_ptr(), out["attempts_over_budget"].data_ptr(),
+                    None if mask is None else mask.data_ptr(), None if amask is None else amask.data_ptr(), words,
+                    self._fr_ptr, None if snap is None else snap.data_ptr(), self._stream(),
+                    None if tr is None else C.byref(tr), gate.data_ptr(), int(gate.shape[1])), fn)
+            elif lp is not None:
                 fn = "w2a_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_rollout_linear"
                 args = (self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
                         out["alerts"].data_ptr(), out["attempts_over_budget"].data_ptr(),
@@ -1053,8 +1079,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
             if posterior_returns:
                 out["posterior_returns"] = self._posterior_returns_packed(st0, mask, words, steps)
             if hindsight:
-                out["hindsight_return"] = self._hindsight_packed(st0, steps)[0]
-        self._keep_pol = keep
+                out["hindsight_return"] = self._hindsight_packed(st0, steps, gate)[0]
+        self._keep_pol = (keep, gate)
         self._obs_current = lp is not None  # built-in policies write no observation rows (a reset below may)
         # only what this call returns is decoded (sixteen arrays of N int32 otherwise: 64 MB of writes at 1 M envs)
         st = self.state() if alert_mask else self._state_packed(("finished",))[1]
@@ -1136,7 +1162,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         cloning of hindsight_optimum()["alert_days"], and with env_weight fitting to the elite envs of a population or
         reward- / advantage-weighted regression.
           policy      a kind="linear" or kind="mlp" dict, as rollout() takes it (group, order, require_budget and the
-                      two-row MLP output included; sample and seed are ignored: nothing is drawn)
+                      two-row MLP output included; sample and seed are ignored: nothing is drawn). With
+                      "allowed_days" an alert the schedule asks for on a disallowed day is attempted as 0
+                      and the day is not scored: no gradient, no log-likelihood, and "days" does not count it
           alert_days  bool [N, T] by day of the episode: the actions ATTEMPTED (hindsight_optimum()["alert_days"],
                       rollout(alert_mask=True)["alert_days"]); an attempt with used == budget issues no alert, as in step()
           env_weight  optional float [N], finite (default 1)
@@ -1169,6 +1197,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
         pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
         dw = _policy.check_day_weight(day_weight, min(steps, 2**31 - 1), n, dev)
+        gate = _policy.check_allowed_days(policy, n, ct.T, dev, "imitation_gradient()")
         if self._needs_reset:
             raise RuntimeError("call reset() before imitation_gradient()")
         if not self._obs_current:
@@ -1186,7 +1215,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 lp.group = None if pol.group is None else pol.group.data_ptr()
                 lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
                 rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
-                if dw is None:
+                if gate is not None:
+                    _ffi.check(self._lib.w2a_imitation_gradient_linear_gated(
+                        self._h, C.byref(lp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
+                        0 if dw is None else int(dw.shape[0]), steps, self._obs.data_ptr(), rows.data_ptr(),
+                        out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream(), gate.data_ptr(),
+                        int(gate.shape[1])), "w2a_imitation_gradient_linear_gated")
+                elif dw is None:
                     _ffi.check(self._lib.w2a_imitation_gradient_linear(
                         self._h, C.byref(lp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), rows.data_ptr(),
                         out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream()),
@@ -1213,7 +1248,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                      device=dev)
                 ws = torch.empty(self._lib.w2a_imitation_gradient_mlp_workspace_bytes(
                     n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
-                if dw is None:
+                if gate is not None:
+                    _ffi.check(self._lib.w2a_imitation_gradient_mlp_gated(
+                        self._h, C.byref(mp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
+                        0 if dw is None else int(dw.shape[0]), steps, self._obs.data_ptr(), blocks.data_ptr(),
+                        out["log_likelihood"].data_ptr(), out["days"].data_ptr(), ws.data_ptr(), ws.numel(),
+                        self._stream(), gate.data_ptr(), int(gate.shape[1])), "w2a_imitation_gradient_mlp_gated")
+                elif dw is None:
                     _ffi.check(self._lib.w2a_imitation_gradient_mlp(
                         self._h, C.byref(mp), mask.data_ptr(), words, wp, steps, self._obs.data_ptr(), blocks.data_ptr(),
                         out["log_likelihood"].data_ptr(), out["days"].data_ptr(), ws.data_ptr(), ws.numel(),
@@ -1248,7 +1289,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
           g_e    = w_e sum_s [live_s rho_s A_s (a_s - p_s) + entropy_coef dH_s/dz] dz_s/dtheta,  H_s the Bernoulli entropy
         and per group the mean of g_e over its envs, so ``theta += lr * grad`` ascends
         mean_e w_e (L_e + entropy_coef sum_s H_s).
-          policy        a kind="linear" or kind="mlp" dict, as imitation_gradient() takes it
+          policy        a kind="linear" or kind="mlp" dict, as imitation_gradient() takes it ("allowed_days" included:
+                        a disallowed day is attempted as 0 and adds no ratio, entropy, approx_kl or clipped day; "days"
+                        does not count it and "log_prob" is 0 there)
           alert_days    bool [N, T] by day of the episode (rollout(alert_mask=True)["alert_days"])
           advantage     float [S >= n_steps, N], finite (ValueError), by call-day and ENV ID: value_gradient()'s
                         "advantage", or any other (GAE, discounting and normalisation are the caller's)
@@ -1279,6 +1322,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
         adv, old, clip, beta = _policy.check_surrogate_args(advantage, old_log_prob, clip, entropy_coef,
                                                             min(steps, 2**31 - 1), n, dev)
+        gate = _policy.check_allowed_days(policy, n, ct.T, dev, "surrogate_gradient()")
         if self._needs_reset:
             raise RuntimeError("call reset() before surrogate_gradient()")
         if not self._obs_current:
@@ -1307,9 +1351,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 lp.group = None if pol.group is None else pol.group.data_ptr()
                 lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
                 rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
-                _ffi.check(self._lib.w2a_surrogate_gradient_linear(
-                    self._h, C.byref(lp), *front, rows.data_ptr(), *outs, self._stream()),
-                    "w2a_surrogate_gradient_linear")
+                if gate is None:
+                    _ffi.check(self._lib.w2a_surrogate_gradient_linear(
+                        self._h, C.byref(lp), *front, rows.data_ptr(), *outs, self._stream()),
+                        "w2a_surrogate_gradient_linear")
+                else:
+                    _ffi.check(self._lib.w2a_surrogate_gradient_linear_gated(
+                        self._h, C.byref(lp), *front, rows.data_ptr(), *outs, self._stream(), gate.data_ptr(),
+                        int(gate.shape[1])), "w2a_surrogate_gradient_linear_gated")
                 # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
                 g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
                 out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
@@ -1327,9 +1376,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                      device=dev)
                 ws = torch.empty(self._lib.w2a_surrogate_gradient_mlp_workspace_bytes(
                     n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
-                _ffi.check(self._lib.w2a_surrogate_gradient_mlp(
-                    self._h, C.byref(mp), *front, blocks.data_ptr(), *outs, ws.data_ptr(), ws.numel(), self._stream()),
-                    "w2a_surrogate_gradient_mlp")
+                sgm_args = (self._h, C.byref(mp), *front, blocks.data_ptr(), *outs, ws.data_ptr(), ws.numel(),
+                            self._stream())
+                if gate is None:
+                    _ffi.check(self._lib.w2a_surrogate_gradient_mlp(*sgm_args), "w2a_surrogate_gradient_mlp")
+                else:
+                    _ffi.check(self._lib.w2a_surrogate_gradient_mlp_gated(*sgm_args, gate.data_ptr(),
+                                                                          int(gate.shape[1])),
+                               "w2a_surrogate_gradient_mlp_gated")
                 out["policy_gradient"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden,
                                                                             pol.n_out)}
             ws_ = out["surrogate"].double() if w is None else (w.double() * out["surrogate"].double())
@@ -1479,7 +1533,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return out
 
     # ------------------------------------------------------------------ hindsight optimum
-    def hindsight_optimum(self, start_state: dict | None = None, n_steps: int | None = None) -> dict:
+    def hindsight_optimum(self, start_state: dict | None = None, n_steps: int | None = None,
+                          allowed_days=None) -> dict:
         """Every env's best alert schedule in hindsight: knowing the weather of the whole stretch, the env's own
         posterior draw and its remaining budget, the schedule of at most budget - used alerts with the highest return
         over the days from start_state (a state() dict; default: the current state) for n_steps days (default: to the
@@ -1492,9 +1547,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
         Envs finished in start_state give 0 and an empty schedule. An exact DP over (alerts issued, current streak)
         (w2a_hindsight_optimum, include/w2a.h); ties do not alert. Reads start_state and the tables only: the env's
         state, observation buffer and bookkeeping are untouched. Sampled reward and faithful semantics only; tables
-        whose slot-27 (alert_2wks of the agent) coefficient is nonzero are refused (ValueError)."""
+        whose slot-27 (alert_2wks of the agent) coefficient is nonzero are refused (ValueError).
+        allowed_days: optional bool [N, T] by day of the episode (alert_gate(), or any other mask; ValueError for
+        another dtype or shape): the DP may alert only on allowed days, so the result is the best schedule UNDER the
+        restriction -- the regret yardstick and the imitation expert of a policy with the same "allowed_days". Its
+        return is still bit for bit what the env pays for that schedule."""
         self._check_hindsight("hindsight_optimum()")
         ct, n, dev = self.ct, self.num_envs, self.device
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev,
+                                          "hindsight_optimum()")
         if start_state is None:
             st = self._state_packed(_HS_FIELDS)[1]
         else:
@@ -1509,7 +1570,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if steps <= 0:
             raise ValueError("n_steps must be positive")
         with torch.cuda.device(dev):
-            ret, mask, alerts = self._hindsight_packed(st, steps)
+            ret, mask, alerts = self._hindsight_packed(st, steps, gate)
         words = mask.shape[1]
         bits = torch.arange(32, device=dev, dtype=torch.int32)
         days = (((mask.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()
@@ -1529,9 +1590,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
             raise ValueError(f"{who}: some coefficient row has a nonzero slot-27 (alert_2wks of the agent) term; the "
                              "(alerts, streak) DP is exact only without it")
 
-    def _hindsight_packed(self, st0: dict, steps: int):
+    def _hindsight_packed(self, st0: dict, steps: int, gate=None):
         """w2a_hindsight_optimum on device int32 state arrays: (return f32 [N], packed bitmap i32 [N, words],
-        alerts i32 [N])."""
+        alerts i32 [N]). gate: packed allowed days, int32 [N, words] (w2a_hindsight_optimum_gated)."""
         n, dev = self.num_envs, self.device
         words = (self.ct.T + 31) // 32
         ret = torch.empty(n, dtype=torch.float32, device=dev)
@@ -1548,10 +1609,70 @@ class HeatAlertVecEnv(_VectorEnvBase):
         v = _ffi.StateView()
         for k in _HS_FIELDS:
             setattr(v, k, st0[k].data_ptr())
-        _ffi.check(self._lib.w2a_hindsight_optimum(self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words,
-                                                   alerts.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()),
-                   "w2a_hindsight_optimum")
+        hs_args = (self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words, alerts.data_ptr(), ws.data_ptr(),
+                   ws_bytes, self._stream())
+        if gate is None:
+            _ffi.check(self._lib.w2a_hindsight_optimum(*hs_args), "w2a_hindsight_optimum")
+        else:
+            _ffi.check(self._lib.w2a_hindsight_optimum_gated(*hs_args, gate.data_ptr(), int(gate.shape[1])),
+                       "w2a_hindsight_optimum_gated")
         return ret, mask, alerts
+
+    # ------------------------------------------------------------------ alert gate
+    def alert_gate(self, feature: str = "heat_qi", threshold=0.8, n_steps: int | None = None,
+                   packed: bool = False) -> torch.Tensor:
+        """bool [N, T] by day of the episode: the days on which the older reference env's alert restriction
+        (``restrict_alerts`` / ``HI_restriction``: an alert attempted while observation[heat_qi] < HI_restriction becomes
+        "no alert") lets an alert through -- the "allowed_days" of a kind="linear" or kind="mlp" policy dict and of
+        hindsight_optimum(). Bit t of env e is set iff the value of `feature` in the observation row the agent HOLDS
+        when it chooses day t's action is >= threshold (>=, as in the reference; the built-in "threshold" kind tests >).
+        That row is the one step() would have returned: the table row of day max(t - 1, 0) under the faithful semantics
+        (the lagging observation, Q6: days 0 and 1 both see row 0), the row of day t itself with the "obs" fix.
+          feature    a table-sourced observation column (KeyError for an unknown name; ValueError for the state-sourced
+                     alert_lag1, alerts_streak, remaining_budget and the agent's alert_2wks, with the threshold kind's message)
+          threshold  a float, or a float [N] tensor: tau_county[county_of_env] for per-county thresholds, tau_group[group]
+                     for a sweep (ValueError for another shape, a non-float tensor or NaN)
+          n_steps    days from every env's current day (default: to the end of every episode)
+          packed     True: return the kernel's own int32 [N, ceil(T / 32)] words (bit t & 31 of word t >> 5), which
+                     "allowed_days" and allowed_days= also take -- nothing is unpacked here or packed again per call
+        Covers the days each env would still step from its current state; days before, days past the stretch and
+        finished envs are False. Reads the tables with each env's (county, year) and the state; writes nothing but its
+        result (w2a_alert_gate, include/w2a.h). Nothing is kept on the env: the mask is an argument of the calls that
+        take it, and any other bool [N, T] mask (weekends off, a month window) is as good."""
+        if self._needs_reset:
+            raise RuntimeError("call reset() before alert_gate()")
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if feature not in ct.feature_names:
+            raise KeyError(feature)
+        col = ct.feature_names.index(feature)
+        slot = int(_policy.slot_map(ct.obs_slot, ct.n_obs)[col])
+        if 24 <= slot <= 27 or ("alert_2wks" in self.fixes and slot == ct.slot_of.get("alerts_2wks", -1)):
+            raise ValueError(f"alert_gate(feature={feature!r}): threshold policies read table-sourced columns only")
+        if n_steps is not None:
+            if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps <= 0:
+                raise ValueError(f"alert_gate(): n_steps must be a positive int, got {n_steps!r}")
+        steps = int(n_steps) if n_steps is not None else ct.T
+        tau, tau_t = 0.0, None
+        if torch.is_tensor(threshold) or isinstance(threshold, np.ndarray):
+            tau_t = threshold if torch.is_tensor(threshold) else torch.as_tensor(threshold)
+            if not tau_t.is_floating_point() or tuple(tau_t.shape) != (n,):
+                raise ValueError(f"alert_gate(): threshold must be a float or a float [{n}] tensor, got "
+                                 f"{tuple(tau_t.shape)} {tau_t.dtype}")
+            tau_t = tau_t.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if bool(torch.isnan(tau_t).any()):
+                raise ValueError("alert_gate(): threshold holds NaN")
+        else:
+            if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+                    or np.isnan(threshold):
+                raise ValueError(f"alert_gate(): threshold must be a float or a float [{n}] tensor, got {threshold!r}")
+            tau = float(threshold)
+        words = (ct.T + 31) // 32
+        out = torch.empty((n, words), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _ffi.check(self._lib.w2a_alert_gate(self._h, col, tau, None if tau_t is None else tau_t.data_ptr(), steps,
+                                                out.data_ptr(), words, self._stream()), "w2a_alert_gate")
+        self._keep_gate = tau_t  # the launch is asynchronous
+        return out if packed else _policy.unpack_alert_days(out, ct.T)
 
     def _rollout_posterior_mean(self, p, steps, out, mask, amask, words, snap, st0) -> int:
         """rollout() with reward_mode="posterior_mean": one launch of k_pm_rollout when it applies, else per day

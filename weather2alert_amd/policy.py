@@ -12,7 +12,9 @@ per-group reduction of the returns. Nothing here launches a kernel, so all of it
      "group": g,              # int [num_envs] in [0, G); may be omitted when G == 1
      "sample": False,         # False: alert iff logit > 0; True: alert iff u < sigmoid(logit)
      "seed": 0,               # sample=True only: keys the Bernoulli policy's counter-RNG uniform u
-     "require_budget": False} # never attempt an alert with no budget left
+     "require_budget": False, # never attempt an alert with no budget left
+     "allowed_days": None}    # optional bool [num_envs, T] by day of the episode (HeatAlertVecEnv.alert_gate(), or any
+                              # other mask): on a day whose bit is clear the attempted action is 0, before the budget test
 """
 from __future__ import annotations
 
@@ -23,7 +25,8 @@ import torch
 
 ROW_FLOATS = 32
 LOGIT_SLOTS = 30  # slots the day loop multiplies (0..29); an observation column elsewhere cannot be served
-KEYS = {"kind", "weight", "bias", "group", "sample", "seed", "require_budget"}
+KEYS = {"kind", "weight", "bias", "group", "sample", "seed", "require_budget", "allowed_days"}
+GATE_KINDS = ("linear", "mlp")  # the kinds whose kernels take "allowed_days"
 
 
 @dataclass
@@ -148,6 +151,46 @@ def check_policy_gradient(policy_gradient, kind, sample, reward_mode="sampled", 
 IMITATION_KINDS = ("linear", "mlp")
 
 
+def check_day_bitmap(days, name: str, num_envs: int, T: int, who: str) -> torch.Tensor:
+    """A bool [num_envs, T] array by day of the episode (``alert_days``, ``allowed_days``) as a torch tensor; ValueError
+    for another dtype or shape."""
+    ad = days if torch.is_tensor(days) else torch.as_tensor(np.asarray(days))
+    if ad.dtype != torch.bool:
+        raise ValueError(f"{who}: {name} must be bool, got {ad.dtype}")
+    if ad.dim() != 2 or tuple(ad.shape) != (num_envs, T):
+        raise ValueError(f"{who}: {name} must be bool [{num_envs}, {T}] (by day of the episode), "
+                         f"got {tuple(ad.shape)}")
+    return ad
+
+
+def check_allowed_days(policy, num_envs: int, T: int, device, who: str):
+    """The ``"allowed_days"`` key of a policy dict (or the ``allowed_days=`` of hindsight_optimum(), passed as
+    ``{"kind": "linear", "allowed_days": mask}``): None when it is absent or None, else the gate packed like a
+    schedule, int32 [num_envs, ceil(T / 32)] on `device`. ValueError for a kind that takes no gate (every built-in kind:
+    their kernels are not gated), a dtype other than bool and a shape other than [num_envs, T]. A mask that is already
+    packed -- int32 [num_envs, ceil(T / 32)], alert_gate(packed=True) -- is taken as it is: a loop over epochs then packs
+    nothing per call. The shape decides before the dtype is looked at: an int32 [N, 1] array at T <= 32 is read as packed
+    words, never refused as "not bool" (of no consequence at the tables' T)."""
+    if not isinstance(policy, dict) or policy.get("allowed_days") is None:
+        return None
+    kind = policy.get("kind")
+    if kind not in GATE_KINDS:
+        raise ValueError(f"{who}: 'allowed_days' is taken by kind {' or '.join(repr(k) for k in GATE_KINDS)} only, "
+                         f"got {kind!r}")
+    words = (T + 31) // 32
+    ad = policy["allowed_days"]
+    if torch.is_tensor(ad) and ad.dtype == torch.int32 and tuple(ad.shape) == (num_envs, words):
+        return ad.to(device).contiguous()
+    ad = check_day_bitmap(ad, "allowed_days", num_envs, T, who)
+    return pack_alert_days(ad.to(device), words)
+
+
+def unpack_alert_days(words: torch.Tensor, T: int) -> torch.Tensor:
+    """The inverse of pack_alert_days: int32 [N, W] -> bool [N, T]."""
+    bits = torch.arange(32, device=words.device, dtype=torch.int32)
+    return (((words.unsqueeze(-1) >> bits) & 1).reshape(words.shape[0], words.shape[1] * 32)[:, :T]).bool()
+
+
 def pack_alert_days(alert_days: torch.Tensor, words: int) -> torch.Tensor:
     """bool [N, T <= 32 * words] by day of the episode -> int32 [N, words], bit (t & 31) of word t >> 5: the bitmap the
     rollout kernels write and w2a_posterior_returns / w2a_imitation_gradient_* read."""
@@ -178,12 +221,7 @@ def check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs: int, T
             raise ValueError(f"{who}: n_steps must be positive")
     if alert_days is None:
         raise ValueError(f"{who}: alert_days is required")
-    ad = alert_days if torch.is_tensor(alert_days) else torch.as_tensor(np.asarray(alert_days))
-    if ad.dtype != torch.bool:
-        raise ValueError(f"{who}: alert_days must be bool, got {ad.dtype}")
-    if ad.dim() != 2 or tuple(ad.shape) != (num_envs, T):
-        raise ValueError(f"{who}: alert_days must be bool [{num_envs}, {T}] (by day of the episode), "
-                         f"got {tuple(ad.shape)}")
+    ad = check_day_bitmap(alert_days, "alert_days", num_envs, T, who)
     w = None
     if env_weight is not None:
         w = env_weight if torch.is_tensor(env_weight) else torch.as_tensor(np.asarray(env_weight))
@@ -322,7 +360,7 @@ def group_mean_columns(values_t: torch.Tensor, group: torch.Tensor | None, n_gro
 # One or two hidden layers of width 1..64; the first takes the n_obs observation columns in observation order; the
 # output has one row (the logit) or two (SB3's two action values: logit = row1 - row0, folded here in fp64).
 
-MLP_KEYS = {"kind", "layers", "activation", "group", "order", "sample", "seed", "require_budget"}
+MLP_KEYS = {"kind", "layers", "activation", "group", "order", "sample", "seed", "require_budget", "allowed_days"}
 MLP_WIDTHS = (16, 32, 64)  # the kernel's padded hidden widths
 MLP_MAX_HIDDEN = 2
 MLP_ACTIVATIONS = ("tanh", "relu")
