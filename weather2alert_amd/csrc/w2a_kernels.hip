@@ -26,6 +26,10 @@
 //     run time by w2a_set_posterior_kernel; the matrix unit's other user is the policy rollout k_rollout_mfma
 //     (w2a_rollout_mfma.hip.h: the table-sourced part of both logits per (county, year) tile as int8 MFMAs).
 //
+// The C ABI's host side lives in this file, except two parts it includes inside its extern "C" block: w2a_step
+// (w2a_step_dispatch.hip.h) and the learned-policy entry points -- w2a_rollout_linear / _mlp, the policy, imitation,
+// surrogate and value gradients and GAE, with their shared checks and argument fills (w2a_policy_dispatch.hip.h).
+//
 // No fallback path exists: without this library (or without a ROCm device) constructing an env raises.
 
 #include <hip/hip_runtime.h>
@@ -34,6 +38,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "w2a.h"
 
@@ -825,1461 +830,8 @@ int w2a_rollout(w2a_env *env, const w2a_policy *policy, int32_t n_steps, float *
   return W2A_OK;
 }
 
-// what W2A_Q_LAST_ROLLOUT_KERNEL reports after w2a_rollout_linear (the built-in kernels' values come from
-// w2a_bookkeeping.h: bk_rollout_kernel)
-#define W2A_ROLLOUT_KERNEL_LINEAR 3
-
-// the host-side checks of a trajectory (w2a_rollout_linear_record, w2a_rollout_mlp_record): before anything else
-static int check_trajectory(const w2a_trajectory *traj, const char *fn) {
-  if (!traj) return fail(W2A_ERR_ARG, "%s: NULL trajectory", fn);
-  if (!traj->obs || !traj->logit || !traj->reward || !traj->action || !traj->flags)
-    return fail(W2A_ERR_ARG, "%s: NULL trajectory array", fn);
-  return W2A_OK;
-}
-
-// zeroes the flags of every (call-day, env) the kernel writes: entries of envs that take no step keep 0
-static int clear_trajectory_flags(const w2a_env *env, int32_t n_steps, const w2a_trajectory *traj, hipStream_t s) {
-  HIP_TRY(hipMemsetAsync(traj->flags, 0, (size_t)n_steps * (size_t)env->n, s));
-  return W2A_OK;
-}
-
-// the allowed-days bitmap of the *_gated entry points: checked where the schedule's bitmap is
-static int check_gate(const char *fn, const w2a_env *env, const uint32_t *gate, int32_t gate_words) {
-  if (!gate) return fail(W2A_ERR_ARG, "%s: NULL allowed_days (the entry point without _gated takes no gate)", fn);
-  if ((int64_t)gate_words * 32 < env->tb.T) return fail(W2A_ERR_ARG, "%s: allowed_days needs ceil(T/32) words per env", fn);
-  return W2A_OK;
-}
-
-// gated: the call came through w2a_rollout_linear_gated (gate is then checked, and the GATE instantiations run)
-static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                          int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
-                          uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
-                          void *stream, const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
-                          int32_t gate_words = 0) {
-  // what can be checked without the handle first (so that it is checked on any machine)
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((alert_mask || attempt_mask) && mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask / attempt_mask need ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the "
-                             "observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  if (gated) {
-    const int rc = check_gate(fn, env, gate, gate_words);
-    if (rc != W2A_OK) return rc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  LinearRolloutArgs la;
-  memset(&la, 0, sizeof(la));
-  la.gate = gated ? gate : nullptr;
-  la.gate_words = gated ? gate_words : 0;
-  // every observation column must sit on a slot the day loop multiplies (0..RO64_SLOTS-1): then slot 31, which carries
-  // the bias, is provably none of them
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    la.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = la.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.pol.seed = policy->seed;
-  a.n_steps = n_steps; a.ret_out = ret_out; a.alerts_out = alerts_out; a.attempts_over_budget = attempts_over_budget;
-  a.alert_mask = alert_mask; a.attempt_mask = attempt_mask; a.mask_words = mask_words; a.last_return = last_return;
-  a.ret_snapshot = ret_snapshot;
-  a.order = env->order;
-  la.weight = reinterpret_cast<const float4 *>(policy->weight);
-  la.bias = policy->bias;
-  la.group = policy->group;
-  la.n_groups = policy->n_groups;
-  la.n_obs = env->tb.n_obs;
-  la.obs_mask = obs_mask;
-  la.obs = obs;
-  hipStream_t s = (hipStream_t)stream;
-  HipDev dv{env, s};
-  (void)bk_rollout_begin(env->bk, dv, n_steps);  // same lock-step bookkeeping as w2a_rollout
-  env->bk.last_rollout_kernel = W2A_ROLLOUT_KERNEL_LINEAR;
-  if (alert_mask) HIP_TRY(hipMemsetAsync(alert_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
-  if (attempt_mask) HIP_TRY(hipMemsetAsync(attempt_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  const bool masks = alert_mask || attempt_mask || ret_snapshot;
-  w2a_trajectory tr;
-  memset(&tr, 0, sizeof(tr));
-  if (traj) {
-    tr = *traj;
-    la.r.order = nullptr;  // identity order: the kernel's staged store design (every env's result is order-independent)
-    const int rc = clear_trajectory_flags(env, n_steps, traj, s);
-    if (rc != W2A_OK) return rc;
-  }
-#define W2A_LAUNCH_LINEAR(M, S, R)                                                                        \
-  do {                                                                                                    \
-    if (gated) hipLaunchKernelGGL((k_rollout_linear<M, S, R, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr); \
-    else hipLaunchKernelGGL((k_rollout_linear<M, S, R, false>), dim3(g64), dim3(BLOCK), 0, s, la, tr);      \
-  } while (0)
-  if (traj) {
-    if (masks && policy->sample) W2A_LAUNCH_LINEAR(true, true, true);
-    else if (masks) W2A_LAUNCH_LINEAR(true, false, true);
-    else if (policy->sample) W2A_LAUNCH_LINEAR(false, true, true);
-    else W2A_LAUNCH_LINEAR(false, false, true);
-  } else {
-    if (masks && policy->sample) W2A_LAUNCH_LINEAR(true, true, false);
-    else if (masks) W2A_LAUNCH_LINEAR(true, false, false);
-    else if (policy->sample) W2A_LAUNCH_LINEAR(false, true, false);
-    else W2A_LAUNCH_LINEAR(false, false, false);
-  }
-#undef W2A_LAUNCH_LINEAR
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
-                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
-  return rollout_linear("w2a_rollout_linear", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
-                        mask_words, last_return, ret_snapshot, stream, nullptr);
-}
-
-int w2a_rollout_linear_record(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
-                              float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
-                              uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
-                              void *stream, const w2a_trajectory *traj) {
-  const int rc = check_trajectory(traj, "w2a_rollout_linear_record");
-  if (rc != W2A_OK) return rc;
-  return rollout_linear("w2a_rollout_linear_record", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
-                        mask_words, last_return, ret_snapshot, stream, traj);
-}
-
-int w2a_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                             int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
-                             uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
-                             void *stream, const w2a_trajectory *traj, const uint32_t *allowed_days,
-                             int32_t allowed_words) {
-  if (traj) {
-    const int rc = check_trajectory(traj, "w2a_rollout_linear_gated");
-    if (rc != W2A_OK) return rc;
-  }
-  return rollout_linear("w2a_rollout_linear_gated", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
-                        mask_words, last_return, ret_snapshot, stream, traj, true, allowed_days, allowed_words);
-}
-
-// what W2A_Q_LAST_ROLLOUT_KERNEL reports after w2a_rollout_mlp
-#define W2A_ROLLOUT_KERNEL_MLP 4
-
-static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                       int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
-                       int32_t mask_words, float *last_return, float *ret_snapshot, void *stream,
-                       const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
-                       int32_t gate_words = 0) {
-  // what can be checked without the handle first (so that it is checked on any machine)
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->n_layers != 1 && policy->n_layers != 2) return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
-  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
-  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
-  if (policy->sample != 0 && policy->sample != 1) return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((alert_mask || attempt_mask) && mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask / attempt_mask need ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the "
-                             "observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
-  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  MlpRolloutArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.gate = gated ? gate : nullptr;
-  ma.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    ma.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = ma.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.pol.seed = policy->seed;
-  a.n_steps = n_steps; a.ret_out = ret_out; a.alerts_out = alerts_out; a.attempts_over_budget = attempts_over_budget;
-  a.alert_mask = alert_mask; a.attempt_mask = attempt_mask; a.mask_words = mask_words; a.last_return = last_return;
-  a.ret_snapshot = ret_snapshot;
-  a.order = policy->order ? reinterpret_cast<const uint32_t *>(policy->order) : env->order;
-  ma.params = policy->params;
-  ma.group = policy->group;
-  ma.n_groups = policy->n_groups;
-  ma.stride = (int32_t)stride;
-  ma.activation = policy->activation;
-  ma.n_obs = env->tb.n_obs;
-  ma.obs_mask = obs_mask;
-  ma.obs = obs;
-  hipStream_t s = (hipStream_t)stream;
-  HipDev dv{env, s};
-  (void)bk_rollout_begin(env->bk, dv, n_steps);  // same lock-step bookkeeping as w2a_rollout
-  env->bk.last_rollout_kernel = W2A_ROLLOUT_KERNEL_MLP;
-  if (alert_mask) HIP_TRY(hipMemsetAsync(alert_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
-  if (attempt_mask) HIP_TRY(hipMemsetAsync(attempt_mask, 0, (size_t)env->n * mask_words * sizeof(uint32_t), s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  const bool masks = alert_mask || attempt_mask || ret_snapshot;
-  const int32_t smp = policy->sample;
-  if (traj) {
-    const int rc = clear_trajectory_flags(env, n_steps, traj, s);
-    if (rc != W2A_OK) return rc;
-    // one group: identity order, the kernel's staged store design (results are order-independent); with groups the
-    // group-major order keeps the kernel's group loop short and the rows are stored directly
-    if (policy->n_groups == 1) ma.r.order = nullptr;
-  }
-  switch (policy->width * 4 + policy->n_layers) {
-    case 16 * 4 + 1: launch_rollout_mlp<16, 1>(ma, masks, smp, traj, g64, s); break;
-    case 16 * 4 + 2: launch_rollout_mlp<16, 2>(ma, masks, smp, traj, g64, s); break;
-    case 32 * 4 + 1: launch_rollout_mlp<32, 1>(ma, masks, smp, traj, g64, s); break;
-    case 32 * 4 + 2: launch_rollout_mlp<32, 2>(ma, masks, smp, traj, g64, s); break;
-    case 64 * 4 + 1: launch_rollout_mlp<64, 1>(ma, masks, smp, traj, g64, s); break;
-    default: launch_rollout_mlp<64, 2>(ma, masks, smp, traj, g64, s); break;
-  }
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-int w2a_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                    int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
-                    int32_t mask_words, float *last_return, float *ret_snapshot, void *stream) {
-  return rollout_mlp("w2a_rollout_mlp", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
-                     mask_words, last_return, ret_snapshot, stream, nullptr);
-}
-
-int w2a_rollout_mlp_record(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                           int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
-                           uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
-                           void *stream, const w2a_trajectory *traj) {
-  const int rc = check_trajectory(traj, "w2a_rollout_mlp_record");
-  if (rc != W2A_OK) return rc;
-  return rollout_mlp("w2a_rollout_mlp_record", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
-                     mask_words, last_return, ret_snapshot, stream, traj);
-}
-
-int w2a_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
-                          int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
-                          uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
-                          void *stream, const w2a_trajectory *traj, const uint32_t *allowed_days, int32_t allowed_words) {
-  if (traj) {
-    const int rc = check_trajectory(traj, "w2a_rollout_mlp_gated");
-    if (rc != W2A_OK) return rc;
-  }
-  return rollout_mlp("w2a_rollout_mlp_gated", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask, attempt_mask,
-                     mask_words, last_return, ret_snapshot, stream, traj, true, allowed_days, allowed_words);
-}
-
-// scratch of w2a_policy_gradient_linear: (delta_s, A_s) and the alert issued, per (call-day, env)
-size_t w2a_policy_gradient_workspace_bytes(int64_t num_envs, int32_t n_steps) {
-  if (num_envs <= 0 || n_steps <= 0) return 0;
-  const size_t days = (size_t)num_envs * (size_t)n_steps;
-  return align256(sizeof(float2) * days) + align256(days);
-}
-
-static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
-                                  const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
-                                  bool gated, const uint32_t *gate, int32_t gate_words) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->sample != 1)
-    return fail(W2A_ERR_ARG, "%s: sample must be 1 (a deterministic policy has no score function)", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
-  if (baseline != W2A_PG_BASELINE_NONE && baseline != W2A_PG_BASELINE_NO_ALERT)
-    return fail(W2A_ERR_ARG, "%s: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!grad || !workspace) return fail(W2A_ERR_ARG, "%s: NULL grad or workspace", fn);
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
-                             "the observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  if (workspace_bytes < w2a_policy_gradient_workspace_bytes(env->n, n_steps))
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_gradient_workspace_bytes", fn);
-  if (gated) {
-    const int rc = check_gate(fn, env, gate, gate_words);
-    if (rc != W2A_OK) return rc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  PolicyGradArgs ga;
-  memset(&ga, 0, sizeof(ga));
-  LinearRolloutArgs &la = ga.l;
-  la.gate = gated ? gate : nullptr;
-  la.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    la.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = la.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.pol.seed = policy->seed;
-  a.n_steps = n_steps;
-  a.order = env->order;
-  la.weight = reinterpret_cast<const float4 *>(policy->weight);
-  la.bias = policy->bias;
-  la.group = policy->group;
-  la.n_groups = policy->n_groups;
-  la.n_obs = env->tb.n_obs;
-  la.obs_mask = obs_mask;
-  la.obs = const_cast<float *>(obs);  // the kernel only reads it
-  ga.baseline = baseline;
-  ga.day = reinterpret_cast<float2 *>(workspace);
-  ga.day_alert = reinterpret_cast<uint8_t *>(workspace) + align256(sizeof(float2) * (size_t)env->n * (size_t)n_steps);
-  ga.grad = grad;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words (the rollout that follows would make them current itself); changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  if (gated) hipLaunchKernelGGL(k_policy_gradient_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ga);
-  else hipLaunchKernelGGL(k_policy_gradient_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ga);
-  HIP_TRY(hipGetLastError());
-  return W2A_OK;
-}
-
-int w2a_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
-                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
-  return policy_gradient_linear("w2a_policy_gradient_linear", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, false,
-                                nullptr, 0);
-}
-
-int w2a_policy_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
-                                     const float *obs, float *grad, void *workspace, size_t workspace_bytes,
-                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
-  return policy_gradient_linear("w2a_policy_gradient_linear_gated", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, true,
-                                allowed_days, allowed_words);
-}
-
-// the workspace of w2a_policy_gradient_mlp: pass 1's scratch (9 B per env-day, 12 B per env) and the partial blocks
-// (fp64 [stride] each) of pass 2's waves
-struct PgmLayout {
-  int32_t tiles;      // 64-env tiles per wave of pass 2
-  uint32_t n_chunks;  // its waves
-  uint32_t capacity;  // partial blocks: one per wave and one per group boundary of a group-major order
-  size_t day, day_alert, total, n_valid, chunk_count, chunk_base, tag, pcount, partial, bytes;
-};
-#define PGM_TARGET_WAVES 1024  // one wave per SIMD of the device
-#define PGM_MAX_TILES 16
-
-static PgmLayout pgm_layout(int64_t n, int32_t n_steps, int32_t n_groups, int32_t width, int32_t n_layers) {
-  PgmLayout L;
-  const int64_t n_tiles = (n + 63) / 64;
-  int64_t tiles = (n_tiles + PGM_TARGET_WAVES - 1) / PGM_TARGET_WAVES;
-  tiles = tiles < 1 ? 1 : (tiles > PGM_MAX_TILES ? PGM_MAX_TILES : tiles);
-  L.tiles = (int32_t)tiles;
-  L.n_chunks = (uint32_t)((n_tiles + tiles - 1) / tiles);
-  const int64_t groups = (int64_t)n_groups < n ? (int64_t)n_groups : n;
-  L.capacity = (uint32_t)(L.n_chunks + groups);
-  const size_t days = (size_t)n * (size_t)n_steps;
-  const size_t stride = (size_t)W2A_MLP_STRIDE((int64_t)width, n_layers);
-  size_t off = 0;
-  L.day = off; off += align256(sizeof(float2) * days);
-  L.day_alert = off; off += align256(days);
-  L.total = off; off += align256(sizeof(double) * (size_t)n);
-  L.n_valid = off; off += align256(sizeof(int32_t) * (size_t)n);
-  L.chunk_count = off; off += align256(sizeof(uint32_t) * L.n_chunks);
-  L.chunk_base = off; off += align256(sizeof(uint32_t) * ((size_t)L.n_chunks + 1));
-  L.tag = off; off += align256(sizeof(int32_t) * (size_t)L.capacity);
-  L.pcount = off; off += align256(sizeof(uint32_t) * (size_t)L.capacity);
-  L.partial = off; off += align256(sizeof(double) * (size_t)L.capacity * stride);
-  L.bytes = off;
-  return L;
-}
-
-size_t w2a_policy_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
-                                               int32_t n_layers) {
-  if (num_envs <= 0 || n_steps <= 0 || n_groups <= 0) return 0;
-  if ((width != 16 && width != 32 && width != 64) || (n_layers != 1 && n_layers != 2)) return 0;
-  return pgm_layout(num_envs, n_steps, n_groups, width, n_layers).bytes;
-}
-
-static int policy_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
-                               const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
-                               bool gated, const uint32_t *gate, int32_t gate_words) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->n_layers != 1 && policy->n_layers != 2)
-    return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
-  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
-  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
-  if (policy->sample != 1)
-    return fail(W2A_ERR_ARG, "%s: sample must be 1 (a deterministic policy has no score function)", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
-  if (baseline != W2A_PG_BASELINE_NONE && baseline != W2A_PG_BASELINE_NO_ALERT)
-    return fail(W2A_ERR_ARG, "%s: baseline must be W2A_PG_BASELINE_NONE or W2A_PG_BASELINE_NO_ALERT", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!grad || !workspace) return fail(W2A_ERR_ARG, "%s: NULL grad or workspace", fn);
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
-                             "the observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
-  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
-  const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
-  if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_gradient_mlp_workspace_bytes", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  MlpGradArgs ga;
-  memset(&ga, 0, sizeof(ga));
-  MlpRolloutArgs &ma = ga.m;
-  ma.gate = gated ? gate : nullptr;
-  ma.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    ma.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = ma.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.pol.seed = policy->seed;
-  a.n_steps = n_steps;
-  // the gradient kernels write no state, so their visiting order is their own: the policy's (group-major, so that the
-  // partial blocks fit the workspace) or identity -- never the handle's feature-row order
-  a.order = reinterpret_cast<const uint32_t *>(policy->order);
-  ma.params = policy->params;
-  ma.group = policy->group;
-  ma.n_groups = policy->n_groups;
-  ma.stride = (int32_t)stride;
-  ma.activation = policy->activation;
-  ma.n_obs = env->tb.n_obs;
-  ma.obs_mask = obs_mask;
-  ma.obs = const_cast<float *>(obs);  // the kernels only read it
-  ga.baseline = baseline;
-  char *ws = reinterpret_cast<char *>(workspace);
-  ga.day = reinterpret_cast<float2 *>(ws + L.day);
-  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
-  ga.total = reinterpret_cast<double *>(ws + L.total);
-  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
-  ga.tiles = L.tiles;
-  ga.n_chunks = L.n_chunks;
-  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
-  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
-  ga.capacity = L.capacity;
-  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
-  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
-  ga.partial = reinterpret_cast<double *>(ws + L.partial);
-  ga.grad = grad;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words (the rollout that follows would make them current itself); changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  switch (policy->width * 4 + policy->n_layers) {
-    case 16 * 4 + 1: launch_pgm<16, 1>(ga, g64, s); break;
-    case 16 * 4 + 2: launch_pgm<16, 2>(ga, g64, s); break;
-    case 32 * 4 + 1: launch_pgm<32, 1>(ga, g64, s); break;
-    case 32 * 4 + 2: launch_pgm<32, 2>(ga, g64, s); break;
-    case 64 * 4 + 1: launch_pgm<64, 1>(ga, g64, s); break;
-    default: launch_pgm<64, 2>(ga, g64, s); break;
-  }
-  HIP_TRY(hipGetLastError());
-  return W2A_OK;
-}
-
-int w2a_policy_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
-                            const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream) {
-  return policy_gradient_mlp("w2a_policy_gradient_mlp", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, false,
-                             nullptr, 0);
-}
-
-int w2a_policy_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
-                                  const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
-                                  const uint32_t *allowed_days, int32_t allowed_words) {
-  return policy_gradient_mlp("w2a_policy_gradient_mlp_gated", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, true,
-                             allowed_days, allowed_words);
-}
-
-// the checks w2a_imitation_gradient_linear and _mlp share once the policy's own have passed (same order in both)
-static int check_imitation(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
-                           const float *loglik, const int32_t *days) {
-  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to score)", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!grad || !loglik || !days) return fail(W2A_ERR_ARG, "%s: NULL grad, loglik or days", fn);
-  return W2A_OK;
-}
-
-static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy,
-                                     const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
-                                     const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
-                                     float *grad, float *loglik, int32_t *days, void *stream, bool gated = false,
-                                     const uint32_t *gate = nullptr, int32_t gate_words = 0) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->sample != 0 && policy->sample != 1)
-    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
-  const int rc = check_imitation(fn, alert_mask, obs, grad, loglik, days);
-  if (rc != W2A_OK) return rc;
-  if (day_weight && day_weight_days < n_steps)
-    return fail(W2A_ERR_ARG, "%s: day_weight holds fewer call-days than n_steps", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change "
-                             "what the observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  ImLinearArgs ia;
-  memset(&ia, 0, sizeof(ia));
-  LinearRolloutArgs &la = ia.l;
-  la.gate = gated ? gate : nullptr;
-  la.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    la.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = la.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.n_steps = n_steps;
-  a.order = env->order;
-  la.weight = reinterpret_cast<const float4 *>(policy->weight);
-  la.bias = policy->bias;
-  la.group = policy->group;
-  la.n_groups = policy->n_groups;
-  la.n_obs = env->tb.n_obs;
-  la.obs_mask = obs_mask;
-  la.obs = const_cast<float *>(obs);  // the kernel only reads it
-  ia.im.alert_mask = alert_mask; ia.im.mask_words = mask_words; ia.im.env_weight = env_weight;
-  ia.im.day_weight = day_weight;
-  ia.im.loglik = loglik; ia.im.days = days;
-  ia.grad = grad;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  if (gated) hipLaunchKernelGGL(k_imitation_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ia);
-  else hipLaunchKernelGGL(k_imitation_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ia);
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-int w2a_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                                  float *grad, float *loglik, int32_t *days, void *stream) {
-  return imitation_gradient_linear("w2a_imitation_gradient_linear", env, policy, alert_mask, mask_words, env_weight,
-                                   nullptr, 0, n_steps, obs, grad, loglik, days, stream);
-}
-
-int w2a_imitation_gradient_linear_weighted(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                           int32_t mask_words, const float *env_weight, const float *day_weight,
-                                           int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
-                                           float *loglik, int32_t *days, void *stream) {
-  return imitation_gradient_linear("w2a_imitation_gradient_linear_weighted", env, policy, alert_mask, mask_words,
-                                   env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream);
-}
-
-// day_weight nullable (= 1), as w2a_imitation_gradient_linear
-int w2a_imitation_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                        int32_t mask_words, const float *env_weight, const float *day_weight,
-                                        int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
-                                        float *loglik, int32_t *days, void *stream, const uint32_t *allowed_days,
-                                        int32_t allowed_words) {
-  return imitation_gradient_linear("w2a_imitation_gradient_linear_gated", env, policy, alert_mask, mask_words,
-                                   env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
-                                   true, allowed_days, allowed_words);
-}
-
-// the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
-size_t w2a_imitation_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
-                                                  int32_t n_layers) {
-  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
-}
-
-static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy,
-                                  const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
-                                  const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
-                                  float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
-                                  void *stream, bool gated = false, const uint32_t *gate = nullptr,
-                                  int32_t gate_words = 0) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->n_layers != 1 && policy->n_layers != 2)
-    return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
-  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
-  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
-  if (policy->sample != 0 && policy->sample != 1)
-    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
-  const int rc = check_imitation(fn, alert_mask, obs, grad, loglik, days);
-  if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
-  if (day_weight && day_weight_days < n_steps)
-    return fail(W2A_ERR_ARG, "%s: day_weight holds fewer call-days than n_steps", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
-                             "the observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
-  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
-  const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
-  if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_imitation_gradient_mlp_workspace_bytes", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  ImMlpArgs ia;
-  memset(&ia, 0, sizeof(ia));
-  MlpGradArgs &ga = ia.g;
-  MlpRolloutArgs &ma = ga.m;
-  ma.gate = gated ? gate : nullptr;
-  ma.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    ma.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = ma.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.n_steps = n_steps;
-  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the policy's (group-major) or identity
-  a.order = reinterpret_cast<const uint32_t *>(policy->order);
-  ma.params = policy->params;
-  ma.group = policy->group;
-  ma.n_groups = policy->n_groups;
-  ma.stride = (int32_t)stride;
-  ma.activation = policy->activation;
-  ma.n_obs = env->tb.n_obs;
-  ma.obs_mask = obs_mask;
-  ma.obs = const_cast<float *>(obs);  // the kernels only read it
-  char *ws = reinterpret_cast<char *>(workspace);
-  ga.day = reinterpret_cast<float2 *>(ws + L.day);
-  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
-  ga.total = reinterpret_cast<double *>(ws + L.total);
-  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
-  ga.tiles = L.tiles;
-  ga.n_chunks = L.n_chunks;
-  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
-  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
-  ga.capacity = L.capacity;
-  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
-  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
-  ga.partial = reinterpret_cast<double *>(ws + L.partial);
-  ga.grad = grad;
-  ia.im.alert_mask = alert_mask; ia.im.mask_words = mask_words; ia.im.env_weight = env_weight;
-  ia.im.day_weight = day_weight;
-  ia.im.loglik = loglik; ia.im.days = days;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  switch (policy->width * 4 + policy->n_layers) {
-    case 16 * 4 + 1: launch_im<16, 1>(ia, g64, s); break;
-    case 16 * 4 + 2: launch_im<16, 2>(ia, g64, s); break;
-    case 32 * 4 + 1: launch_im<32, 1>(ia, g64, s); break;
-    case 32 * 4 + 2: launch_im<32, 2>(ia, g64, s); break;
-    case 64 * 4 + 1: launch_im<64, 1>(ia, g64, s); break;
-    default: launch_im<64, 2>(ia, g64, s); break;
-  }
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-int w2a_imitation_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                               float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
-                               void *stream) {
-  return imitation_gradient_mlp("w2a_imitation_gradient_mlp", env, policy, alert_mask, mask_words, env_weight, nullptr,
-                                0, n_steps, obs, grad, loglik, days, workspace, workspace_bytes, stream);
-}
-
-int w2a_imitation_gradient_mlp_weighted(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                                        int32_t mask_words, const float *env_weight, const float *day_weight,
-                                        int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
-                                        float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
-                                        void *stream) {
-  return imitation_gradient_mlp("w2a_imitation_gradient_mlp_weighted", env, policy, alert_mask, mask_words, env_weight,
-                                day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
-                                workspace_bytes, stream);
-}
-
-// day_weight nullable (= 1), as w2a_imitation_gradient_mlp
-int w2a_imitation_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                                     int32_t mask_words, const float *env_weight, const float *day_weight,
-                                     int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
-                                     float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
-                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
-  return imitation_gradient_mlp("w2a_imitation_gradient_mlp_gated", env, policy, alert_mask, mask_words, env_weight,
-                                day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
-                                workspace_bytes, stream, true, allowed_days, allowed_words);
-}
-
-// the checks w2a_surrogate_gradient_linear and _mlp share once the policy's own have passed (same order in both)
-static int check_surrogate_outputs(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
-                                   const float *surrogate, const int32_t *clipped_days, const float *approx_kl,
-                                   const float *entropy, const int32_t *days) {
-  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to score)", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!grad || !surrogate || !clipped_days || !approx_kl || !entropy || !days)
-    return fail(W2A_ERR_ARG, "%s: NULL grad, surrogate, clipped_days, approx_kl, entropy or days", fn);
-  return W2A_OK;
-}
-
-// ... and what the surrogate adds to the weighted imitation calls' checks, where they check day_weight_days
-static int check_surrogate_inputs(const char *fn, const float *advantage, int32_t advantage_days,
-                                  const float *old_log_prob, int32_t old_log_prob_days, double clip,
-                                  double entropy_coef, int32_t n_steps) {
-  if (!advantage) return fail(W2A_ERR_ARG, "%s: NULL advantage", fn);
-  if (advantage_days < n_steps) return fail(W2A_ERR_ARG, "%s: advantage holds fewer call-days than n_steps", fn);
-  if (old_log_prob && old_log_prob_days < n_steps)
-    return fail(W2A_ERR_ARG, "%s: old_log_prob holds fewer call-days than n_steps", fn);
-  if (!isfinite(clip) || clip < 0.0) return fail(W2A_ERR_ARG, "%s: clip must be finite and not negative", fn);
-  if (!isfinite(entropy_coef)) return fail(W2A_ERR_ARG, "%s: entropy_coef must be finite", fn);
-  return W2A_OK;
-}
-
-static int surrogate_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy,
-                                     const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
-                                     const float *advantage, int32_t advantage_days, const float *old_log_prob,
-                                     int32_t old_log_prob_days, double clip, double entropy_coef, int32_t n_steps,
-                                     const float *obs, float *grad, float *surrogate, int32_t *clipped_days,
-                                     float *approx_kl, float *entropy, int32_t *days, float *log_prob, void *stream,
-                                     bool gated, const uint32_t *gate, int32_t gate_words) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->weight || !policy->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->sample != 0 && policy->sample != 1)
-    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
-  int rc = check_surrogate_outputs(fn, alert_mask, obs, grad, surrogate, clipped_days, approx_kl, entropy, days);
-  if (rc != W2A_OK) return rc;
-  rc = check_surrogate_inputs(fn, advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps);
-  if (rc != W2A_OK) return rc;
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change "
-                             "what the observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  SgLinearArgs sa;
-  memset(&sa, 0, sizeof(sa));
-  LinearRolloutArgs &la = sa.l;
-  la.gate = gated ? gate : nullptr;
-  la.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    la.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = la.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.n_steps = n_steps;
-  a.order = env->order;
-  la.weight = reinterpret_cast<const float4 *>(policy->weight);
-  la.bias = policy->bias;
-  la.group = policy->group;
-  la.n_groups = policy->n_groups;
-  la.n_obs = env->tb.n_obs;
-  la.obs_mask = obs_mask;
-  la.obs = const_cast<float *>(obs);  // the kernel only reads it
-  sa.sg.alert_mask = alert_mask; sa.sg.mask_words = mask_words; sa.sg.env_weight = env_weight;
-  sa.sg.advantage = advantage; sa.sg.old_log_prob = old_log_prob;
-  sa.sg.lo = 1.0 - clip; sa.sg.hi = 1.0 + clip; sa.sg.beta = entropy_coef;
-  sa.sg.log_prob = log_prob; sa.sg.surrogate = surrogate; sa.sg.clipped = clipped_days; sa.sg.approx_kl = approx_kl;
-  sa.sg.entropy = entropy; sa.sg.days = days;
-  sa.grad = grad;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  if (log_prob) HIP_TRY(hipMemsetAsync(log_prob, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  if (gated) hipLaunchKernelGGL(k_surrogate_linear<true>, dim3(g64), dim3(BLOCK), 0, s, sa);
-  else hipLaunchKernelGGL(k_surrogate_linear<false>, dim3(g64), dim3(BLOCK), 0, s, sa);
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-int w2a_surrogate_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                  int32_t mask_words, const float *env_weight, const float *advantage,
-                                  int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
-                                  double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
-                                  float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
-                                  int32_t *days, float *log_prob, void *stream) {
-  return surrogate_gradient_linear("w2a_surrogate_gradient_linear", env, policy, alert_mask, mask_words, env_weight,
-                                   advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef,
-                                   n_steps, obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob,
-                                   stream, false, nullptr, 0);
-}
-
-int w2a_surrogate_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
-                                        int32_t mask_words, const float *env_weight, const float *advantage,
-                                        int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
-                                        double clip, double entropy_coef, int32_t n_steps, const float *obs,
-                                        float *grad, float *surrogate, int32_t *clipped_days, float *approx_kl,
-                                        float *entropy, int32_t *days, float *log_prob, void *stream,
-                                        const uint32_t *allowed_days, int32_t allowed_words) {
-  return surrogate_gradient_linear("w2a_surrogate_gradient_linear_gated", env, policy, alert_mask, mask_words,
-                                   env_weight, advantage, advantage_days, old_log_prob, old_log_prob_days, clip,
-                                   entropy_coef, n_steps, obs, grad, surrogate, clipped_days, approx_kl, entropy, days,
-                                   log_prob, stream, true, allowed_days, allowed_words);
-}
-
-// the workspace of w2a_imitation_gradient_mlp: the same scratch and partial blocks serve the same second pass
-size_t w2a_surrogate_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
-                                                  int32_t n_layers) {
-  return w2a_imitation_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
-}
-
-static int surrogate_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy,
-                                  const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
-                                  const float *advantage, int32_t advantage_days, const float *old_log_prob,
-                                  int32_t old_log_prob_days, double clip, double entropy_coef, int32_t n_steps,
-                                  const float *obs, float *grad, float *surrogate, int32_t *clipped_days,
-                                  float *approx_kl, float *entropy, int32_t *days, float *log_prob, void *workspace,
-                                  size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate,
-                                  int32_t gate_words) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
-  if (!policy) return fail(W2A_ERR_ARG, "%s: NULL policy", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!policy->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
-  if (policy->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (policy->n_layers != 1 && policy->n_layers != 2)
-    return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
-  if (policy->width != 16 && policy->width != 32 && policy->width != 64)
-    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
-  if (policy->activation != W2A_MLP_TANH && policy->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
-  if (policy->sample != 0 && policy->sample != 1)
-    return fail(W2A_ERR_ARG, "%s: sample must be 0 or 1", fn);
-  if (policy->require_budget != 0 && policy->require_budget != 1)
-    return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
-  if ((uintptr_t)policy->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
-  int rc = check_surrogate_outputs(fn, alert_mask, obs, grad, surrogate, clipped_days, approx_kl, entropy, days);
-  if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
-  rc = check_surrogate_inputs(fn, advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps);
-  if (rc != W2A_OK) return rc;
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what "
-                             "the observation is)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  const int64_t stride = W2A_MLP_STRIDE((int64_t)policy->width, policy->n_layers);
-  if ((int64_t)policy->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
-  const PgmLayout L = pgm_layout(env->n, n_steps, policy->n_groups, policy->width, policy->n_layers);
-  if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_surrogate_gradient_mlp_workspace_bytes", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
-  SgMlpArgs sa;
-  memset(&sa, 0, sizeof(sa));
-  MlpGradArgs &ga = sa.g;
-  MlpRolloutArgs &ma = ga.m;
-  ma.gate = gated ? gate : nullptr;
-  ma.gate_words = gated ? gate_words : 0;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    ma.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = ma.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.pol.require_budget = policy->require_budget;
-  a.n_steps = n_steps;
-  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the policy's (group-major) or identity
-  a.order = reinterpret_cast<const uint32_t *>(policy->order);
-  ma.params = policy->params;
-  ma.group = policy->group;
-  ma.n_groups = policy->n_groups;
-  ma.stride = (int32_t)stride;
-  ma.activation = policy->activation;
-  ma.n_obs = env->tb.n_obs;
-  ma.obs_mask = obs_mask;
-  ma.obs = const_cast<float *>(obs);  // the kernels only read it
-  char *ws = reinterpret_cast<char *>(workspace);
-  ga.day = reinterpret_cast<float2 *>(ws + L.day);
-  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
-  ga.total = reinterpret_cast<double *>(ws + L.total);
-  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
-  ga.tiles = L.tiles;
-  ga.n_chunks = L.n_chunks;
-  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
-  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
-  ga.capacity = L.capacity;
-  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
-  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
-  ga.partial = reinterpret_cast<double *>(ws + L.partial);
-  ga.grad = grad;
-  sa.sg.alert_mask = alert_mask; sa.sg.mask_words = mask_words; sa.sg.env_weight = env_weight;
-  sa.sg.advantage = advantage; sa.sg.old_log_prob = old_log_prob;
-  sa.sg.lo = 1.0 - clip; sa.sg.hi = 1.0 + clip; sa.sg.beta = entropy_coef;
-  sa.sg.log_prob = log_prob; sa.sg.surrogate = surrogate; sa.sg.clipped = clipped_days; sa.sg.approx_kl = approx_kl;
-  sa.sg.entropy = entropy; sa.sg.days = days;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  if (log_prob) HIP_TRY(hipMemsetAsync(log_prob, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  switch (policy->width * 4 + policy->n_layers) {
-    case 16 * 4 + 1: launch_sg<16, 1>(sa, g64, s); break;
-    case 16 * 4 + 2: launch_sg<16, 2>(sa, g64, s); break;
-    case 32 * 4 + 1: launch_sg<32, 1>(sa, g64, s); break;
-    case 32 * 4 + 2: launch_sg<32, 2>(sa, g64, s); break;
-    case 64 * 4 + 1: launch_sg<64, 1>(sa, g64, s); break;
-    default: launch_sg<64, 2>(sa, g64, s); break;
-  }
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-int w2a_surrogate_gradient_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                               int32_t mask_words, const float *env_weight, const float *advantage,
-                               int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
-                               double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
-                               float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
-                               int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes, void *stream) {
-  return surrogate_gradient_mlp("w2a_surrogate_gradient_mlp", env, policy, alert_mask, mask_words, env_weight,
-                                advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps,
-                                obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob, workspace,
-                                workspace_bytes, stream, false, nullptr, 0);
-}
-
-int w2a_surrogate_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
-                                     int32_t mask_words, const float *env_weight, const float *advantage,
-                                     int32_t advantage_days, const float *old_log_prob, int32_t old_log_prob_days,
-                                     double clip, double entropy_coef, int32_t n_steps, const float *obs, float *grad,
-                                     float *surrogate, int32_t *clipped_days, float *approx_kl, float *entropy,
-                                     int32_t *days, float *log_prob, void *workspace, size_t workspace_bytes,
-                                     void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
-  return surrogate_gradient_mlp("w2a_surrogate_gradient_mlp_gated", env, policy, alert_mask, mask_words, env_weight,
-                                advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps,
-                                obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob, workspace,
-                                workspace_bytes, stream, true, allowed_days, allowed_words);
-}
-
-// the checks w2a_value_gradient_linear and _mlp share once the network's own have passed (same order in both)
-static int check_value(const char *fn, const uint32_t *alert_mask, const float *obs, const void *grad,
-                       const float *sq_error, const int32_t *days, const float *ret) {
-  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to follow)", fn);
-  if (!obs) return fail(W2A_ERR_ARG, "%s: NULL obs (the rows the agent holds are the first day's input)", fn);
-  if (!grad || !sq_error || !days || !ret) return fail(W2A_ERR_ARG, "%s: NULL grad, sq_error, days or ret", fn);
-  return W2A_OK;
-}
-
-// scratch of w2a_value_gradient_linear: y_s (fp64) and the alert issued, per (call-day, env) -- 9 B, as the policy gradient's
-size_t w2a_value_gradient_linear_workspace_bytes(int64_t num_envs, int32_t n_steps) {
-  return w2a_policy_gradient_workspace_bytes(num_envs, n_steps);
-}
-
-int w2a_value_gradient_linear(w2a_env *env, const w2a_linear_policy *value, const uint32_t *alert_mask,
-                              int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                              float *grad, float *sq_error, int32_t *days, float *ret, float *advantage,
-                              void *workspace, size_t workspace_bytes, void *stream) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_linear's checks
-  if (!value) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL value");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: n_steps must be positive");
-  if (!value->weight || !value->bias) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL weight or bias");
-  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: n_groups must be positive");
-  if ((uintptr_t)value->weight & 15) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: weight must be 16-B aligned");
-  const int rc = check_value("w2a_value_gradient_linear", alert_mask, obs, grad, sq_error, days, ret);
-  if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL workspace");
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: workspace must be 256-B aligned");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: NULL handle");
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: alert_mask needs ceil(T/32) words per env");
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: not available with corrected-semantics flags (they change what "
-                             "the observation and the reward are)");
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
-  if (workspace_bytes < w2a_value_gradient_linear_workspace_bytes(env->n, n_steps))
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_linear: workspace smaller than w2a_value_gradient_linear_workspace_bytes");
-  REFUSE_WHILE_CAPTURING("w2a_value_gradient_linear", stream);
-  VgLinearArgs va;
-  memset(&va, 0, sizeof(va));
-  LinearRolloutArgs &la = va.l;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_value_gradient_linear: an observation column sits on slot 30 or 31 of the feature row");
-    obs_mask |= 1u << sl;
-    la.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = la.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.n_steps = n_steps;
-  a.order = env->order;
-  la.weight = reinterpret_cast<const float4 *>(value->weight);
-  la.bias = value->bias;
-  la.group = value->group;
-  la.n_groups = value->n_groups;
-  la.n_obs = env->tb.n_obs;
-  la.obs_mask = obs_mask;
-  la.obs = const_cast<float *>(obs);  // the kernel only reads it
-  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
-  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
-  va.day_y = reinterpret_cast<double *>(workspace);
-  va.day_alert = reinterpret_cast<uint8_t *>(workspace) + align256(sizeof(double) * (size_t)env->n * (size_t)n_steps);
-  va.grad = grad;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, "w2a_value_gradient_linear")) return W2A_ERR_STATE;
-  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  hipLaunchKernelGGL(k_value_gradient_linear, dim3(g64), dim3(BLOCK), 0, s, va);
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-// the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
-size_t w2a_value_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
-                                              int32_t n_layers) {
-  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
-}
-
-int w2a_value_gradient_mlp(w2a_env *env, const w2a_mlp_policy *value, const uint32_t *alert_mask, int32_t mask_words,
-                           const float *env_weight, int32_t n_steps, const float *obs, float *grad, float *sq_error,
-                           int32_t *days, float *ret, float *advantage, void *workspace, size_t workspace_bytes,
-                           void *stream) {
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_rollout_mlp's checks
-  if (!value) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL value");
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_steps must be positive");
-  if (!value->params) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL params");
-  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_groups must be positive");
-  if (value->n_layers != 1 && value->n_layers != 2)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_layers must be 1 or 2");
-  if (value->width != 16 && value->width != 32 && value->width != 64)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: width must be 16, 32 or 64");
-  if (value->activation != W2A_MLP_TANH && value->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: activation must be W2A_MLP_TANH or W2A_MLP_RELU");
-  if ((uintptr_t)value->params & 15) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: params must be 16-B aligned");
-  const int rc = check_value("w2a_value_gradient_mlp", alert_mask, obs, grad, sq_error, days, ret);
-  if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL workspace");
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: workspace must be 256-B aligned");
-  if (!env) return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: NULL handle");
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: alert_mask needs ceil(T/32) words per env");
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: not available with corrected-semantics flags (they change what "
-                             "the observation and the reward are)");
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)");
-  const int64_t stride = W2A_MLP_STRIDE((int64_t)value->width, value->n_layers);
-  if ((int64_t)value->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: n_groups * block size must stay below 2^31 floats");
-  const PgmLayout L = pgm_layout(env->n, n_steps, value->n_groups, value->width, value->n_layers);
-  if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "w2a_value_gradient_mlp: workspace smaller than w2a_value_gradient_mlp_workspace_bytes");
-  REFUSE_WHILE_CAPTURING("w2a_value_gradient_mlp", stream);
-  VgMlpArgs va;
-  memset(&va, 0, sizeof(va));
-  MlpGradArgs &ga = va.g;
-  MlpRolloutArgs &ma = ga.m;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "w2a_value_gradient_mlp: an observation column sits on slot 30 or 31 of the feature row");
-    obs_mask |= 1u << sl;
-    ma.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = ma.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.n_steps = n_steps;
-  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the network's (group-major) or identity
-  a.order = reinterpret_cast<const uint32_t *>(value->order);
-  ma.params = value->params;
-  ma.group = value->group;
-  ma.n_groups = value->n_groups;
-  ma.stride = (int32_t)stride;
-  ma.activation = value->activation;
-  ma.n_obs = env->tb.n_obs;
-  ma.obs_mask = obs_mask;
-  ma.obs = const_cast<float *>(obs);  // the kernels only read it
-  char *ws = reinterpret_cast<char *>(workspace);
-  ga.day = reinterpret_cast<float2 *>(ws + L.day);
-  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
-  ga.total = reinterpret_cast<double *>(ws + L.total);
-  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
-  ga.tiles = L.tiles;
-  ga.n_chunks = L.n_chunks;
-  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
-  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
-  ga.capacity = L.capacity;
-  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
-  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
-  ga.partial = reinterpret_cast<double *>(ws + L.partial);
-  ga.grad = grad;
-  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
-  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, "w2a_value_gradient_mlp")) return W2A_ERR_STATE;
-  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, sizeof(float) * (size_t)env->n * (size_t)n_steps, s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  switch (value->width * 4 + value->n_layers) {
-    case 16 * 4 + 1: launch_vg<16, 1>(va, g64, s); break;
-    case 16 * 4 + 2: launch_vg<16, 2>(va, g64, s); break;
-    case 32 * 4 + 1: launch_vg<32, 1>(va, g64, s); break;
-    case 32 * 4 + 2: launch_vg<32, 2>(va, g64, s); break;
-    case 64 * 4 + 1: launch_vg<64, 1>(va, g64, s); break;
-    default: launch_vg<64, 2>(va, g64, s); break;
-  }
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-// what w2a_value_gradient_linear_gae and _mlp_gae check beyond check_value (same order in both)
-static int check_gae(const char *fn, double gamma, double lambda, int32_t bootstrap, const float *advantage,
-                     const float *value_target, const float *target, int32_t target_days, int32_t n_steps) {
-  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(W2A_ERR_ARG, "%s: gamma must lie in [0, 1]", fn);
-  if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(W2A_ERR_ARG, "%s: lambda must lie in [0, 1]", fn);
-  if (bootstrap != 0 && bootstrap != 1) return fail(W2A_ERR_ARG, "%s: bootstrap must be 0 or 1", fn);
-  if (target) {
-    if (target_days < n_steps) return fail(W2A_ERR_ARG, "%s: target holds fewer call-days than n_steps", fn);
-    if (advantage || value_target)
-      return fail(W2A_ERR_ARG, "%s: advantage and value_target are not formed when target is given", fn);
-    if (gamma != 1.0 || lambda != 1.0 || bootstrap)
-      return fail(W2A_ERR_ARG, "%s: gamma, lambda and bootstrap have no meaning when target is given", fn);
-  }
-  return W2A_OK;
-}
-
-// scratch of w2a_value_gradient_linear_gae: delta_s / c_s and V_s (fp64) and the alert issued, per (call-day, env) -- 17 B
-size_t w2a_value_gradient_linear_gae_workspace_bytes(int64_t num_envs, int32_t n_steps) {
-  if (num_envs <= 0 || n_steps <= 0) return 0;
-  const size_t days = (size_t)num_envs * (size_t)n_steps;
-  return 2 * align256(sizeof(double) * days) + align256(days);
-}
-
-int w2a_value_gradient_linear_gae(w2a_env *env, const w2a_linear_policy *value, const uint32_t *alert_mask,
-                                  int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                                  float *grad, float *sq_error, int32_t *days, float *ret, float *advantage,
-                                  double gamma, double lambda, int32_t bootstrap, float *value_target,
-                                  const float *target, int32_t target_days, void *workspace, size_t workspace_bytes,
-                                  void *stream) {
-  const char *fn = "w2a_value_gradient_linear_gae";
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_value_gradient_linear's checks
-  if (!value) return fail(W2A_ERR_ARG, "%s: NULL value", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!value->weight || !value->bias) return fail(W2A_ERR_ARG, "%s: NULL weight or bias", fn);
-  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if ((uintptr_t)value->weight & 15) return fail(W2A_ERR_ARG, "%s: weight must be 16-B aligned", fn);
-  int rc = check_value(fn, alert_mask, obs, grad, sq_error, days, ret);
-  if (rc != W2A_OK) return rc;
-  rc = check_gae(fn, gamma, lambda, bootstrap, advantage, value_target, target, target_days, n_steps);
-  if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T) return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the observation and "
-                             "the reward are)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  if (workspace_bytes < w2a_value_gradient_linear_gae_workspace_bytes(env->n, n_steps))
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_value_gradient_linear_gae_workspace_bytes", fn);
-  REFUSE_WHILE_CAPTURING("w2a_value_gradient_linear_gae", stream);
-  GaeLinearArgs xa;
-  memset(&xa, 0, sizeof(xa));
-  VgLinearArgs &va = xa.v;
-  LinearRolloutArgs &la = va.l;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) la.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    la.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = la.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.n_steps = n_steps;
-  a.order = env->order;
-  la.weight = reinterpret_cast<const float4 *>(value->weight);
-  la.bias = value->bias;
-  la.group = value->group;
-  la.n_groups = value->n_groups;
-  la.n_obs = env->tb.n_obs;
-  la.obs_mask = obs_mask;
-  la.obs = const_cast<float *>(obs);  // the kernel only reads it
-  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
-  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
-  const size_t col = align256(sizeof(double) * (size_t)env->n * (size_t)n_steps);
-  va.day_y = reinterpret_cast<double *>(workspace);
-  xa.day_v = reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + col);
-  va.day_alert = reinterpret_cast<uint8_t *>(workspace) + 2 * col;
-  va.grad = grad;
-  xa.g.gamma = gamma; xa.g.gl = gamma * lambda; xa.g.bootstrap = bootstrap;
-  xa.g.value_target = value_target; xa.g.target = target;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  const size_t rows = sizeof(float) * (size_t)env->n * (size_t)n_steps;
-  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, rows, s));
-  if (value_target) HIP_TRY(hipMemsetAsync(value_target, 0, rows, s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  if (target) hipLaunchKernelGGL(k_value_gradient_linear_gae<true>, dim3(g64), dim3(BLOCK), 0, s, xa);
-  else hipLaunchKernelGGL(k_value_gradient_linear_gae<false>, dim3(g64), dim3(BLOCK), 0, s, xa);
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
-
-// the workspace of w2a_policy_gradient_mlp: the same scratch and partial blocks serve the same second pass
-size_t w2a_value_gradient_mlp_gae_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
-                                                  int32_t n_layers) {
-  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
-}
-
-int w2a_value_gradient_mlp_gae(w2a_env *env, const w2a_mlp_policy *value, const uint32_t *alert_mask,
-                               int32_t mask_words, const float *env_weight, int32_t n_steps, const float *obs,
-                               float *grad, float *sq_error, int32_t *days, float *ret, float *advantage, double gamma,
-                               double lambda, int32_t bootstrap, float *value_target, const float *target,
-                               int32_t target_days, void *workspace, size_t workspace_bytes, void *stream) {
-  const char *fn = "w2a_value_gradient_mlp_gae";
-  // what can be checked without the handle first (so that it is checked on any machine): w2a_value_gradient_mlp's checks
-  if (!value) return fail(W2A_ERR_ARG, "%s: NULL value", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (!value->params) return fail(W2A_ERR_ARG, "%s: NULL params", fn);
-  if (value->n_groups <= 0) return fail(W2A_ERR_ARG, "%s: n_groups must be positive", fn);
-  if (value->n_layers != 1 && value->n_layers != 2) return fail(W2A_ERR_ARG, "%s: n_layers must be 1 or 2", fn);
-  if (value->width != 16 && value->width != 32 && value->width != 64)
-    return fail(W2A_ERR_ARG, "%s: width must be 16, 32 or 64", fn);
-  if (value->activation != W2A_MLP_TANH && value->activation != W2A_MLP_RELU)
-    return fail(W2A_ERR_ARG, "%s: activation must be W2A_MLP_TANH or W2A_MLP_RELU", fn);
-  if ((uintptr_t)value->params & 15) return fail(W2A_ERR_ARG, "%s: params must be 16-B aligned", fn);
-  int rc = check_value(fn, alert_mask, obs, grad, sq_error, days, ret);
-  if (rc != W2A_OK) return rc;
-  rc = check_gae(fn, gamma, lambda, bootstrap, advantage, value_target, target, target_days, n_steps);
-  if (rc != W2A_OK) return rc;
-  if (!workspace) return fail(W2A_ERR_ARG, "%s: NULL workspace", fn);
-  if ((uintptr_t)workspace & 255) return fail(W2A_ERR_ARG, "%s: workspace must be 256-B aligned", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T) return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (they change what the observation and "
-                             "the reward are)", fn);
-  if (env->n * (int64_t)env->tb.n_obs >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: num_envs * n_obs must stay below 2^31 (32-bit observation offsets)", fn);
-  const int64_t stride = W2A_MLP_STRIDE((int64_t)value->width, value->n_layers);
-  if ((int64_t)value->n_groups * stride >= (1ll << 31))
-    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
-  const PgmLayout L = pgm_layout(env->n, n_steps, value->n_groups, value->width, value->n_layers);
-  if (workspace_bytes < L.bytes)
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_value_gradient_mlp_gae_workspace_bytes", fn);
-  REFUSE_WHILE_CAPTURING("w2a_value_gradient_mlp_gae", stream);
-  GaeMlpArgs xa;
-  memset(&xa, 0, sizeof(xa));
-  VgMlpArgs &va = xa.v;
-  MlpGradArgs &ga = va.g;
-  MlpRolloutArgs &ma = ga.m;
-  uint32_t obs_mask = 0;
-  for (int k = 0; k < RO64_SLOTS; ++k) ma.slot_obs[k] = -1;
-  for (int j = 0; j < env->tb.n_obs; ++j) {
-    const int sl = env->obs_slot_host[j];
-    if (sl < 0 || sl >= RO64_SLOTS)
-      return fail(W2A_ERR_SCHEMA, "%s: an observation column sits on slot 30 or 31 of the feature row", fn);
-    obs_mask |= 1u << sl;
-    ma.slot_obs[sl] = (int8_t)j;
-  }
-  RolloutArgs &a = ma.r;
-  a.tb = env->tb; a.st = env->st; a.status = env->status; a.n = env->n; a.gid0 = env->gid0;
-  a.n_steps = n_steps;
-  // as w2a_policy_gradient_mlp: the kernels write no state, so the visiting order is the network's (group-major) or identity
-  a.order = reinterpret_cast<const uint32_t *>(value->order);
-  ma.params = value->params;
-  ma.group = value->group;
-  ma.n_groups = value->n_groups;
-  ma.stride = (int32_t)stride;
-  ma.activation = value->activation;
-  ma.n_obs = env->tb.n_obs;
-  ma.obs_mask = obs_mask;
-  ma.obs = const_cast<float *>(obs);  // the kernels only read it
-  char *ws = reinterpret_cast<char *>(workspace);
-  ga.day = reinterpret_cast<float2 *>(ws + L.day);
-  ga.day_alert = reinterpret_cast<uint8_t *>(ws + L.day_alert);
-  ga.total = reinterpret_cast<double *>(ws + L.total);
-  ga.n_valid = reinterpret_cast<int32_t *>(ws + L.n_valid);
-  ga.tiles = L.tiles;
-  ga.n_chunks = L.n_chunks;
-  ga.chunk_count = reinterpret_cast<uint32_t *>(ws + L.chunk_count);
-  ga.chunk_base = reinterpret_cast<uint32_t *>(ws + L.chunk_base);
-  ga.capacity = L.capacity;
-  ga.tag = reinterpret_cast<int32_t *>(ws + L.tag);
-  ga.pcount = reinterpret_cast<uint32_t *>(ws + L.pcount);
-  ga.partial = reinterpret_cast<double *>(ws + L.partial);
-  ga.grad = grad;
-  va.v.alert_mask = alert_mask; va.v.mask_words = mask_words; va.v.env_weight = env_weight;
-  va.v.sq_error = sq_error; va.v.days = days; va.v.ret = ret; va.v.advantage = advantage;
-  xa.g.gamma = gamma; xa.g.gl = gamma * lambda; xa.g.bootstrap = bootstrap;
-  xa.g.value_target = value_target; xa.g.target = target;
-  hipStream_t s = (hipStream_t)stream;
-  // reads the canonical state words; changes nothing else
-  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
-  const size_t rows = sizeof(float) * (size_t)env->n * (size_t)n_steps;
-  if (advantage) HIP_TRY(hipMemsetAsync(advantage, 0, rows, s));
-  if (value_target) HIP_TRY(hipMemsetAsync(value_target, 0, rows, s));
-  const unsigned g64 = (unsigned)((((env->n + BLOCK - 1) / BLOCK) + 7) / 8 * 8);
-  switch (value->width * 4 + value->n_layers) {
-    case 16 * 4 + 1: launch_gae<16, 1>(xa, g64, s); break;
-    case 16 * 4 + 2: launch_gae<16, 2>(xa, g64, s); break;
-    case 32 * 4 + 1: launch_gae<32, 1>(xa, g64, s); break;
-    case 32 * 4 + 2: launch_gae<32, 2>(xa, g64, s); break;
-    case 64 * 4 + 1: launch_gae<64, 1>(xa, g64, s); break;
-    default: launch_gae<64, 2>(xa, g64, s); break;
-  }
-  HIP_TRY(hipGetLastError());
-  end_call(env, s);
-  return W2A_OK;
-}
+// the learned-policy entry points (w2a_rollout_linear / _mlp, the policy, imitation, surrogate and value gradients, GAE)
+#include "w2a_policy_dispatch.hip.h"
 
 int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint32_t *alert_mask, int32_t mask_words,
                           int32_t n_steps, float *out, void *stream) {
