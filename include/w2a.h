@@ -964,6 +964,57 @@ int w2a_hindsight_optimum_gated(w2a_env *env, const w2a_state_view *start, int32
                                 size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
                                 int32_t allowed_words);
 
+/* Fisher-vector products of a policy along a GIVEN alert schedule: the primitive of the natural policy gradient and of
+ * TRPO's conjugate-gradient step, over the episodes at hand and with no observation row recorded. Every env is forced
+ * along its own schedule from the handle's CURRENT state and observation rows exactly as in
+ * w2a_surrogate_gradient_linear: the same alert_mask, the same attempted-versus-issued rule, the same o_s and the same
+ * m_s (a day on which require_budget forces the action, or which allowed_days closes, is not scored). The state, the
+ * tables, the schedule, obs and the vector are only read, as there.
+ * The Fisher information of one Bernoulli decision with logit z_s and p_s = sigmoid(z_s) is p_s (1 - p_s) J_s^T J_s,
+ * J_s = dz_s/dtheta. For env e of group g, with v_g that group's block of the vector:
+ *   u_s   = J_s . v_g                                   (linear: vec_weight[g] . o_s + vec_bias[g])
+ *   Fv_e  = w_e sum_s m_s p_s (1 - p_s) u_s J_s^T        (linear: J_s = (o_s, 1)); w_e = env_weight[e] (NULL: 1)
+ *   q_e   = sum_s m_s p_s (1 - p_s) u_s^2                (unweighted)
+ * The mean of Fv_e over a group's envs is F_g v_g, and the mean of w_e q_e is <v_g, F_g v_g>: 1/2 eps^2 of it is the
+ * second-order term of the group's mean w_e sum_s KL(pi_theta || pi_{theta + eps v}). The schedule's labels enter only
+ * through the states visited.
+ *   vec_weight, vec_bias   device f32 [n_groups][32] (16-B aligned, slot order as policy->weight) and [n_groups]: read
+ *                          with the policy's clamped group id, never outside these bounds
+ *   fv          device f32 [n_obs + 1][num_envs], column-major as w2a_surrogate_gradient_linear's grad: Fv_e
+ *   quadratic   f32 [num_envs]: q_e;   days  i32 [num_envs]: sum_s m_s, as w2a_surrogate_gradient_linear
+ *   allowed_days, allowed_words   nullable gate, as the *_gated entry points take it (NULL: every day is allowed and
+ *                          allowed_words is not read)
+ * Numerics contract: z_s and u_s are two fp64 FMA chains in the slot order of k_rollout_linear; p_s and 1 - p_s are
+ * formed in fp64 from exp(-|z_s|) without cancellation; the coefficient, its products with o_s and every sum over s are
+ * fp64; Fv_e and q_e are rounded to f32 once. No scratch memory, no atomics: identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_surrogate_gradient_linear refuses its policy, then for a NULL or misaligned vector, a NULL
+ * alert_mask, obs or output, then as that call for the handle and the gate; W2A_ERR_STATE while `stream` is recording a
+ * hipGraph. */
+int w2a_fisher_vector_product_linear(w2a_env *env, const w2a_linear_policy *policy, const float *vec_weight,
+                                     const float *vec_bias, const uint32_t *alert_mask, int32_t mask_words,
+                                     const float *env_weight, int32_t n_steps, const float *obs, float *fv,
+                                     float *quadratic, int32_t *days, void *stream, const uint32_t *allowed_days,
+                                     int32_t allowed_words);
+/* The same product for an MLP policy, already reduced per group: fv[g] = (1 / N_g) sum over the envs of group g of Fv_e,
+ * a block in the layout of policy->params (a group without envs gives a block of NaN; envs finished on entry contribute
+ * zero and count). `vector` is device f32 [n_groups][W2A_MLP_STRIDE(width, n_layers)], 16-B aligned, in the packed
+ * layout and stride of policy->params, padding zero. u_s is the forward-mode tangent of the f32 network along v_g,
+ * computed on the matrix cores next to the logit: adot_1 = V1 x + vb1, hdot_1 = act'(h_1) adot_1,
+ * adot_2 = W2 hdot_1 + V2 h_1 + vb2, u = w_o . hdot + v_o . h + vb_o, with act' taken from the activation's value as in the
+ * backward pass (tanh: 1 - h^2; ReLU: 1 where h > 0, 0 at exactly 0).
+ * Numerics contract: z_s is the f32 logit of k_rollout_mlp, bit for bit; u_s is f32 (k-ordered fmaf chains, the bias
+ * first); p_s, 1 - p_s, c_s = w_e p_s (1 - p_s) u_s and q_e are fp64 and c_s is rounded to f32 once; from there on the
+ * second pass, the fp64 sums over tiles and the reduction are the kernels of w2a_policy_gradient_mlp, run unchanged
+ * (day = (c_s, 0), total = 1). No atomics: two identical calls give identical bits. The workspace is that of
+ * w2a_policy_gradient_mlp. */
+size_t w2a_fisher_vector_product_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                     int32_t n_layers);
+int w2a_fisher_vector_product_mlp(w2a_env *env, const w2a_mlp_policy *policy, const float *vector,
+                                  const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                                  int32_t n_steps, const float *obs, float *fv, float *quadratic, int32_t *days,
+                                  void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                                  int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ SYMBOLS = [
     "w2a_imitation_gradient_linear_gated", "w2a_surrogate_gradient_linear_gated", "w2a_hindsight_optimum_gated",
     "w2a_rollout_mlp_gated", "w2a_policy_gradient_mlp_gated", "w2a_imitation_gradient_mlp_gated",
     "w2a_surrogate_gradient_mlp_gated",
+    "w2a_fisher_vector_product_linear", "w2a_fisher_vector_product_mlp_workspace_bytes",
+    "w2a_fisher_vector_product_mlp",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
@@ -261,6 +263,16 @@ def load(build_if_missing: bool = True):
     lib.w2a_surrogate_gradient_mlp_gated.argtypes = lib.w2a_surrogate_gradient_mlp.argtypes + gate
     lib.w2a_hindsight_optimum_gated.restype = C.c_int
     lib.w2a_hindsight_optimum_gated.argtypes = lib.w2a_hindsight_optimum.argtypes + gate
+    # Fisher-vector products: the policy, the vector, the schedule, env_weight, n_steps, obs, the outputs, [the
+    # workspace,] the stream and the nullable gate
+    lib.w2a_fisher_vector_product_linear.restype = C.c_int
+    lib.w2a_fisher_vector_product_linear.argtypes = [vp, C.POINTER(LinearPolicy), vp, vp, vp, i32, vp, i32, vp, vp, vp,
+                                                     vp, vp] + gate
+    lib.w2a_fisher_vector_product_mlp_workspace_bytes.restype = C.c_size_t
+    lib.w2a_fisher_vector_product_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.w2a_fisher_vector_product_mlp.restype = C.c_int
+    lib.w2a_fisher_vector_product_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, vp, i32, vp, i32, vp, vp, vp, vp, vp,
+                                                  C.c_size_t, vp] + gate
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     if lib.w2a_abi_version() != ABI_VERSION:

@@ -58,6 +58,7 @@
 #include "w2a_policy_gradient_mlp.hip.h"
 #include "w2a_imitation.hip.h"
 #include "w2a_surrogate.hip.h"
+#include "w2a_fisher.hip.h"
 #include "w2a_value.hip.h"
 #include "w2a_gae.hip.h"
 #include "w2a_hindsight.hip.h"

@@ -2,7 +2,8 @@
 // imitation, surrogate and value gradients and GAE, with their _record, _gated and _weighted forms. Part of libw2a.so;
 // included only by w2a_kernels.hip inside its extern "C" block. No device code lives here.
 //
-// Twelve bodies serve those exports. What they share is written once, in the helpers of the first half of this file:
+// Twelve bodies serve those exports, and two more the Fisher-vector products (w2a_fisher_vector_product_linear / _mlp,
+// which take their nullable gate directly). What they share is written once, in the helpers of the first half of this file:
 //   check_linear_policy_struct / check_mlp_policy_struct   the checks of the policy struct (and n_steps): need no handle
 //   check_handle_common      NULL handle, the schedule's word count, corrected-semantics flags, 2^31 observation offsets
 //   check_mlp_stride / check_mlp_workspace                 2^31 floats of parameters; the PgmLayout workspace's size
@@ -904,6 +905,93 @@ int w2a_surrogate_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy,
                                 advantage, advantage_days, old_log_prob, old_log_prob_days, clip, entropy_coef, n_steps,
                                 obs, grad, surrogate, clipped_days, approx_kl, entropy, days, log_prob, workspace,
                                 workspace_bytes, stream, true, allowed_days, allowed_words);
+}
+
+// ---- Fisher-vector products: read the canonical state words, change nothing else -------------------------------------
+// New exports take the nullable gate directly (NULL: no gate, allowed_words is not read), so there are no _gated twins.
+static int check_fisher_outputs(const char *fn, const uint32_t *alert_mask, const float *obs, const void *fv,
+                                const float *quadratic, const int32_t *days) {
+  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to follow)", fn);
+  W2A_CHECK(check_obs(fn, obs));
+  if (!fv || !quadratic || !days) return fail(W2A_ERR_ARG, "%s: NULL fv, quadratic or days", fn);
+  return W2A_OK;
+}
+
+static void fill_fisher(FisherArgs &f, const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                        float *quadratic, int32_t *days) {
+  f.alert_mask = alert_mask; f.mask_words = mask_words; f.env_weight = env_weight;
+  f.quadratic = quadratic; f.days = days;
+}
+
+size_t w2a_fisher_vector_product_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                                     int32_t n_layers) {
+  return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
+}
+
+int w2a_fisher_vector_product_linear(w2a_env *env, const w2a_linear_policy *policy, const float *vec_weight,
+                                     const float *vec_bias, const uint32_t *alert_mask, int32_t mask_words,
+                                     const float *env_weight, int32_t n_steps, const float *obs, float *fv,
+                                     float *quadratic, int32_t *days, void *stream, const uint32_t *allowed_days,
+                                     int32_t allowed_words) {
+  const char *fn = "w2a_fisher_vector_product_linear";
+  W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
+  if (!vec_weight || !vec_bias) return fail(W2A_ERR_ARG, "%s: NULL vec_weight or vec_bias", fn);
+  if ((uintptr_t)vec_weight & 15) return fail(W2A_ERR_ARG, "%s: vec_weight must be 16-B aligned", fn);
+  W2A_CHECK(check_fisher_outputs(fn, alert_mask, obs, fv, quadratic, days));
+  W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_SCHEDULE, mask_words));
+  if (allowed_days) W2A_CHECK(check_gate(fn, env, allowed_days, allowed_words));
+  W2A_CHECK(refuse_while_capturing(fn, stream));
+  FvLinearArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, allowed_days, allowed_days ? allowed_words : 0, fa.l));
+  fa.l.r.pol.require_budget = policy->require_budget;
+  fa.l.r.order = env->order;
+  fill_fisher(fa.fv, alert_mask, mask_words, env_weight, quadratic, days);
+  fa.vec_weight = reinterpret_cast<const float4 *>(vec_weight);
+  fa.vec_bias = vec_bias;
+  fa.grad = fv;
+  hipStream_t s = (hipStream_t)stream;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  const unsigned g64 = grid64(env);
+  if (allowed_days) hipLaunchKernelGGL(k_fisher_linear<true>, dim3(g64), dim3(BLOCK), 0, s, fa);
+  else hipLaunchKernelGGL(k_fisher_linear<false>, dim3(g64), dim3(BLOCK), 0, s, fa);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+int w2a_fisher_vector_product_mlp(w2a_env *env, const w2a_mlp_policy *policy, const float *vector,
+                                  const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
+                                  int32_t n_steps, const float *obs, float *fv, float *quadratic, int32_t *days,
+                                  void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                                  int32_t allowed_words) {
+  const char *fn = "w2a_fisher_vector_product_mlp";
+  W2A_CHECK(check_mlp_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
+  if (!vector) return fail(W2A_ERR_ARG, "%s: NULL vector", fn);
+  if ((uintptr_t)vector & 15) return fail(W2A_ERR_ARG, "%s: vector must be 16-B aligned", fn);
+  W2A_CHECK(check_fisher_outputs(fn, alert_mask, obs, fv, quadratic, days));
+  W2A_CHECK(check_workspace_pointer(fn, workspace));
+  W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_SCHEDULE, mask_words));
+  PgmLayout L;
+  W2A_CHECK(check_mlp_workspace(fn, env, policy, n_steps, workspace_bytes,
+                                "%s: workspace smaller than w2a_fisher_vector_product_mlp_workspace_bytes", L));
+  if (allowed_days) W2A_CHECK(check_gate(fn, env, allowed_days, allowed_words));
+  W2A_CHECK(refuse_while_capturing(fn, stream));
+  FvMlpArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  W2A_CHECK(fill_mlp(fn, env, policy, n_steps, obs, allowed_days, allowed_days ? allowed_words : 0, fa.g.m));
+  fa.g.m.r.pol.require_budget = policy->require_budget;
+  fa.g.m.r.order = mlp_own_order(policy);
+  bind_pgm_workspace(fa.g, L, workspace, fv);
+  fill_fisher(fa.fv, alert_mask, mask_words, env_weight, quadratic, days);
+  fa.vec = vector;
+  hipStream_t s = (hipStream_t)stream;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  const unsigned g64 = grid64(env);
+  dispatch_mlp_shape(policy->width, policy->n_layers, [&](auto W, auto L_) { launch_fv<W(), L_()>(fa, g64, s); });
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
 }
 
 // ---- value gradients and GAE: read the canonical state words, change nothing else; no gate, no pol fields ------------

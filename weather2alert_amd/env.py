@@ -1393,6 +1393,96 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 out["group_surrogate"] = _policy.group_mean(ws_, pol.group, pol.n_groups)
         return out
 
+    # ------------------------------------------------------------------ natural gradient / TRPO: Fisher-vector products
+    def fisher_vector_product(self, policy: dict, alert_days, vector, env_weight=None,
+                              n_steps: int | None = None) -> dict:
+        """The Fisher-vector product F v of a linear or MLP policy over the episodes at hand, along a GIVEN alert
+        schedule: what the natural policy gradient and TRPO's conjugate-gradient step need, formed inside the kernel with
+        no observation row recorded. Every env is forced along its own schedule exactly as in surrogate_gradient() (the
+        same rows o_s, the same scored days: a day on which require_budget forces the action, or which "allowed_days"
+        closes, is not scored). With z_s the logit, p_s = sigmoid(z_s), J_s = dz_s/dtheta and v_g the block of `vector`
+        of the env's group:
+          u_s  = J_s . v_g
+          Fv_e = w_e sum_s p_s (1 - p_s) u_s J_s^T        q_e = sum_s p_s (1 - p_s) u_s^2  (unweighted)
+        and per group the mean of Fv_e over its envs, F_g v_g. The labels of the schedule enter only through the states
+        visited. 1/2 eps^2 "group_quadratic" is the second-order term of the mean over envs of
+        w_e sum_s KL(pi_theta || pi_{theta + eps v}), so TRPO's step length is sqrt(2 delta / group_quadratic) without
+        another pass (examples/trpo_on_device.py).
+          policy      a kind="linear" or kind="mlp" dict, as surrogate_gradient() takes it ("allowed_days", group,
+                      require_budget and the two-row MLP output included; sample and seed are ignored)
+          alert_days  bool [N, T] by day of the episode: the actions ATTEMPTED, as surrogate_gradient()
+          vector      in the shape of the "policy_gradient" the other calls return -- linear: {"weight": [G, n_obs],
+                      "bias": [G]}; mlp: {"layers": [(V, vb), ...]} in the policy's own shapes -- finite (ValueError)
+          env_weight, n_steps  as surrogate_gradient()
+        Returns
+          "fisher_vector_product"  same structure as "policy_gradient" (NaN for a group without envs)
+          "quadratic"              f32 [N]  q_e
+          "days"                   i32 [N]  scored days, as surrogate_gradient()
+          "group_quadratic"        f32 [G]  mean over the group's envs of env_weight * quadratic = <v_g, F_g v_g>
+        Envs finished on entry contribute zero and count. No side effects: the state, the tables, the observation buffer
+        and the RNG are only read. No floating-point atomics: two identical calls give identical bits. Needs the
+        observation buffer current (RuntimeError as surrogate_gradient()) and faithful observations.
+        w2a_fisher_vector_product_linear / _mlp (include/w2a.h)."""
+        kind = policy.get("kind") if isinstance(policy, dict) else None
+        ct, n, dev = self.ct, self.num_envs, self.device
+        mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,
+                                                      who="fisher_vector_product()")
+        check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
+        pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        vec = _policy.check_fisher_args(kind, vector, pol, ct.n_obs, ct.obs_slot, dev)
+        gate = _policy.check_allowed_days(policy, n, ct.T, dev, "fisher_vector_product()")
+        if self._needs_reset:
+            raise RuntimeError("call reset() before fisher_vector_product()")
+        if not self._obs_current:
+            raise RuntimeError(f"fisher_vector_product(kind={kind!r}) reads the observation buffer, which does not hold "
+                               "the agents' current rows (write_obs=False, a built-in rollout or load_state_dict since "
+                               "the last step()/reset()): call step() or reset() first")
+        words = mask.shape[1]
+        out = {"quadratic": torch.empty(n, dtype=torch.float32, device=dev),
+               "days": torch.empty(n, dtype=torch.int32, device=dev)}
+        wp = None if w is None else w.data_ptr()
+        front = (mask.data_ptr(), words, wp, steps, self._obs.data_ptr())
+        outs = (out["quadratic"].data_ptr(), out["days"].data_ptr())
+        gate_args = (None, 0) if gate is None else (gate.data_ptr(), int(gate.shape[1]))
+        with torch.cuda.device(dev):
+            if kind == "linear":
+                lp = _ffi.LinearPolicy()
+                lp.weight, lp.bias = pol.weight_slots.data_ptr(), pol.bias.data_ptr()
+                lp.group = None if pol.group is None else pol.group.data_ptr()
+                lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
+                rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
+                _ffi.check(self._lib.w2a_fisher_vector_product_linear(
+                    self._h, C.byref(lp), vec[0].data_ptr(), vec[1].data_ptr(), *front, rows.data_ptr(), *outs,
+                    self._stream(), *gate_args), "w2a_fisher_vector_product_linear")
+                # per-env products -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
+                g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
+                out["fisher_vector_product"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
+            else:
+                mp = _ffi.MlpPolicy()
+                mp.params = pol.params.data_ptr()
+                mp.group = None if pol.group is None else pol.group.data_ptr()
+                # always group-major (the partial blocks are sized for it), whatever "order" a rollout would use
+                gorder = None if pol.group is None else (pol.order if pol.group_major else _policy.group_order(pol.group))
+                mp.order = None if gorder is None else gorder.data_ptr()
+                mp.n_groups, mp.n_layers, mp.width = pol.n_groups, pol.n_layers, pol.width
+                mp.activation = _ffi.MLP_ACTIVATIONS[pol.activation]
+                mp.sample, mp.require_budget, mp.seed = 0, int(pol.require_budget), 0
+                blocks = torch.empty((pol.n_groups, _policy.mlp_stride(pol.width, pol.n_layers)), dtype=torch.float32,
+                                     device=dev)
+                ws = torch.empty(self._lib.w2a_fisher_vector_product_mlp_workspace_bytes(
+                    n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
+                _ffi.check(self._lib.w2a_fisher_vector_product_mlp(
+                    self._h, C.byref(mp), vec.data_ptr(), *front, blocks.data_ptr(), *outs, ws.data_ptr(), ws.numel(),
+                    self._stream(), *gate_args), "w2a_fisher_vector_product_mlp")
+                out["fisher_vector_product"] = {"layers": _policy.unpack_mlp_grad(blocks, ct.obs_slot, ct.n_obs,
+                                                                                  pol.hidden, pol.n_out)}
+            wq = out["quadratic"].double() if w is None else (w.double() * out["quadratic"].double())
+            if pol.group is None:  # one group: the fp64 mean, rounded once
+                out["group_quadratic"] = wq.mean().to(torch.float32).reshape(1)
+            else:
+                out["group_quadratic"] = _policy.group_mean(wq, pol.group, pol.n_groups)
+        return out
+
     # ------------------------------------------------------------------ critic: value regression along a schedule
     def value_gradient(self, value: dict, alert_days, env_weight=None, n_steps: int | None = None,
                        advantage: bool = False, gamma: float = 1.0, gae_lambda: float = 1.0, bootstrap: bool = False,

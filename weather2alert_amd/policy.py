@@ -514,6 +514,67 @@ def unpack_mlp_grad(P, obs_slot, n_obs: int, hidden, n_out: int = 1):
     return layers
 
 
+def check_fisher_args(kind, vector, pol, n_obs: int, obs_slot, device):
+    """The ``vector`` of ``fisher_vector_product()``, which has the shape of the "policy_gradient" the gradient calls
+    return for the checked policy `pol` (LinearPolicyArgs or MlpPolicyArgs): linear {"weight": [G, n_obs], "bias": [G]},
+    mlp {"layers": [(V, vb), ...]} in the policy's own shapes (a leading G where the policy has G > 1 blocks; a two-row
+    output as two rows). ValueError for another structure, a shape that differs in any layer, another G, and an entry
+    that is not finite (as float32). Returns the vector in the kernel's form on `device`, packed by what the policy
+    itself goes through -- linear: (f32 [G, 32] in slot order, f32 [G]); mlp: f32 [G, stride] -- both linear maps, so the
+    two-row fold and the padding come out right and the padding stays zero."""
+    who = "fisher_vector_product()"
+    if not isinstance(vector, dict):
+        raise ValueError(f"{who}: vector must be a dict in the shape of \"policy_gradient\", got {type(vector).__name__}")
+    G = pol.n_groups
+    if kind == "linear":
+        if set(vector) != {"weight", "bias"}:
+            raise ValueError(f"{who}: a linear policy's vector is {{'weight': [G, n_obs], 'bias': [G]}}, "
+                             f"got keys {sorted(vector)}")
+        vw, vb = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in (vector["weight"], vector["bias"]))
+        if not vw.is_floating_point() or not vb.is_floating_point():
+            raise ValueError(f"{who}: vector must be float, got {vw.dtype} and {vb.dtype}")
+        if tuple(vw.shape) != (G, n_obs):
+            raise ValueError(f"{who}: vector['weight'] must be [G={G}, n_obs={n_obs}], got {tuple(vw.shape)}")
+        if vb.numel() != G or vb.dim() > 1:
+            raise ValueError(f"{who}: vector['bias'] must be [G={G}], got {tuple(vb.shape)}")
+        vw = vw.detach().to(device=device, dtype=torch.float32)
+        vb = vb.detach().reshape(G).to(device=device, dtype=torch.float32).contiguous()
+        if not bool(torch.isfinite(vw).all()) or not bool(torch.isfinite(vb).all()):
+            raise ValueError(f"{who}: vector must be finite (as float32)")
+        return to_slot_order(vw, obs_slot, n_obs).contiguous(), vb
+    if set(vector) != {"layers"}:
+        raise ValueError(f"{who}: an mlp policy's vector is {{'layers': [(V, vb), ...]}}, got keys {sorted(vector)}")
+    layers = vector["layers"]
+    if not isinstance(layers, (list, tuple)) or len(layers) != pol.n_layers + 1:
+        raise ValueError(f"{who}: vector['layers'] must hold {pol.n_layers + 1} (V, vb) pairs, as the policy's layers")
+    fan_in, out_rows = [n_obs] + list(pol.hidden), list(pol.hidden) + [pol.n_out]
+    full = []
+    for i, layer in enumerate(layers):
+        if not isinstance(layer, (list, tuple)) or len(layer) != 2:
+            raise ValueError(f"{who}: vector layer {i} must be a (V, vb) pair")
+        V, vb = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in layer)
+        if not V.is_floating_point() or not vb.is_floating_point():
+            raise ValueError(f"{who}: vector layer {i} must be float, got {V.dtype} and {vb.dtype}")
+        V, vb = V.detach().cpu(), vb.detach().cpu()
+        if G == 1 and V.dim() == 2:
+            V = V.unsqueeze(0)
+        if G == 1 and vb.dim() == 1:
+            vb = vb.unsqueeze(0)
+        if tuple(V.shape) != (G, out_rows[i], fan_in[i]) or tuple(vb.shape) != (G, out_rows[i]):
+            raise ValueError(f"{who}: vector layer {i} must be [G={G}, {out_rows[i]}, {fan_in[i]}] and "
+                             f"[G={G}, {out_rows[i]}], the policy's own shapes, got {tuple(np.shape(layer[0]))} and "
+                             f"{tuple(np.shape(layer[1]))}")
+        if not bool(torch.isfinite(V.to(torch.float32)).all()) or not bool(torch.isfinite(vb.to(torch.float32)).all()):
+            raise ValueError(f"{who}: vector must be finite (as float32)")
+        full.append((V, vb))
+    try:
+        P, width, nl, G_v = pack_mlp(full, obs_slot, n_obs)
+    except ValueError as e:  # the folded output row overflowing f32
+        raise ValueError(f"{who}: {e}") from None
+    assert (width, nl, G_v) == (pol.width, pol.n_layers, G)
+    return P.to(device).contiguous()
+
+
 def mlp_grad_to_module(module: torch.nn.Module, grad: dict, group: int = 0, ascent: bool = True) -> None:
     """Write ``rollout(mlp, policy_gradient=...)["policy_gradient"]`` of group `group` into the ``.grad`` of the Linears
     of the Sequential mlp_from_module accepts (in order). ascent=True writes the NEGATED gradient, so that a torch
