@@ -211,6 +211,7 @@ struct w2a_env {
   W2aBook bk;
   int pm_kernel;         // W2A_PM_* : which posterior-mean reward kernel w2a_posterior_mean_reward launches
   int w_tail_used;       // some coefficient row uses slot 28, 30 or 31 (scanned once by w2a_create)
+  uint32_t s64_launches; // k_step64 launches issued on this handle: its parity is the launch's walk direction (w2a_step64.hip.h)
 };
 
 static thread_local char g_err[512] = "";

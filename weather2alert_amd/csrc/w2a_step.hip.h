@@ -24,6 +24,7 @@ struct StepArgs {
                           // is read from the mirror's day word, StateArrays::pk_day)
   int32_t skip_finished;  // k_step64: envs whose episode is over are left untouched (reward 0, done 1, no status bit)
   int32_t next_step;      // AUTORESET variants: restart on the call after the terminal step (W2A_STEP_NEXT_STEP)
+  uint32_t walk_rev;      // k_step64: every XCD walks its share of the env tiles backwards (odd launches; speed only)
 };
 
 #ifndef W2A_MIN_WAVES

@@ -113,6 +113,23 @@ __device__ __forceinline__ void st1_sc1(void *p, uint32_t v) {
 #ifndef W2A_S64_TILES
 #define W2A_S64_TILES 1  // consecutive 64-env tiles per wave (2 and 4, with the next tile's state loads in flight, measured slower)
 #endif
+// Serpentine walk: an XCD's share of a launch (state words, outputs and the coefficient rows it touches)
+// is about three times its 4 MiB L2, so when every launch walks the tiles in the same order, the lines a launch wants
+// first are the ones the previous launch evicted longest ago: nothing is reused from launch to launch. Odd launches of a
+// handle (StepArgs::walk_rev, set by w2a_step) therefore walk every XCD's share backwards -- the envs served last by one
+// step are served first by the next and find their coefficient line and state words still in L2. Every env is served by
+// exactly one wave with the same arithmetic in both directions. 0 = the same walk on every launch.
+#ifndef W2A_S64_SERPENTINE
+#define W2A_S64_SERPENTINE 1
+#endif
+// logical_block() with every XCD's contiguous share in reverse order (workgroup b runs on XCD b % 8 in both)
+__device__ __forceinline__ uint32_t logical_block_rev(uint32_t b, uint32_t per_xcd) {
+#if W2A_XCD_SWIZZLE
+  return (b & 7u) * per_xcd + (per_xcd - 1u - (b >> 3));
+#else
+  return 8u * per_xcd - 1u - b;
+#endif
+}
 // One 64-env tile of one wave, phases A..C, from the tile's already loaded state words and action.
 // REWARD_GIVEN: a.reward already holds today's reward (w2a_posterior_mean_reward ran on the same state and actions):
 // no coefficient gather and no logits here, the rest of env.py:238-262 as usual.
@@ -450,8 +467,15 @@ __global__ __launch_bounds__(BLOCK, FIXES ? 3 : W2A_S64_MIN_WAVES) void k_step64
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   S64WaveT<FIXES> &sw = s_w[wave];
-  const uint32_t lb = logical_block(blockIdx.x, gridDim.x >> 3);  // grid is a multiple of 8 workgroups
-  const int64_t wave_env0 = ((int64_t)lb * S64_WAVES + wave) * (S64_ENVS * W2A_S64_TILES);
+  uint32_t lb = logical_block(blockIdx.x, gridDim.x >> 3);  // grid is a multiple of 8 workgroups
+  int wave_tile = wave;  // which of the workgroup's wave shares this wave serves
+#if W2A_S64_SERPENTINE
+  if (a.walk_rev) {  // same XCD, same share, last tile first; padding tiles are still past the end and return below
+    lb = logical_block_rev(blockIdx.x, gridDim.x >> 3);
+    wave_tile = S64_WAVES - 1 - wave;
+  }
+#endif
+  const int64_t wave_env0 = ((int64_t)lb * S64_WAVES + wave_tile) * (S64_ENVS * W2A_S64_TILES);
   if (wave_env0 >= a.n) return;  // whole wave past the end (padding tiles); no workgroup barrier is used below
   // packed variant: the day of this wave's tile(s), one word per 64 envs (wave-uniform address)
   uint32_t dayn = 0;

@@ -65,6 +65,10 @@ int w2a_step(w2a_env *env, const void *actions, int action_dtype, float *obs, fl
     const int64_t per_wg = (int64_t)BLOCK * W2A_S64_TILES;
     const int64_t tiles = (env->n + per_wg - 1) / per_wg;
     dim3 grid64((unsigned)(((tiles + 7) / 8) * 8));
+    // serpentine walk: consecutive launches of a handle walk the tiles in opposite directions (w2a_step64.hip.h). The
+    // direction is a kernel argument, so a recorded launch keeps the one it was recorded with: consecutive recorded
+    // steps still alternate, and no result depends on it.
+    a.walk_rev = env->s64_launches++ & 1u;
     if (plan.kernel == W2A_BK_STEP_PACKED) {
       // lock-step mirror (StateArrays::pk_hot / pk_c): 20 B in and 8 B out of per-env state instead of 28 and 12
       a.uni_nd = plan.uni_nd;
