@@ -372,6 +372,15 @@ int w2a_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_
 enum { W2A_MLP_TANH = 0, W2A_MLP_RELU = 1 };
 #define W2A_MLP_STRIDE(width, n_layers) \
   (W2A_ROW_FLOATS * (width) + (width) + ((n_layers) == 2 ? (width) * (width) + (width) : 0) + (width) + 4)
+/* The two-head layout of the same block, read by w2a_q_gradient_mlp alone (a Q-net with one output row per action;
+ * every other entry point takes the layout above): everything up to and including b2 (b1 with one hidden layer) is
+ * unchanged, and the tail  w_out[width], b_out, 0, 0, 0  becomes
+ *             w_out0[width]     Q(o, 0): no alert
+ *             w_out1[width]     Q(o, 1): alert
+ *             b_out0, b_out1, 0, 0
+ * W2A_MLP_HEADS_STRIDE = W2A_MLP_STRIDE + width floats per block: rows stay 16-B aligned. The struct is the same
+ * w2a_mlp_policy; which layout `params` holds is decided by the entry point it is passed to. */
+#define W2A_MLP_HEADS_STRIDE(width, n_layers) (W2A_MLP_STRIDE(width, n_layers) + (width))
 typedef struct w2a_mlp_policy {
   const float *params;
   const int32_t *group;
@@ -1014,6 +1023,47 @@ int w2a_fisher_vector_product_mlp(w2a_env *env, const w2a_mlp_policy *policy, co
                                   int32_t n_steps, const float *obs, float *fv, float *quadratic, int32_t *days,
                                   void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
                                   int32_t allowed_words);
+/* DQN / double-DQN temporal-difference semi-gradient of a two-head MLP Q-net along a GIVEN alert schedule, reduced per
+ * group. The env is forced along its schedule exactly as in w2a_value_gradient_mlp (the same bitmap, the same
+ * attempted-versus-issued rule, the same rows o_s, the same reward statements); an off-policy replay buffer is therefore
+ * a list of (reset seed, schedule bitmap) pairs and no observation row is stored. `q` and `target_net` point to blocks
+ * in the TWO-HEAD layout above (W2A_MLP_HEADS_STRIDE floats each); target_net = NULL: the online net is its own target
+ * (the second evaluation of every row is then skipped). Of target_net only params, width, n_layers, activation and
+ * n_groups are read, and the last four must equal q's; group and order are q's. For env e over the call-days
+ * s = 0 .. S_e - 1 on which it takes a step, with a_s the alert ISSUED on day s (after the budget test):
+ *   N_s      0 when day s is the episode's last day, and on the call's last day (s + 1 == n_steps) unless bootstrap = 1;
+ *            else max_a' Qt(o_{s+1}, a'), or with double_q = 1 Qt(o_{s+1}, a*), a* = 1 iff Q(o_{s+1}, 1) > Q(o_{s+1}, 0)
+ *            under the ONLINE net. With q->require_budget = 1 the max / argmax is restricted to a' = 0 when no budget is
+ *            left after day s (an alert there would be a no-op).
+ *   y_s      = r_s + gamma N_s
+ *   delta_s  = y_s - Q(o_s, a_s)
+ *   c_s      = delta_s (W2A_Q_LOSS_SQUARED, l = delta^2 / 2) or clamp(delta_s, +-huber_delta) (W2A_Q_LOSS_HUBER,
+ *              l = delta^2 / 2 inside, huber_delta (|delta| - huber_delta / 2) outside: smooth_l1 at huber_delta = 1)
+ *   grad[g]  = (1 / N_g) sum over the envs e of group g of  w_e sum_s c_s dQ(o_s, a_s)/dtheta(theta_g)
+ * the semi-gradient (y_s is held fixed), pointing in the ASCENT direction of -loss as every other gradient here. Envs
+ * finished on entry contribute zero and count; a group without envs gives a block of NaN.
+ *   grad        device f32 [n_groups][W2A_MLP_HEADS_STRIDE(width, n_layers)] in the two-head layout
+ *   loss        f32 [num_envs]: sum_s l(delta_s), unweighted;   days  i32 [num_envs]: S_e;   ret  f32 [num_envs]: sum_s r_s
+ *   td_error, td_target   nullable f32 [n_steps][num_envs] by call-day and ENV ID: delta_s and y_s on stepped days, 0
+ *               elsewhere (the library zero-fills them on `stream` first)
+ *   workspace   w2a_q_gradient_mlp_workspace_bytes(...) bytes, 256-B aligned: the layout of w2a_value_gradient_mlp with
+ *               the partial blocks at the two-head stride. A smaller one is refused; nothing is written past it.
+ * Numerics contract: head a of a row is, bit for bit, the f32 logit k_rollout_mlp forms for the one-output net made of
+ * the same hidden layers and output row a. y_s, delta_s and c_s are formed in fp64 from the f32 head values and the f32
+ * reward; w_e c_s is rounded to f32 once, and from there on the second pass is that of w2a_policy_gradient_mlp with the
+ * output row selected per env-day; the fp64 sums over tiles and the reduction run unchanged. An env's outputs do not
+ * depend on the other envs, the group layout or the visiting order. No atomics: identical calls give identical bits.
+ * W2A_ERR_ARG where w2a_value_gradient_mlp refuses (same order; sample is not looked at), then for a target net that
+ * differs in shape, a gamma outside [0, 1], a double_q, loss or bootstrap that is no listed value and a huber_delta
+ * that is not finite and positive; W2A_ERR_STATE while `stream` is recording a hipGraph. */
+enum { W2A_Q_LOSS_SQUARED = 0, W2A_Q_LOSS_HUBER = 1 };
+size_t w2a_q_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                          int32_t n_layers);
+int w2a_q_gradient_mlp(w2a_env *env, const w2a_mlp_policy *q, const w2a_mlp_policy *target_net,
+                       const uint32_t *alert_mask, int32_t mask_words, const float *env_weight, int32_t n_steps,
+                       const float *obs, float *grad, float *loss_out, int32_t *days, float *ret, double gamma,
+                       int32_t double_q, int32_t loss, double huber_delta, int32_t bootstrap, float *td_error,
+                       float *td_target, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

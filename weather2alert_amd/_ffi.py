@@ -40,6 +40,7 @@ SYMBOLS = [
     "w2a_surrogate_gradient_mlp_gated",
     "w2a_fisher_vector_product_linear", "w2a_fisher_vector_product_mlp_workspace_bytes",
     "w2a_fisher_vector_product_mlp",
+    "w2a_q_gradient_mlp_workspace_bytes", "w2a_q_gradient_mlp",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
@@ -74,6 +75,7 @@ class Trajectory(C.Structure):
 
 
 TRAJ_VALID, TRAJ_TERMINATED, TRAJ_ALERT = 1, 2, 4  # W2A_TRAJ_* flag bits
+Q_LOSSES = {"squared": 0, "huber": 1}  # W2A_Q_LOSS_SQUARED, W2A_Q_LOSS_HUBER
 PG_BASELINES = {"none": 0, "no_alert": 1}  # W2A_PG_BASELINE_NONE, W2A_PG_BASELINE_NO_ALERT
 
 
@@ -273,6 +275,13 @@ def load(build_if_missing: bool = True):
     lib.w2a_fisher_vector_product_mlp.restype = C.c_int
     lib.w2a_fisher_vector_product_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, vp, i32, vp, i32, vp, vp, vp, vp, vp,
                                                   C.c_size_t, vp] + gate
+    # Q-learning: the online net, the nullable target net, the schedule, env_weight, n_steps, obs, grad, loss, days,
+    # ret, gamma, double_q, loss kind, huber_delta, bootstrap, td_error, td_target, the workspace and the stream
+    lib.w2a_q_gradient_mlp_workspace_bytes.restype = C.c_size_t
+    lib.w2a_q_gradient_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.w2a_q_gradient_mlp.restype = C.c_int
+    lib.w2a_q_gradient_mlp.argtypes = [vp, C.POINTER(MlpPolicy), C.POINTER(MlpPolicy), vp, i32, vp, i32, vp, vp, vp, vp,
+                                       vp, C.c_double, i32, i32, C.c_double, i32, vp, vp, vp, C.c_size_t, vp]
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     if lib.w2a_abi_version() != ABI_VERSION:

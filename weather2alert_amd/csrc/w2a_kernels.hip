@@ -61,6 +61,7 @@
 #include "w2a_fisher.hip.h"
 #include "w2a_value.hip.h"
 #include "w2a_gae.hip.h"
+#include "w2a_qlearn.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"

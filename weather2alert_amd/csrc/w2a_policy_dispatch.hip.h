@@ -2,8 +2,8 @@
 // imitation, surrogate and value gradients and GAE, with their _record, _gated and _weighted forms. Part of libw2a.so;
 // included only by w2a_kernels.hip inside its extern "C" block. No device code lives here.
 //
-// Twelve bodies serve those exports, and two more the Fisher-vector products (w2a_fisher_vector_product_linear / _mlp,
-// which take their nullable gate directly). What they share is written once, in the helpers of the first half of this file:
+// Twelve bodies serve those exports, two more the Fisher-vector products (w2a_fisher_vector_product_linear / _mlp,
+// which take their nullable gate directly) and one w2a_q_gradient_mlp (a second, nullable parameter struct: the target net). What they share is written once, in the helpers of the first half of this file:
 //   check_linear_policy_struct / check_mlp_policy_struct   the checks of the policy struct (and n_steps): need no handle
 //   check_handle_common      NULL handle, the schedule's word count, corrected-semantics flags, 2^31 observation offsets
 //   check_mlp_stride / check_mlp_workspace                 2^31 floats of parameters; the PgmLayout workspace's size
@@ -308,7 +308,9 @@ struct PgmLayout {
 #define PGM_TARGET_WAVES 1024  // one wave per SIMD of the device
 #define PGM_MAX_TILES 16
 
-static PgmLayout pgm_layout(int64_t n, int32_t n_steps, int32_t n_groups, int32_t width, int32_t n_layers) {
+// heads: 1, or 2 for the two-head blocks of w2a_q_gradient_mlp (the partial blocks then have that layout's stride)
+static PgmLayout pgm_layout(int64_t n, int32_t n_steps, int32_t n_groups, int32_t width, int32_t n_layers,
+                            int32_t heads = 1) {
   PgmLayout L;
   const int64_t n_tiles = (n + 63) / 64;
   int64_t tiles = (n_tiles + PGM_TARGET_WAVES - 1) / PGM_TARGET_WAVES;
@@ -318,7 +320,8 @@ static PgmLayout pgm_layout(int64_t n, int32_t n_steps, int32_t n_groups, int32_
   const int64_t groups = (int64_t)n_groups < n ? (int64_t)n_groups : n;
   L.capacity = (uint32_t)(L.n_chunks + groups);
   const size_t days = (size_t)n * (size_t)n_steps;
-  const size_t stride = (size_t)W2A_MLP_STRIDE((int64_t)width, n_layers);
+  const size_t stride = heads == 2 ? (size_t)W2A_MLP_HEADS_STRIDE((int64_t)width, n_layers)
+                                   : (size_t)W2A_MLP_STRIDE((int64_t)width, n_layers);
   size_t off = 0;
   L.day = off; off += align256(sizeof(float2) * days);
   L.day_alert = off; off += align256(days);
@@ -407,6 +410,14 @@ size_t w2a_value_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps,
 size_t w2a_value_gradient_mlp_gae_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
                                                   int32_t n_layers) {
   return w2a_policy_gradient_mlp_workspace_bytes(num_envs, n_steps, n_groups, width, n_layers);
+}
+
+// w2a_q_gradient_mlp: the layout of w2a_value_gradient_mlp with the partial blocks at the two-head stride
+size_t w2a_q_gradient_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                          int32_t n_layers) {
+  if (num_envs <= 0 || n_steps <= 0 || n_groups <= 0) return 0;
+  if ((width != 16 && width != 32 && width != 64) || (n_layers != 1 && n_layers != 2)) return 0;
+  return pgm_layout(num_envs, n_steps, n_groups, width, n_layers, 2).bytes;
 }
 
 // scratch of w2a_value_gradient_linear: y_s (fp64) and the alert issued, per (call-day, env) -- 9 B, as the policy gradient's
@@ -1121,6 +1132,73 @@ int w2a_value_gradient_mlp_gae(w2a_env *env, const w2a_mlp_policy *value, const 
   W2A_CHECK(clear_day_rows(env, n_steps, value_target, s));
   const unsigned g64 = grid64(env);
   dispatch_mlp_shape(value->width, value->n_layers, [&](auto W, auto L_) { launch_gae<W(), L_()>(xa, g64, s); });
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// ---- Q-learning ------------------------------------------------------------------------------------------------------
+// what w2a_q_gradient_mlp checks beyond check_value: the target net against the online one, and the estimator's scalars
+static int check_q_args(const char *fn, const w2a_mlp_policy *q, const w2a_mlp_policy *target_net, double gamma,
+                        int32_t double_q, int32_t loss, double huber_delta, int32_t bootstrap) {
+  if (q->require_budget != 0 && q->require_budget != 1) return fail(W2A_ERR_ARG, "%s: require_budget must be 0 or 1", fn);
+  if (target_net) {
+    if (!target_net->params) return fail(W2A_ERR_ARG, "%s: NULL params of the target net", fn);
+    if ((uintptr_t)target_net->params & 15) return fail(W2A_ERR_ARG, "%s: the target net's params must be 16-B aligned", fn);
+    if (target_net->width != q->width || target_net->n_layers != q->n_layers ||
+        target_net->activation != q->activation || target_net->n_groups != q->n_groups)
+      return fail(W2A_ERR_ARG, "%s: the target net must have the online net's width, n_layers, activation and n_groups", fn);
+  }
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(W2A_ERR_ARG, "%s: gamma must lie in [0, 1]", fn);
+  if (double_q != 0 && double_q != 1) return fail(W2A_ERR_ARG, "%s: double_q must be 0 or 1", fn);
+  if (loss != W2A_Q_LOSS_SQUARED && loss != W2A_Q_LOSS_HUBER)
+    return fail(W2A_ERR_ARG, "%s: loss must be W2A_Q_LOSS_SQUARED or W2A_Q_LOSS_HUBER", fn);
+  if (loss == W2A_Q_LOSS_HUBER && !(isfinite(huber_delta) && huber_delta > 0.0))
+    return fail(W2A_ERR_ARG, "%s: huber_delta must be finite and positive", fn);
+  if (bootstrap != 0 && bootstrap != 1) return fail(W2A_ERR_ARG, "%s: bootstrap must be 0 or 1", fn);
+  return W2A_OK;
+}
+
+int w2a_q_gradient_mlp(w2a_env *env, const w2a_mlp_policy *q, const w2a_mlp_policy *target_net,
+                       const uint32_t *alert_mask, int32_t mask_words, const float *env_weight, int32_t n_steps,
+                       const float *obs, float *grad, float *loss_out, int32_t *days, float *ret, double gamma,
+                       int32_t double_q, int32_t loss, double huber_delta, int32_t bootstrap, float *td_error,
+                       float *td_target, void *workspace, size_t workspace_bytes, void *stream) {
+  const char *fn = "w2a_q_gradient_mlp";
+  if (!q) return fail(W2A_ERR_ARG, "%s: NULL q (the online Q-net)", fn);  // not the value calls' "NULL value"
+  W2A_CHECK(check_mlp_policy_struct(fn, q, n_steps, SAMPLE_IGNORED));
+  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to follow)", fn);
+  W2A_CHECK(check_obs(fn, obs));
+  if (!grad || !loss_out || !days || !ret) return fail(W2A_ERR_ARG, "%s: NULL grad, loss, days or ret", fn);
+  W2A_CHECK(check_q_args(fn, q, target_net, gamma, double_q, loss, huber_delta, bootstrap));
+  W2A_CHECK(check_workspace_pointer(fn, workspace));
+  W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS_AND_REWARD, MASK_SCHEDULE, mask_words));
+  if ((int64_t)q->n_groups * W2A_MLP_HEADS_STRIDE((int64_t)q->width, q->n_layers) >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
+  const PgmLayout L = pgm_layout(env->n, n_steps, q->n_groups, q->width, q->n_layers, 2);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_q_gradient_mlp_workspace_bytes", fn);
+  W2A_CHECK(refuse_while_capturing(fn, stream));
+  QgMlpArgs qa;
+  memset(&qa, 0, sizeof(qa));
+  W2A_CHECK(fill_mlp(fn, env, q, n_steps, obs, nullptr, 0, qa.g.m));
+  qa.g.m.stride = (int32_t)W2A_MLP_HEADS_STRIDE((int64_t)q->width, q->n_layers);  // below 2^31: checked above
+  qa.g.m.r.order = mlp_own_order(q);
+  qa.g.m.r.pol.require_budget = q->require_budget;  // masks the next row's max / argmax when no budget is left
+  bind_pgm_workspace(qa.g, L, workspace, grad);
+  fill_value(qa.v, alert_mask, mask_words, env_weight, loss_out, days, ret, td_error);
+  qa.tparams = target_net ? target_net->params : q->params;
+  qa.td_target = td_target;
+  qa.gamma = gamma;
+  qa.huber_delta = loss == W2A_Q_LOSS_HUBER ? huber_delta : 0.0;
+  qa.double_q = double_q;
+  qa.bootstrap = bootstrap;
+  hipStream_t s = (hipStream_t)stream;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  W2A_CHECK(clear_day_rows(env, n_steps, td_error, s));
+  W2A_CHECK(clear_day_rows(env, n_steps, td_target, s));
+  const unsigned g64 = grid64(env);
+  dispatch_mlp_shape(q->width, q->n_layers, [&](auto W, auto L_) { launch_qg<W(), L_()>(qa, g64, s); });
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;

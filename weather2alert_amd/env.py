@@ -1622,6 +1622,102 @@ class HeatAlertVecEnv(_VectorEnvBase):
             del out["return"]  # no reward was formed
         return out
 
+    # ------------------------------------------------------------------ Q-learning along a schedule
+    def q_gradient(self, q: dict, alert_days, target_net: dict | None = None, gamma: float = 0.99, double: bool = False,
+                   loss: str = "huber", huber_delta: float = 1.0, env_weight=None, n_steps: int | None = None,
+                   bootstrap: bool = False, td_error: bool = False, td_target: bool = False) -> dict:
+        """The DQN / double-DQN temporal-difference semi-gradient of a two-head MLP Q-net along a GIVEN alert schedule,
+        with no observation row recorded: an episode is regenerated from its seed (reset(seed=) on a twin) and forced
+        along its schedule, so a replay buffer is a list of (seed, alert_days) pairs, 1 bit per env-day.
+          q           a kind="mlp" dict as rollout() takes it (groups, padded widths, tanh or ReLU,
+                      policy.mlp_from_module(model.q_net.q_net)) whose output layer has exactly TWO rows: row a is
+                      Q(o, a). A one-row output, "allowed_days", "sample" and an "order" that is not group-major:
+                      ValueError. "require_budget": True masks the next row's max / argmax, see below.
+          target_net  None (the online net is its own target) or a second dict with the same hidden widths, activation
+                      and number of groups (ValueError otherwise)
+          alert_days, env_weight, n_steps, bootstrap   as value_gradient()
+        Every env is forced along its own schedule exactly as in value_gradient() (the same rows o_s, the same rewards).
+        Per env e over the call-days s it steps, with a_s the alert actually ISSUED (after the budget test):
+          N_s     = 0 on the episode's last day, and on the call's last day unless bootstrap=True; otherwise
+                    max_a' Qt(o_{s+1}, a'), or with double=True Qt(o_{s+1}, a*), a* = 1 iff Q(o_{s+1}, 1) > Q(o_{s+1}, 0)
+                    under the ONLINE net. With "require_budget" the max / argmax is restricted to a' = 0 when no budget
+                    is left after day s: an alert there is a no-op (action masking).
+          y_s     = r_s + gamma N_s;   delta_s = y_s - Q(o_s, a_s)
+          c_s     = delta_s for loss="squared" (l = delta^2 / 2); clamp(delta_s, +-huber_delta) for "huber" (l = delta^2 / 2
+                    inside, huber_delta (|delta| - huber_delta / 2) outside: SB3's smooth_l1_loss at huber_delta = 1)
+          g_e     = w_e sum_s c_s dQ(o_s, a_s)/dtheta   (the semi-gradient: nothing flows through y_s)
+        and per group the mean of g_e over its envs, so ``theta += lr * grad`` DESCENDS the TD loss ("Adam descends":
+        policy.mlp_heads_grad_to_module writes the negated gradient into an SB3-shaped q_net). Returns
+          "q_gradient"   {"layers": [(dW, db), ...]} in the net's own shapes, the output layer with its two rows; the
+                         mean over each group's envs (envs finished on entry give zero and count; NaN for a group
+                         without envs)
+          "loss"         f32 [N]  sum_s l(delta_s), unweighted
+          "days"         i32 [N]  days scored (every stepped day is)
+          "return"       f32 [N]  sum_s r_s along the schedule (undiscounted)
+          "group_loss"   f32 [G]  mean over the group's envs of env_weight * loss
+          "td_error"     (td_error=True) f32 [S, N] by call-day and ENV ID: delta_s on stepped days, 0 elsewhere -- what
+                         prioritised replay needs
+          "td_target"    (td_target=True) f32 [S, N]: y_s
+        No side effects: the state, the tables, the schedule, the observation buffer and the RNG are only read. No
+        floating-point atomics: two identical calls give identical bits. Needs the observation buffer current
+        (RuntimeError as value_gradient()), reward_mode="sampled" and faithful semantics (ValueError where
+        value_gradient() refuses: rewards enter here). w2a_q_gradient_mlp (include/w2a.h)."""
+        who = "q_gradient()"
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if not isinstance(q, dict) or q.get("kind") != "mlp":
+            raise ValueError(f"{who} needs kind 'mlp', got {q.get('kind') if isinstance(q, dict) else q!r}")
+        mask, w, steps = _policy.check_imitation_args("mlp", alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,
+                                                      who=who)
+        if self.reward_mode != "sampled":
+            raise ValueError(f"{who} needs reward_mode='sampled'")
+        pol, tparams = _policy.check_q_net(q, target_net, ct.n_obs, n, ct.obs_slot, dev, who)
+        gamma, huber_delta = _policy.check_q_args(gamma, double, loss, huber_delta, bootstrap, td_error, td_target, who)
+        if self._needs_reset:
+            raise RuntimeError("call reset() before q_gradient()")
+        if not self._obs_current:
+            raise RuntimeError("q_gradient() reads the observation buffer, which does not hold the agents' current rows "
+                               "(write_obs=False, a built-in rollout or load_state_dict since the last step()/reset()): "
+                               "call step() or reset() first")
+        words = mask.shape[1]
+        out = {"loss": torch.empty(n, dtype=torch.float32, device=dev),
+               "days": torch.empty(n, dtype=torch.int32, device=dev),
+               "return": torch.empty(n, dtype=torch.float32, device=dev)}
+        for key, wanted in (("td_error", td_error), ("td_target", td_target)):
+            if wanted:
+                out[key] = torch.empty((steps, n), dtype=torch.float32, device=dev)  # zero-filled by the library
+        with torch.cuda.device(dev):
+            mp = _ffi.MlpPolicy()
+            mp.params = pol.params.data_ptr()
+            mp.group = None if pol.group is None else pol.group.data_ptr()
+            mp.order = None if pol.group is None else pol.order.data_ptr()  # group-major: check_q_net
+            mp.n_groups, mp.n_layers, mp.width = pol.n_groups, pol.n_layers, pol.width
+            mp.activation = _ffi.MLP_ACTIVATIONS[pol.activation]
+            mp.sample, mp.require_budget, mp.seed = 0, int(pol.require_budget), 0
+            tp = None
+            if tparams is not None:
+                tp = _ffi.MlpPolicy()
+                tp.params, tp.group, tp.order = tparams.data_ptr(), None, None
+                tp.n_groups, tp.n_layers, tp.width, tp.activation = mp.n_groups, mp.n_layers, mp.width, mp.activation
+                tp.sample, tp.require_budget, tp.seed = 0, 0, 0
+            blocks = torch.empty((pol.n_groups, _policy.mlp_heads_stride(pol.width, pol.n_layers)), dtype=torch.float32,
+                                 device=dev)
+            ws = torch.empty(self._lib.w2a_q_gradient_mlp_workspace_bytes(n, steps, pol.n_groups, pol.width, pol.n_layers),
+                             dtype=torch.uint8, device=dev)
+            _ffi.check(self._lib.w2a_q_gradient_mlp(
+                self._h, C.byref(mp), None if tp is None else C.byref(tp), mask.data_ptr(), words,
+                None if w is None else w.data_ptr(), steps, self._obs.data_ptr(), blocks.data_ptr(),
+                out["loss"].data_ptr(), out["days"].data_ptr(), out["return"].data_ptr(), gamma, int(double),
+                _ffi.Q_LOSSES[loss], huber_delta, int(bootstrap), out["td_error"].data_ptr() if td_error else None,
+                out["td_target"].data_ptr() if td_target else None, ws.data_ptr(), ws.numel(), self._stream()),
+                "w2a_q_gradient_mlp")
+            out["q_gradient"] = {"layers": _policy.unpack_mlp_heads_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden)}
+            wl = out["loss"].double() if w is None else (w.double() * out["loss"].double())
+            if pol.group is None:  # one group: the fp64 mean, rounded once
+                out["group_loss"] = wl.mean().to(torch.float32).reshape(1)
+            else:
+                out["group_loss"] = _policy.group_mean(wl, pol.group, pol.n_groups)
+        return out
+
     # ------------------------------------------------------------------ hindsight optimum
     def hindsight_optimum(self, start_state: dict | None = None, n_steps: int | None = None,
                           allowed_days=None) -> dict:

@@ -514,6 +514,120 @@ def unpack_mlp_grad(P, obs_slot, n_obs: int, hidden, n_out: int = 1):
     return layers
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Two-head Q-nets: q_gradient() (csrc/w2a_qlearn.hip.h). The output layer keeps its two rows, Q(o, 0) and Q(o, 1).
+# ----------------------------------------------------------------------------------------------------------------------
+def mlp_heads_stride(width: int, n_layers: int) -> int:
+    """Floats per group block of the two-head layout (w2a.h: W2A_MLP_HEADS_STRIDE): the block of mlp_stride with the tail
+    wo[w], bo, 3 pad replaced by wo0[w], wo1[w], bo0, bo1, 2 pad."""
+    return mlp_stride(width, n_layers) + width
+
+
+def pack_mlp_heads(layers, obs_slot, n_obs: int):
+    """Pack layers whose output layer has exactly two rows into the two-head layout: f32 [G, mlp_heads_stride] on the
+    CPU, with (width, n_layers, G). Nothing is folded: row a of the output layer is Q(o, a). Up to and including the
+    first output row the block is pack_mlp's of the one-output net made of the same hidden layers and row 0."""
+    L, G = _mlp_layers(layers, n_obs)
+    Wo, bo = L[-1]
+    if Wo.shape[1] != 2:
+        raise ValueError(f"mlp q-net: the output layer must have exactly 2 rows (one action value each), got {Wo.shape[1]}")
+    P0, w, nl, _ = pack_mlp(L[:-1] + [(Wo[:, :1], bo[:, :1])], obs_slot, n_obs)
+    P1 = pack_mlp(L[:-1] + [(Wo[:, 1:], bo[:, 1:])], obs_slot, n_obs)[0]
+    st = mlp_stride(w, nl)
+    P = torch.zeros((G, st + w), dtype=torch.float32)
+    P[:, :st - 4] = P0[:, :st - 4]
+    P[:, st - 4:st - 4 + w] = P1[:, st - 4 - w:st - 4]
+    P[:, st - 4 + w] = P0[:, st - 4]
+    P[:, st - 3 + w] = P1[:, st - 4]
+    return P, w, nl, G
+
+
+def unpack_mlp_heads_grad(P, obs_slot, n_obs: int, hidden):
+    """A gradient in the two-head block layout (f32 or f64 [G, mlp_heads_stride(width, n_layers)], as w2a_q_gradient_mlp
+    writes it) -> layers [(dW [G, out, in], db [G, out]), ...] in torch's Linear convention with the real widths
+    `hidden` and a two-row output layer: the adjoint of pack_mlp_heads' placement, <pack(L), P> = <L, unpack(P)>."""
+    hidden = [int(h) for h in hidden]
+    nl, w = len(hidden), mlp_width(hidden)
+    st = mlp_stride(w, nl)
+    if P.dim() != 2 or P.shape[1] != st + w:
+        raise ValueError(f"unpack_mlp_heads_grad: expected [G, {st + w}] for hidden widths {hidden}, got {tuple(P.shape)}")
+    pad = torch.zeros((P.shape[0], 3), dtype=P.dtype, device=P.device)
+    row0 = torch.cat([P[:, :st - 4], P[:, st - 4 + w:st - 3 + w], pad], dim=1)
+    row1 = torch.cat([P[:, :st - 4 - w], P[:, st - 4:st - 4 + w], P[:, st - 3 + w:st - 2 + w], pad], dim=1)
+    L0 = unpack_mlp_grad(row0, obs_slot, n_obs, hidden, 1)
+    L1 = unpack_mlp_grad(row1, obs_slot, n_obs, hidden, 1)
+    return L0[:-1] + [(torch.cat([L0[-1][0], L1[-1][0]], dim=1).contiguous(),
+                       torch.cat([L0[-1][1], L1[-1][1]], dim=1).contiguous())]
+
+
+def mlp_heads_grad_to_module(module: torch.nn.Module, grad: dict, group: int = 0, ascent: bool = True) -> None:
+    """Write ``q_gradient()["q_gradient"]`` of group `group` into the ``.grad`` of the Linears of an SB3-shaped q_net
+    (``model.q_net.q_net``: Linear, act, [Linear, act,] Linear with two output units), as mlp_grad_to_module does for a
+    policy: ascent=True writes the NEGATED gradient, so that a torch optimizer's ``step()`` descends the TD loss."""
+    out = grad["layers"][-1][0]
+    if out.shape[-2] != 2:
+        raise ValueError(f"mlp_heads_grad_to_module: the gradient's output layer has {out.shape[-2]} rows, not 2")
+    mlp_grad_to_module(module, grad, group, ascent)
+
+
+Q_LOSSES = ("huber", "squared")
+
+
+def check_q_net(q, target_net, n_obs: int, num_envs: int, obs_slot, device, who: str = "q_gradient()"):
+    """The two nets of ``q_gradient()``: `q` a kind="mlp" dict as rollout() takes it whose output layer has exactly two
+    rows, `target_net` None or a second one with the same hidden widths, activation and number of groups (its "group",
+    "order" and "require_budget" are not read: the online net's hold). ValueError for a one-row output, for
+    "allowed_days" and "sample" (gates and sampling have no meaning here) and for an "order" that is not group-major.
+    Returns (MlpPolicyArgs of q with `params` in the two-head layout, the target's f32 [G, stride] blocks or None)."""
+    if not isinstance(q, dict) or q.get("kind") != "mlp":
+        raise ValueError(f"{who} needs kind 'mlp', got {q.get('kind') if isinstance(q, dict) else type(q).__name__!r}")
+    if q.get("allowed_days") is not None:
+        raise ValueError(f"{who}: 'allowed_days' is not taken (gates are out of scope for Q-learning here)")
+    if q.get("sample"):
+        raise ValueError(f"{who}: 'sample' is not taken (the schedule holds the actions; collect with rollout())")
+    pol = check_mlp_policy(q, n_obs, num_envs, obs_slot, device)
+    if pol.n_out != 2:
+        raise ValueError(f"{who}: the output layer must have exactly 2 rows (one action value each), got {pol.n_out}")
+    if q.get("order") is not None and pol.group is not None and not torch.equal(pol.order, group_order(pol.group)):
+        raise ValueError(f"{who}: 'order' must be group-major (leave it out: the envs are visited sorted by group)")
+    pol.params = pack_mlp_heads(q["layers"], obs_slot, n_obs)[0].to(device).contiguous()
+    tparams = None
+    if target_net is not None:
+        if not isinstance(target_net, dict) or target_net.get("kind") != "mlp":
+            raise ValueError(f"{who}: target_net must be None or a kind='mlp' dict")
+        unknown = set(target_net) - MLP_KEYS
+        if unknown:
+            raise ValueError(f"{who}: target_net: unknown key(s) {sorted(unknown)}")
+        if "layers" not in target_net:
+            raise ValueError(f"{who}: target_net: 'layers' is required")
+        if target_net.get("activation", "tanh") != pol.activation:
+            raise ValueError(f"{who}: target_net's activation differs from the online net's ({pol.activation!r})")
+        tl, tG = _mlp_layers(target_net["layers"], n_obs)
+        t_hidden = tuple(int(W.shape[1]) for W, _ in tl[:-1])
+        if t_hidden != tuple(pol.hidden) or tG != pol.n_groups:
+            raise ValueError(f"{who}: target_net must have the online net's hidden widths {tuple(pol.hidden)} and "
+                             f"{pol.n_groups} group(s), got {t_hidden} and {tG}")
+        tparams = pack_mlp_heads(target_net["layers"], obs_slot, n_obs)[0].to(device).contiguous()
+    return pol, tparams
+
+
+def check_q_args(gamma, double, loss, huber_delta, bootstrap, td_error, td_target, who: str = "q_gradient()"):
+    """The scalars of ``q_gradient()``: gamma a finite number in [0, 1], loss "huber" or "squared", huber_delta finite and
+    positive, double / bootstrap / td_error / td_target plain bools: ValueError otherwise. Returns (gamma, huber_delta)."""
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not np.isfinite(gamma) \
+            or not 0.0 <= float(gamma) <= 1.0:
+        raise ValueError(f"{who}: gamma must be a finite number in [0, 1], got {gamma!r}")
+    if loss not in Q_LOSSES:
+        raise ValueError(f"{who}: loss must be one of {Q_LOSSES}, got {loss!r}")
+    if isinstance(huber_delta, bool) or not isinstance(huber_delta, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(huber_delta) or not huber_delta > 0:
+        raise ValueError(f"{who}: huber_delta must be a finite positive number, got {huber_delta!r}")
+    for nm, v in (("double", double), ("bootstrap", bootstrap), ("td_error", td_error), ("td_target", td_target)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{who}: {nm} must be a bool, got {v!r}")
+    return float(gamma), float(huber_delta)
+
+
 def check_fisher_args(kind, vector, pol, n_obs: int, obs_slot, device):
     """The ``vector`` of ``fisher_vector_product()``, which has the shape of the "policy_gradient" the gradient calls
     return for the checked policy `pol` (LinearPolicyArgs or MlpPolicyArgs): linear {"weight": [G, n_obs], "bias": [G]},
