@@ -702,8 +702,9 @@ def test_imitation_gradient(dev, tabs, name, kind, case):
 # ------------------------------------------------------------------ f. refusals
 def test_layouts_the_policy_kernels_cannot_serve_are_refused(dev, tabs):
     """An observation column on slot 30: step() serves it (the row is a gather of 32 slots); every policy entry refuses
-    it -- the host check of policy.slot_map first, and with that check out of the way the library's own schema error --
-    and nothing is written. An obs_slot that is not injective is refused by w2a_create."""
+    it (rollout, the gradient and imitation calls, value_gradient on both its paths, surrogate_gradient,
+    fisher_vector_product and q_gradient) -- the host check of policy.slot_map first, and with that check out of the way the
+    library's own schema error -- and nothing is written. An obs_slot that is not injective is refused by w2a_create."""
     from weather2alert_amd import HeatAlertVecEnv, _ffi
 
     tb, n = tabs["narrow"], 70
@@ -732,6 +733,18 @@ def test_layouts_the_policy_kernels_cannot_serve_are_refused(dev, tabs):
     calls = [lambda: env.rollout(lin), lambda: env.rollout(mlp), lambda: env.rollout(lin, record=True),
              lambda: env.rollout(lin, policy_gradient=True), lambda: env.rollout(mlp, policy_gradient=True),
              lambda: env.imitation_gradient(lin, sched), lambda: env.imitation_gradient(mlp, sched)]
+    # the critic, PPO, Fisher and Q entry points, linear and MLP where both exist, the plain and the GAE path of the critic
+    adv = np.zeros((ct.T, n), np.float32)
+    vec_lin = {"weight": np.ones_like(W), "bias": np.ones_like(b)}
+    vec_mlp = {"layers": [(np.ones_like(Wl), np.ones_like(bl)) for Wl, bl in layers]}
+    qnet = dict(kind="mlp", layers=E.net(ct, (16,), 2, seed=4), activation="tanh", group=g)
+    gae = dict(gamma=0.97, gae_lambda=0.9, bootstrap=True, n_steps=7)
+    lin2, mlp2 = ({k: v for k, v in p.items() if k != "sample"} for p in (lin, mlp))
+    calls += [lambda: env.value_gradient(lin2, sched), lambda: env.value_gradient(mlp2, sched),
+              lambda: env.value_gradient(lin2, sched, **gae), lambda: env.value_gradient(mlp2, sched, **gae),
+              lambda: env.surrogate_gradient(lin2, sched, adv), lambda: env.surrogate_gradient(mlp2, sched, adv),
+              lambda: env.fisher_vector_product(lin2, sched, vec_lin), lambda: env.fisher_vector_product(mlp2, sched, vec_mlp),
+              lambda: env.q_gradient(qnet, sched), lambda: env.q_gradient(qnet, sched, target_net=dict(qnet), double=True)]
     before = env.state_dict()
     obs0 = env._obs.clone()
     for call in calls:
