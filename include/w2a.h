@@ -882,8 +882,18 @@ enum { W2A_Q_LOCKSTEP = 6,           /* 1: every env is known to be on the same 
                                         w2a_rollout_linear: k_rollout_linear (lane = env); 4 after
                                         w2a_rollout_mlp: k_rollout_mlp (lane = env, f32 matrix cores) */,
        W2A_Q_LAST_STEP_KERNEL = 5    /* what the last w2a_step launched: -1 none yet, 0 k_step (4 lanes per env),
-                                        1 k_step64 on the canonical state words, 2 k_step64 on the lock-step mirror */ };
+                                        1 k_step64 on the canonical state words, 2 k_step64 on the lock-step mirror */,
+       W2A_Q_EPISODE_WORD_BYTES = 7  /* bytes per env of the lock-step mirror's per-episode word: 4 (narrow) or 8 */ };
 int w2a_query(w2a_env *env, int what);
+
+/* Debug / A-B switch, results never depend on it. The lock-step mirror keeps one word per env that is constant while an
+ * episode runs. w2a_create picks its form from the table dims: where the coefficient-row index (S * n_samples values)
+ * and the day-row index (S_w * Y values) fit 32 bits together, a 4-byte word of the two indices (the budget then
+ * travels as the remaining budget in the mirror's state word: 145 B per env-step), else the 8-byte word of budget,
+ * column, row and draw (149 B). force_wide != 0 makes the handle use the 8-byte word whatever the dims, 0 goes back to
+ * the rule. To be called before the handle first steps on the packed form: W2A_ERR_STATE while the mirror is current
+ * or a packed step has been recorded into a hipGraph. */
+int w2a_set_episode_word(w2a_env *env, int force_wide);
 
 /* The caller has overwritten the state buffer (e.g. restored a checkpoint of its canonical part) on `stream`: forget
  * every derived form (lock-step mirror, column grouping, row counts, what is known about days). Host-side bookkeeping

@@ -22,7 +22,7 @@ SYMBOLS = [
     "w2a_abi_version", "w2a_last_error", "w2a_state_bytes", "w2a_create", "w2a_destroy", "w2a_reset",
     "w2a_reset_device_rng", "w2a_set_autoreset", "w2a_step", "w2a_get_state", "w2a_read_status",
     "w2a_sort_workspace_bytes", "w2a_sort_episodes", "w2a_reset_device_rng_sorted", "w2a_observe", "w2a_rollout", "w2a_rollout_order_workspace_bytes", "w2a_rollout_order_attach", "w2a_rollout_order", "w2a_rollout_posterior_mean", "w2a_policy_actions", "w2a_set_semantics",
-    "w2a_group_workspace_bytes", "w2a_group_by_column", "w2a_posterior_mean_reward", "w2a_set_posterior_kernel", "w2a_invalidate", "w2a_query", "w2a_rollout_mfma_workspace_bytes", "w2a_rollout_mfma_prepare",
+    "w2a_group_workspace_bytes", "w2a_group_by_column", "w2a_posterior_mean_reward", "w2a_set_posterior_kernel", "w2a_set_episode_word", "w2a_invalidate", "w2a_query", "w2a_rollout_mfma_workspace_bytes", "w2a_rollout_mfma_prepare",
     "w2a_rollout_linear", "w2a_rollout_mlp", "w2a_rollout_linear_record", "w2a_rollout_mlp_record",
     "w2a_posterior_returns", "w2a_hindsight_workspace_bytes", "w2a_hindsight_optimum",
     "w2a_policy_gradient_workspace_bytes", "w2a_policy_gradient_linear",
@@ -43,6 +43,7 @@ SYMBOLS = [
     "w2a_q_gradient_mlp_workspace_bytes", "w2a_q_gradient_mlp",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
+Q_EPISODE_WORD_BYTES = 7
 ROLLOUT_KERNELS = {0: "k_rollout", 1: "k_rollout64", 2: "k_rollout_mfma", 3: "k_rollout_linear", 4: "k_rollout_mlp"}  # W2A_Q_LAST_ROLLOUT_KERNEL
 PM_KERNELS = {"vector": 0, "matrix": 1, "matrix_i8": 2}  # W2A_PM_VECTOR, W2A_PM_MATRIX_F64, W2A_PM_MATRIX_I8
 POLICY_KINDS = {"never": 0, "always": 1, "bernoulli": 2, "threshold": 3, "table": 4}
@@ -164,6 +165,8 @@ def load(build_if_missing: bool = True):
     lib.w2a_posterior_mean_reward.argtypes = [vp, vp, C.c_int, vp, vp]
     lib.w2a_set_posterior_kernel.restype = C.c_int
     lib.w2a_set_posterior_kernel.argtypes = [vp, C.c_int]
+    lib.w2a_set_episode_word.restype = C.c_int
+    lib.w2a_set_episode_word.argtypes = [vp, C.c_int]
     lib.w2a_rollout_mfma_workspace_bytes.restype = C.c_size_t
     lib.w2a_rollout_mfma_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.w2a_rollout_mfma_prepare.restype = C.c_int

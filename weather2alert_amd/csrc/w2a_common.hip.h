@@ -4,6 +4,7 @@
 #define W2A_COMMON_HIP_H
 
 #include "w2a_bookkeeping.h"
+#include "w2a_episode_word.h"
 
 #ifndef LANES
 #define LANES 4  // lanes per env: 8, 4, 2 or 1 (A/B-tested on MI355X)
@@ -81,13 +82,37 @@ struct StateArrays {
   // stepc word -- written by every reset path (store_episode), read-only while an episode runs, so never stale. Until
   // round 5 the host kept an upper bound of every budget in the buffer instead; four of its eight bookkeeping holes were
   // in that bound.
+  //
+  // NARROW episode word (w2a_episode_word.h; the handle's choice at w2a_create, the kernels get it as `pk_kw` >= 0): where
+  // both row indices of an episode fit 32 bits together, pk_c's allocation holds a dense u32 array in its first 4 B per env,
+  //   word[e]:  wrow[0:kw) xrow[kw:32)      wrow = coef_col * n_samples + sample,  xrow = ep_row
+  // (the two products the step kernel needs, ready made), and the budget does not travel at all: pk_hot.x[0:8) holds the
+  // REMAINING budget (budget - used) instead of `used` -- the step needs nothing else of the pair (at_budget = remaining
+  // == 0, the observation shows remaining - actual). Remaining budgets the field cannot hold (>= PK_REM_ESCAPE, or
+  // negative) are stored as PK_REM_ESCAPE: such a lane keeps the whole 32-bit value in the otherwise unused second half
+  // of pk_c's allocation (pk_rem_of(): one u32 per env behind the episode words; written for every env when the mirror
+  // is packed or an episode starts, then read and written only by lanes on the escape). The mirror stays self-contained:
+  // the packed kernel never touches the canonical words. 145 B per env-step instead of 149.
   uint2 *pk_hot;
   uint2 *pk_c;
   uint32_t *pk_day;
 };
+#define SAMPLE_BITS 12
+#define PACK_W(coef_col, sample) (((uint32_t)(coef_col) << SAMPLE_BITS) | (uint32_t)(sample))
+#define W_COL(y) ((y) >> SAMPLE_BITS)
+#define W_SAMPLE(y) ((y) & ((1u << SAMPLE_BITS) - 1u))
 #define W2A_PK_DAY_POISON 0xFFFFFFFFu
 #define PK_BUDGET_ESCAPE 0xFFFFu
 __device__ __forceinline__ uint32_t pk_budget16(uint32_t budget) { return budget < PK_BUDGET_ESCAPE ? budget : PK_BUDGET_ESCAPE; }
+#define PK_REM_ESCAPE 255u
+__device__ __forceinline__ uint32_t pk_rem8(int32_t remaining) {
+  return (uint32_t)remaining < PK_REM_ESCAPE ? (uint32_t)remaining : PK_REM_ESCAPE;
+}
+__device__ __forceinline__ uint32_t *pk_rem_of(const StateArrays &s, int64_t n) { return reinterpret_cast<uint32_t *>(s.pk_c) + n; }
+// the narrow episode word from the canonical ep_row / ep_w (kw <= 30: w2a_episode_word.h and w2a_create's 32-bit checks)
+__device__ __forceinline__ uint32_t pk_narrow_word(uint32_t ep_row, uint32_t ep_w, uint32_t n_samples, int32_t kw) {
+  return (W_COL(ep_w) * n_samples + W_SAMPLE(ep_w)) | (ep_row << kw);
+}
 #define PK_USED(w) ((w) & 255u)
 #define PK_STREAK(w) (((w) >> 8) & 255u)
 #define PK_HIST(w) (((w) >> 16) & 0x3FFFu)
@@ -157,10 +182,6 @@ __device__ __forceinline__ void set_comp(float4 *x, int idx, float v) {
     if (idx == 4 * q + 3) x[q].w = v;
   }
 }
-#define SAMPLE_BITS 12
-#define PACK_W(coef_col, sample) (((uint32_t)(coef_col) << SAMPLE_BITS) | (uint32_t)(sample))
-#define W_COL(y) ((y) >> SAMPLE_BITS)
-#define W_SAMPLE(y) ((y) & ((1u << SAMPLE_BITS) - 1u))
 
 struct ResetCfg {
   uint64_t seed;
@@ -212,6 +233,7 @@ struct w2a_env {
   int pm_kernel;         // W2A_PM_* : which posterior-mean reward kernel w2a_posterior_mean_reward launches
   int w_tail_used;       // some coefficient row uses slot 28, 30 or 31 (scanned once by w2a_create)
   uint32_t s64_launches; // k_step64 launches issued on this handle: its parity is the launch's walk direction (w2a_step64.hip.h)
+  EpisodeWord ew;        // form of the lock-step mirror's episode word (w2a_episode_word.h)
 };
 
 static thread_local char g_err[512] = "";

@@ -160,10 +160,12 @@ struct HipDev {
   w2a_env *env;
   hipStream_t s;
   void pack_state() {
-    hipLaunchKernelGGL(k_pack_state, dim3((unsigned)((env->n + 255) / 256)), dim3(256), 0, s, env->st, env->n);
+    hipLaunchKernelGGL(k_pack_state, dim3((unsigned)((env->n + 255) / 256)), dim3(256), 0, s, env->st, env->n,
+                       env->ew.narrow ? env->ew.kw : -1, env->tb.n_samples);
   }
   void unpack_state(int32_t n_days) {
-    hipLaunchKernelGGL(k_unpack_state, dim3((unsigned)((env->n + 255) / 256)), dim3(256), 0, s, env->st, env->n, n_days);
+    hipLaunchKernelGGL(k_unpack_state, dim3((unsigned)((env->n + 255) / 256)), dim3(256), 0, s, env->st, env->n, n_days,
+                       env->ew.narrow ? env->ew.kw : -1);
   }
   void poison_mirror() {
     const int64_t tiles = (env->n + 63) / 64;
@@ -266,6 +268,7 @@ int w2a_create(const w2a_tables *t, int64_t num_envs, int64_t env_gid0, void *st
   h->st.pk_c = reinterpret_cast<uint2 *>((char *)h->st.pk_hot + align256(8 * (size_t)num_envs));
   h->st.pk_day = reinterpret_cast<uint32_t *>((char *)h->st.pk_c + align256(8 * (size_t)num_envs));
   bk_init(h->bk, t->T <= 255 && t->S < 65536 && t->n_samples <= 1024 && (int64_t)t->S_w * t->Y < (1 << 22), -1);
+  h->ew = ew_choose(t->S, t->n_samples, t->S_w, t->Y, false);
   h->status = status;
   h->has_autoreset = 0;
   h->perm = nullptr;
@@ -659,6 +662,16 @@ int w2a_set_posterior_kernel(w2a_env *env, int kernel) {
   if (kernel != W2A_PM_VECTOR && kernel != W2A_PM_MATRIX_F64 && kernel != W2A_PM_MATRIX_I8)
     return fail(W2A_ERR_ARG, "w2a_set_posterior_kernel: kernel must be W2A_PM_VECTOR, W2A_PM_MATRIX_F64 or W2A_PM_MATRIX_I8");
   env->pm_kernel = kernel;
+  return W2A_OK;
+}
+
+int w2a_set_episode_word(w2a_env *env, int force_wide) {
+  if (!env) return fail(W2A_ERR_ARG, "w2a_set_episode_word: NULL handle");
+  // the mirror's words are read in the form they were written in: no change while it is current, or while a recorded
+  // packed step (which carries the form as a kernel argument) may be replayed
+  if (env->bk.pk_valid || env->bk.graph_packed)
+    return fail(W2A_ERR_STATE, "w2a_set_episode_word: the packed form of the state is in use; call it right after w2a_create");
+  env->ew = ew_choose(env->tb.S, env->tb.n_samples, env->tb.S_w, env->tb.Y, force_wide != 0);
   return W2A_OK;
 }
 
@@ -1137,6 +1150,7 @@ int w2a_query(w2a_env *env, int what) {
     case W2A_Q_CANONICAL_CURRENT: return env->bk.canon_valid;
     case W2A_Q_LAST_ROLLOUT_KERNEL: return env->bk.last_rollout_kernel;
     case W2A_Q_LAST_STEP_KERNEL: return env->bk.last_step_kernel;
+    case W2A_Q_EPISODE_WORD_BYTES: return env->ew.narrow ? 4 : 8;
     default: return fail(W2A_ERR_ARG, "w2a_query: unknown item");
   }
 }

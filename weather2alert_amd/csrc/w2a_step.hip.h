@@ -25,6 +25,8 @@ struct StepArgs {
   int32_t skip_finished;  // k_step64: envs whose episode is over are left untouched (reward 0, done 1, no status bit)
   int32_t next_step;      // AUTORESET variants: restart on the call after the terminal step (W2A_STEP_NEXT_STEP)
   uint32_t walk_rev;      // k_step64: every XCD walks its share of the env tiles backwards (odd launches; speed only)
+  int32_t pk_kw;          // k_step64 packed variant: >= 0: the mirror's episode word is the narrow one and its coefficient-row
+                          // index has this many bits; -1: the 8-byte word (StateArrays, w2a_common.hip.h)
 };
 
 #ifndef W2A_MIN_WAVES

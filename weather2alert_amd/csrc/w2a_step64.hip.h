@@ -140,7 +140,9 @@ __device__ __forceinline__ uint32_t logical_block_rev(uint32_t b, uint32_t per_x
 // epilogue also writes the mirror's words of the new episode and puts the tile's day word back to 0.
 // FIXES: the corrected-semantics flags of a.tb.fixes (W2A_FIX_*: Q1 agent's 14-day count into the historical column,
 // Q3 true lag, Q5 live over-budget penalty, Q6 observation of the day the next action applies to), as in k_step<..., FIXES>.
-template <bool WRITE_OBS, bool REWARD_GIVEN, bool PACKED, bool AUTORESET = false, bool FIXES = false>
+// NARROW (with PACKED): the mirror's episode word is the 4-byte one (StateArrays, w2a_common.hip.h): c.c is the coefficient-row
+// index itself, and the state word's first field holds what is left of the budget.
+template <bool WRITE_OBS, bool REWARD_GIVEN, bool PACKED, bool AUTORESET = false, bool FIXES = false, bool NARROW = false>
 __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw, const int lane, const int64_t wave_env0,
                                          const bool valid, const uint32_t e, const u3 h, const u3 c, const int32_t act,
                                          const int4 so) {
@@ -153,6 +155,12 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
   // W2A_STEP_NEXT_STEP: an env whose terminal step ran on the previous call restarts on this one (epilogue below); the
   // call is no env step for it: reward 0, not done, no status bit, its action ignored
   const bool restart_in = AUTORESET && a.next_step && D1_FIN(h.b);
+  // first field of the mirror's state word after today: `used`, or (NARROW) what is left of the budget -- decided here
+  // so that the budget does not stay live across the gathers. A lane that came in through the escape (s64_load_packed)
+  // puts the whole 32-bit value back where it found it, unless phase C will leave the env's state alone
+  const uint32_t pk0 = NARROW ? pk_rem8(budget - (int32_t)used2) : used2;
+  if (NARROW && (uint32_t)budget >= PK_REM_ESCAPE && valid && !restart_in && !(a.skip_finished && D1_FIN(h.b)))
+    pk_rem_of(a.st, a.n)[e] = (uint32_t)(budget - (int32_t)used2);
   const uint32_t fx = FIXES ? a.tb.fixes : 0u;
   const bool fix_obs = FIXES && WRITE_OBS && (fx & W2A_FIX_OBS);
   // The effectiveness logit enters the reward through eff * gate * actual (env.py:218-221): its coefficient row is
@@ -166,7 +174,8 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
     // feature row of day t (pre-increment, Q6) and the env's coefficient rows, as float4 indices (32-bit: table
     // sizes are validated in w2a_create). The effectiveness row is fetched only on alert days (k_step).
     const uint32_t day_row = t * (uint32_t)(a.tb.S_w * a.tb.Y) + c.b;
-    const uint32_t wrow = W_COL(c.c) * (uint32_t)a.tb.n_samples + W_SAMPLE(c.c);
+    // (the narrow episode word carries the product itself: s64_load_packed hands it over in c.c)
+    const uint32_t wrow = NARROW ? c.c : W_COL(c.c) * (uint32_t)a.tb.n_samples + W_SAMPLE(c.c);
     // bit 31 of the row index (FIXES only): the observation is the NEXT day's row (W2A_FIX_OBS, not on the terminal step)
     sw.desc[lane] = make_uint2((day_row * (ROWF / 4)) | ((fix_obs && !done) ? 0x80000000u : 0u),
                                (wrow * (2 * ROWF / 4)) | (need_eff << 31));
@@ -345,12 +354,12 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
   h2.c = __float_as_uint(ret);
 #if W2A_S64_SC1 & 2
   // the packed variant's state word goes to the lock-step mirror here too (the host marks the mirror current)
-  if (PACKED) st8_sc1(&a.st.pk_hot[e], v2u{pk_pack_hot(used2, streak2, hist2, done ? 1u : 0u), h2.c});
+  if (PACKED) st8_sc1(&a.st.pk_hot[e], v2u{pk_pack_hot(pk0, streak2, hist2, done ? 1u : 0u), h2.c});
   else st12_sc1(&a.st.hot3[e], v3u{h2.a, h2.b, h2.c});
   if (!REWARD_GIVEN) st4_sc1(&a.reward[e], __float_as_uint(r));
   st1_sc1(&a.done[e], done ? 1u : 0u);
 #else
-  if (PACKED) a.st.pk_hot[e] = make_uint2(pk_pack_hot(used2, streak2, hist2, done ? 1u : 0u), h2.c);
+  if (PACKED) a.st.pk_hot[e] = make_uint2(pk_pack_hot(pk0, streak2, hist2, done ? 1u : 0u), h2.c);
   else a.st.hot3[e] = h2;
   if (!REWARD_GIVEN) a.reward[e] = r;
   a.done[e] = done ? 1 : 0;
@@ -380,7 +389,11 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
         if (ep.bad) atomicOr(a.status, (int)W2A_ST_BAD_EPISODE);
         store_episode(a.st, e, make_uint4(ep.ep_row, ep.ep_w, (uint32_t)ep.sticky, cold.w + 1),
                       make_uint4(pack_d0(0, 0, 0, 0, 0), pack_d1(0, ep.ndays, 0), __float_as_uint(0.0f), (uint32_t)ep.budget));
-        if (PACKED) {  // the mirror's words of the new episode, over the ones phase C has just written (k_pack_state's packing)
+        if (PACKED && NARROW) {  // the mirror's words of the new episode, over the ones phase C has just written
+          a.st.pk_hot[e] = make_uint2(pk_pack_hot(pk_rem8(ep.budget), 0u, 0u, 0u), __float_as_uint(0.0f));  // (k_pack_state's packing)
+          reinterpret_cast<uint32_t *>(a.st.pk_c)[e] = pk_narrow_word(ep.ep_row, ep.ep_w, (uint32_t)a.tb.n_samples, a.pk_kw);
+          pk_rem_of(a.st, a.n)[e] = (uint32_t)ep.budget;
+        } else if (PACKED) {
           a.st.pk_hot[e] = make_uint2(pk_pack_hot(0u, 0u, 0u, 0u), __float_as_uint(0.0f));
           a.st.pk_c[e] = make_uint2(pk_budget16((uint32_t)ep.budget) | (W_COL(ep.ep_w) << 16),
                                     (ep.ep_row & 0x3FFFFFu) | (W_SAMPLE(ep.ep_w) << 22));
@@ -419,7 +432,34 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
 // packed variant: 8 + 8 B per env, the uniform day from the tile's day word (device memory: a recorded step finds the right
 // day on every replay), the episode length from the kernel arguments; the canonical words are rebuilt in registers so
 // that the tile code is shared
+template <bool NARROW>
 __device__ __forceinline__ void s64_load_packed(const StepArgs &a, uint32_t e, uint32_t day, u3 &h, u3 &c, int32_t &act) {
+  if (NARROW) {
+    // narrow episode word: 8 + 4 B per env. c.c carries the coefficient-row index itself (s64_tile), and the pair
+    // (budget, used) is rebuilt as (remaining, 0): the step looks at it only through used == budget and budget - used2
+    // (derive_day, runtime_fields, FIXES' second run-time record), and phase A stores budget - used2 back
+    const uint32_t *ew = reinterpret_cast<const uint32_t *>(a.st.pk_c);
+#if W2A_S64_NT_STATE & 4
+    const v2u phv = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(&a.st.pk_hot[e]));
+    const uint2 ph = make_uint2(phv.x, phv.y);
+    const uint32_t w = __builtin_nontemporal_load(&ew[e]);
+#else
+    const uint2 ph = a.st.pk_hot[e];
+    const uint32_t w = ew[e];
+#endif
+    const uint32_t used = 0u;
+    c.a = PK_USED(ph.x);
+    // what the 8-bit field cannot hold (w2a_common.hip.h, PK_REM_ESCAPE) is kept as a whole word in the second half of
+    // the episode word's allocation: a rare divergent 4-B load (a budget keyword above 254, a negative one)
+    if (c.a == PK_REM_ESCAPE) c.a = pk_rem_of(a.st, a.n)[e];
+    h.a = pack_d0(day, used, PK_STREAK(ph.x), PK_HIST(ph.x) & 1u, 0u);
+    h.b = pack_d1(PK_HIST(ph.x), (uint32_t)a.uni_nd, PK_FIN(ph.x));
+    h.c = ph.y;
+    c.b = w >> a.pk_kw;
+    c.c = w & ((1u << a.pk_kw) - 1u);
+    act = load_action(a, e);
+    return;
+  }
 #if W2A_S64_NT_STATE & 4  // A/B: the mirror's words loaded non-temporally (streamed once per step: no reason to keep them in L2)
   const v2u phv = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(&a.st.pk_hot[e]));
   const v2u pcv = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(&a.st.pk_c[e]));
@@ -460,7 +500,7 @@ __device__ __forceinline__ void s64_load_state(const StepArgs &a, uint32_t e, u3
 // action streams, 28 B per env) has few bytes in flight and a full memory round trip of latency; requesting the
 // NEXT tile's words before the current tile's phases run takes that hop off the wave's critical path for every
 // tile but the first (7 more VGPRs). Measured: DESIGN.md §4.
-template <bool WRITE_OBS, bool REWARD_GIVEN, bool PACKED = false, bool AUTORESET = false, bool FIXES = false>
+template <bool WRITE_OBS, bool REWARD_GIVEN, bool PACKED = false, bool AUTORESET = false, bool FIXES = false, bool NARROW = false>
 __global__ __launch_bounds__(BLOCK, FIXES ? 3 : W2A_S64_MIN_WAVES) void k_step64(const StepArgs a) {
   __shared__ __attribute__((aligned(16))) S64WaveT<FIXES> s_w[S64_WAVES];
   const int tid = threadIdx.x;
@@ -492,7 +532,7 @@ __global__ __launch_bounds__(BLOCK, FIXES ? 3 : W2A_S64_MIN_WAVES) void k_step64
   int32_t an;
   {
     const int64_t env = wave_env0 + lane;
-    if (PACKED) s64_load_packed(a, (uint32_t)(env < a.n ? env : a.n - 1), dayn, hn, cn, an);
+    if (PACKED) s64_load_packed<NARROW>(a, (uint32_t)(env < a.n ? env : a.n - 1), dayn, hn, cn, an);
     else s64_load_state(a, (uint32_t)(env < a.n ? env : a.n - 1), hn, cn, an);
   }
   // slot -> observation column of the 4 row slots this lane owns in the row phase; requested together with the
@@ -512,10 +552,10 @@ __global__ __launch_bounds__(BLOCK, FIXES ? 3 : W2A_S64_MIN_WAVES) void k_step64
       const int64_t en = env + S64_ENVS;
       if (PACKED) {
         dayn = a.st.pk_day[(env0 + S64_ENVS) >> 6];
-        s64_load_packed(a, (uint32_t)(en < a.n ? en : a.n - 1), dayn == W2A_PK_DAY_POISON ? 0u : dayn, hn, cn, an);
+        s64_load_packed<NARROW>(a, (uint32_t)(en < a.n ? en : a.n - 1), dayn == W2A_PK_DAY_POISON ? 0u : dayn, hn, cn, an);
       } else s64_load_state(a, (uint32_t)(en < a.n ? en : a.n - 1), hn, cn, an);
     }
-    s64_tile<WRITE_OBS, REWARD_GIVEN, PACKED, AUTORESET, FIXES>(a, sw, lane, env0, valid, e, h, c, act, so);
+    s64_tile<WRITE_OBS, REWARD_GIVEN, PACKED, AUTORESET, FIXES, PACKED && NARROW>(a, sw, lane, env0, valid, e, h, c, act, so);
     // the per-wave LDS record is rewritten by the next tile
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -526,21 +566,32 @@ __global__ __launch_bounds__(BLOCK, FIXES ? 3 : W2A_S64_MIN_WAVES) void k_step64
 // canonical -> lock-step mirror (entering the packed form: once per episode) and back (before anything else reads the
 // canonical arrays). The day of a 64-env tile is that of its first env (lock step: the host packs only batches it knows
 // to be on one day); the episode length is a table constant the host passes.
-__global__ void k_pack_state(StateArrays st, int64_t n) {
+// pk_kw: the form of the episode word (StepArgs::pk_kw); n_samples: table constant of the narrow word's row index.
+__global__ void k_pack_state(StateArrays st, int64_t n, int32_t pk_kw, int32_t n_samples) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const u3 h = st.hot3[i];
   const u3 c = st.stepc[i];
-  st.pk_hot[i] = make_uint2(pk_pack_hot(D0_USED(h.a), D0_STREAK(h.a), D1_HIST(h.b), D1_FIN(h.b)), h.c);
-  st.pk_c[i] = make_uint2(pk_budget16(c.a) | (W_COL(c.c) << 16), (c.b & 0x3FFFFFu) | (W_SAMPLE(c.c) << 22));
+  if (pk_kw >= 0) {
+    const int32_t rem = (int32_t)c.a - (int32_t)D0_USED(h.a);
+    st.pk_hot[i] = make_uint2(pk_pack_hot(pk_rem8(rem), D0_STREAK(h.a), D1_HIST(h.b), D1_FIN(h.b)), h.c);
+    reinterpret_cast<uint32_t *>(st.pk_c)[i] = pk_narrow_word(c.b, c.c, (uint32_t)n_samples, pk_kw);
+    pk_rem_of(st, n)[i] = (uint32_t)rem;
+  } else {
+    st.pk_hot[i] = make_uint2(pk_pack_hot(D0_USED(h.a), D0_STREAK(h.a), D1_HIST(h.b), D1_FIN(h.b)), h.c);
+    st.pk_c[i] = make_uint2(pk_budget16(c.a) | (W_COL(c.c) << 16), (c.b & 0x3FFFFFu) | (W_SAMPLE(c.c) << 22));
+  }
   if ((i & 63) == 0) st.pk_day[i >> 6] = D0_T(h.a);
 }
-__global__ void k_unpack_state(StateArrays st, int64_t n, int32_t n_days) {
+__global__ void k_unpack_state(StateArrays st, int64_t n, int32_t n_days, int32_t pk_kw) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint2 ph = st.pk_hot[i];
   const uint32_t t = st.pk_day[i >> 6];
-  const uint32_t used = PK_USED(ph.x), hist = PK_HIST(ph.x), fin = PK_FIN(ph.x), last = hist & 1u;
+  const uint32_t hist = PK_HIST(ph.x), fin = PK_FIN(ph.x), last = hist & 1u;
+  uint32_t used = PK_USED(ph.x);
+  // narrow episode word: the field is what is left of the budget (on the escape: the whole word beside the episode words)
+  if (pk_kw >= 0) used = (uint32_t)((int32_t)st.stepc[i].a - (int32_t)(used == PK_REM_ESCAPE ? pk_rem_of(st, n)[i] : used));
   // at_budget as the last step left it (env.py:242: decided BEFORE that day's action); False after a reset
   const uint32_t atb = ((t > 0 || fin) && (int32_t)(used - last) == (int32_t)st.stepc[i].a) ? 1u : 0u;
   u3 h;

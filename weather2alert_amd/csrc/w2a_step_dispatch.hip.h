@@ -69,20 +69,29 @@ int w2a_step(w2a_env *env, const void *actions, int action_dtype, float *obs, fl
     // direction is a kernel argument, so a recorded launch keeps the one it was recorded with: consecutive recorded
     // steps still alternate, and no result depends on it.
     a.walk_rev = env->s64_launches++ & 1u;
+    a.pk_kw = -1;
     if (plan.kernel == W2A_BK_STEP_PACKED) {
       // lock-step mirror (StateArrays::pk_hot / pk_c): 20 B in and 8 B out of per-env state instead of 28 and 12
       a.uni_nd = plan.uni_nd;
-      if (autoreset) {  // a lock-step batch whose episodes restart inside the kernel (recorded loops, lockstep=False by choice)
-        if (env->tb.fixes) {
-          if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, true, true>), grid64, block, 0, s, a);
-          else hipLaunchKernelGGL((k_step64<true, false, true, true, true>), grid64, block, 0, s, a);
-        } else if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, true>), grid64, block, 0, s, a);
-        else hipLaunchKernelGGL((k_step64<true, false, true, true>), grid64, block, 0, s, a);
-      } else if (env->tb.fixes) {  // corrected-semantics flags: their own variants, the faithful kernels carry none of the code
-        if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, false, true>), grid64, block, 0, s, a);
-        else hipLaunchKernelGGL((k_step64<true, false, true, false, true>), grid64, block, 0, s, a);
-      } else if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true>), grid64, block, 0, s, a);
-      else hipLaunchKernelGGL((k_step64<true, false, true>), grid64, block, 0, s, a);
+      a.pk_kw = env->ew.narrow ? env->ew.kw : -1;  // 149 or 145 B per env-step: the episode word's form (w2a_episode_word.h)
+      // NW: the mirror's episode word is the narrow one (a template parameter: the 8-byte form's kernels stay as they were)
+#define W2A_LAUNCH_PK(NW)                                                                                                \
+      do {                                                                                                               \
+        if (autoreset) {  /* a lock-step batch whose episodes restart inside the kernel (recorded loops, lockstep=False by choice) */ \
+          if (env->tb.fixes) {                                                                                           \
+            if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, true, true, NW>), grid64, block, 0, s, a);      \
+            else hipLaunchKernelGGL((k_step64<true, false, true, true, true, NW>), grid64, block, 0, s, a);              \
+          } else if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, true, false, NW>), grid64, block, 0, s, a); \
+          else hipLaunchKernelGGL((k_step64<true, false, true, true, false, NW>), grid64, block, 0, s, a);               \
+        } else if (env->tb.fixes) {  /* corrected-semantics flags: their own variants, the faithful kernels carry none of the code */ \
+          if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, false, true, NW>), grid64, block, 0, s, a);       \
+          else hipLaunchKernelGGL((k_step64<true, false, true, false, true, NW>), grid64, block, 0, s, a);               \
+        } else if (no_obs) hipLaunchKernelGGL((k_step64<false, false, true, false, false, NW>), grid64, block, 0, s, a); \
+        else hipLaunchKernelGGL((k_step64<true, false, true, false, false, NW>), grid64, block, 0, s, a);                \
+      } while (0)
+      if (env->ew.narrow) W2A_LAUNCH_PK(true);
+      else W2A_LAUNCH_PK(false);
+#undef W2A_LAUNCH_PK
       W2A_STEP_TRY(hipGetLastError());
       bk_end_call(env->bk, dv);
       return W2A_OK;

@@ -241,6 +241,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if reward_mode == "posterior_mean" and self.pm_kernel_choice is not None:
             _ffi.check(self._lib.w2a_set_posterior_kernel(h, _ffi.PM_KERNELS[self.pm_kernel_choice]),
                        "w2a_set_posterior_kernel")
+        if self.kernel.force_wide_episode_word:
+            _ffi.check(self._lib.w2a_set_episode_word(h, 1), "w2a_set_episode_word")
         # hot-path constants (step() is called millions of times: no per-call attribute chains)
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self._obs_ptr = self._obs.data_ptr() if self.write_obs else None
@@ -329,15 +331,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
                             (_ffi.STEP_NO_CAPTURE if host_driven else 0) |
                             (_ffi.STEP_REWARD_GIVEN if self._pm else 0) |
                             (_ffi.STEP_CLASSIC if self.step_kernel == "classic" else 0) |
-                            (_ffi.STEP_WIDE if self.step_kernel == "wide" else 0) |
-                            (_ffi.STEP_UNPACKED if self.step_kernel == "unpacked" else 0) |
+                            (_ffi.STEP_WIDE if self.step_kernel in ("wide", "wide_unpacked") else 0) |
+                            (_ffi.STEP_UNPACKED if self.step_kernel in ("unpacked", "wide_unpacked") else 0) |
                             (_ffi.STEP_AUTORESET if self._dev_auto else 0) |
                             (_ffi.STEP_NEXT_STEP if self._dev_auto and self.autoreset == "next_step" else 0))
 
     @property
     def step_kernel_name(self) -> str:
         """The step kernel w2a_step launches for this env right now (mirrors the dispatch in csrc/w2a_kernels.hip)."""
-        wide = self._pm or self.step_kernel == "wide" or (self.step_kernel in ("auto", "unpacked") and
+        wide = self._pm or self.step_kernel in ("wide", "wide_unpacked") or (self.step_kernel in ("auto", "unpacked") and
                                                           self.num_envs >= _ffi.S64_MIN_ENVS)
         return "k_step64" if (wide and self.step_kernel != "classic") else "k_step"
 
@@ -354,6 +356,12 @@ class HeatAlertVecEnv(_VectorEnvBase):
         variant of the 64-envs-per-wave kernel)."""
         return bool(self._lib.w2a_query(self._h, _ffi.Q_PACKED_CURRENT)) and not bool(
             self._lib.w2a_query(self._h, _ffi.Q_CANONICAL_CURRENT))
+
+    @property
+    def episode_word_bytes(self) -> int:
+        """Bytes per env of the lock-step mirror's per-episode word on this handle: 4 (both row indices in one word, the
+        library's choice wherever the table dims allow it) or 8 (csrc/w2a_episode_word.h)."""
+        return int(self._lib.w2a_query(self._h, _ffi.Q_EPISODE_WORD_BYTES))
 
     @property
     def last_rollout_kernel(self) -> str | None:

@@ -12,8 +12,9 @@ class KernelOptions:
     # "auto": batches of >= 131 072 envs run the 64-envs-per-wave kernel (csrc/w2a_step64.hip.h; in-kernel autoreset
     # included), smaller ones the 4-lanes-per-env kernel (the faster choice at each size); "classic" / "wide" force one
     # of them. While the batch is in lock step the 64-envs-per-wave kernel streams a 16-B packed mirror of the per-env
-    # state instead of the 24-B canonical words (include/w2a.h, w2a_state_bytes); "unpacked" = "auto" without it.
-    step_kernel: Literal["auto", "classic", "wide", "unpacked"] = "auto"
+    # state instead of the 24-B canonical words (include/w2a.h, w2a_state_bytes); "unpacked" = "auto" without it,
+    # "wide_unpacked" = "wide" without it (the mirror's bit-for-bit twin at batch sizes "unpacked" gives to the other kernel).
+    step_kernel: Literal["auto", "classic", "wide", "unpacked", "wide_unpacked"] = "auto"
     # False: reward-only steps (no observation rows written)
     write_obs: bool = True
     # "gather": each step gathers the env's coefficient rows and sums the 28 terms. ("table", round 1's precomputed
@@ -34,9 +35,12 @@ class KernelOptions:
     # row, k_reset that writes every index the episode of its source env: no record is moved); "relabel" = round 5's
     # sequence w2a_reset_device_rng + w2a_sort_episodes (state permutation, three copies) + w2a_observe. Bit-identical.
     sorted_reset: Literal["fused", "relabel"] = "fused"
+    # debug / A-B only: keep the lock-step mirror's 8-byte per-episode word on tables whose row indices would fit the
+    # 4-byte one (csrc/w2a_episode_word.h; the wide word is otherwise reached only by tables too large for a quick test)
+    force_wide_episode_word: bool = False
 
     def __post_init__(self):
-        if self.step_kernel not in ("auto", "classic", "wide", "unpacked"):
+        if self.step_kernel not in ("auto", "classic", "wide", "unpacked", "wide_unpacked"):
             raise ValueError(f"step_kernel {self.step_kernel!r}")
         if self.reward_path == "table":
             raise ValueError("reward_path='table' (the precomputed logit table of round 1) was removed: it was slower "
