@@ -42,9 +42,20 @@ __device__ const float4 *g_W8;    // [S * 100][2] float4
                       // instead of three, twice the gathered bytes in flight), one 64-env observation flush
 #define P_PASSES 1
 #define P_ROUNDS 8
-#else
+#define P_ISSUE 8
+#elif defined(PROBE_ONEPASS_2FLUSH)  // k_step64's skeleton since profiles/r26: the rows of all 8 rounds requested before the
+                                     // first wait and consumed before the first store, then two 32-env flushes from the
+                                     // same 4 KB tile. NOT what bench.py loads: with -DPROBE_F64 this kernel needs 128 VGPRs
+                                     // + 44 B of scratch (the real kernel: 106, none) and took 45.2 us where k_step64 took
+                                     // 32.9 us -- it prices its own spills, not the access pattern
 #define P_PASSES 2
 #define P_ROUNDS 4
+#define P_ISSUE 8
+#else  // 4 rounds requested per pass, the second pass's gathers behind the first flush (three dependent memory hops per
+       // wave): k_step64 until profiles/r26, and still its reward-only and FIXES instantiations
+#define P_PASSES 2
+#define P_ROUNDS 4
+#define P_ISSUE 4
 #endif
 #define P_PASS_ENVS (P_ROUNDS * 8)
 #ifdef PROBE_LIB
@@ -133,11 +144,11 @@ __global__ __launch_bounds__(256, 4) void k_probe(const u3 *hot, const u3 *stepc
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #endif
-  for (int pass = 0; pass < P_PASSES; ++pass) {
-    float4 x[P_ROUNDS], w[P_ROUNDS];
+  for (int pass0 = 0; pass0 < P_PASSES; pass0 += P_ISSUE / P_ROUNDS) {
+    float4 x[P_ISSUE], w[P_ISSUE];
 #pragma unroll
-    for (int r = 0; r < P_ROUNDS; ++r) {
-      const uint32_t j = (uint32_t)env0 + pass * P_PASS_ENVS + r * 8 + g;
+    for (int r = 0; r < P_ISSUE; ++r) {
+      const uint32_t j = (uint32_t)env0 + pass0 * P_PASS_ENVS + r * 8 + g;
       x[r] = make_float4(1.f, 2.f, 3.f, 4.f);
 #ifdef PROBE_RANDOM_DATA  // stream-only mode too writes values that do not repeat
       {
@@ -150,7 +161,7 @@ __global__ __launch_bounds__(256, 4) void k_probe(const u3 *hot, const u3 *stepc
       w[r] = x[r];
       if (GATHER) {
 #ifdef PROBE_DEP
-        const uint2 dd = desc[wave][pass * P_PASS_ENVS + r * 8 + g];
+        const uint2 dd = desc[wave][pass0 * P_PASS_ENVS + r * 8 + g];
         x[r] = X[dd.x * 8 + p];
 #if defined(PROBE_ZSTREAM) || defined(PROBE_TABLE)
         w[r] = x[r];
@@ -166,8 +177,9 @@ __global__ __launch_bounds__(256, 4) void k_probe(const u3 *hot, const u3 *stepc
 #endif
       }
     }
+    // (as in k_step64: every requested row is consumed before the first store of a flush leaves)
 #pragma unroll
-    for (int r = 0; r < P_ROUNDS; ++r) {
+    for (int r = 0; r < P_ISSUE; ++r) {
 #ifdef PROBE_F64  // the step kernel's arithmetic: two 4-term fp64 chains and an 8-lane fp64 all-reduce per env
       {
         double zb = (double)x[r].x * (double)w[r].x, ze = (double)x[r].x * (double)w[r].y;
@@ -183,12 +195,17 @@ __global__ __launch_bounds__(256, 4) void k_probe(const u3 *hot, const u3 *stepc
 #else
       acc += x[r].x * w[r].x + x[r].y * w[r].y + x[r].z * w[r].z + x[r].w * w[r].w;
 #endif
-      if (STREAM) {
-        float *t = tile[wave] + (r * 8 + g) * 29 + p * 4;
+    }
+#pragma unroll
+    for (int sub = 0; sub < P_ISSUE / P_ROUNDS; ++sub) {
+    const int pass = pass0 + sub;
+    if (STREAM) {
+#pragma unroll
+      for (int rr = 0; rr < P_ROUNDS; ++rr) {
+        const int r = sub * P_ROUNDS + rr;
+        float *t = tile[wave] + (rr * 8 + g) * 29 + p * 4;
         if (p < 7) { t[0] = x[r].x; t[1] = x[r].y; t[2] = x[r].z; t[3] = x[r].w; } else t[0] = x[r].x;
       }
-    }
-    if (STREAM) {
       __builtin_amdgcn_wave_barrier();
       float *dst = obs + (env0 + pass * P_PASS_ENVS) * 29;
       for (int c0 = 0; c0 < P_PASS_ENVS * 8; c0 += 64) {
@@ -196,6 +213,7 @@ __global__ __launch_bounds__(256, 4) void k_probe(const u3 *hot, const u3 *stepc
         if (ch < P_PASS_ENVS * 29 / 4) __builtin_nontemporal_store(reinterpret_cast<const v4f *>(tile[wave])[ch], reinterpret_cast<v4f *>(dst) + ch);
       }
       __builtin_amdgcn_wave_barrier();
+    }
     }
   }
   // lane = env outputs

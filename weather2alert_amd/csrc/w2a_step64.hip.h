@@ -10,11 +10,14 @@
 // changes its lane <-> env mapping between phases:
 //   A  lane = env          state + action loads (three fully coalesced streams: 768 + 768 + 256 B per wave),
 //                          budget gate / history / termination once per env, descriptors to LDS
-//   B  8 lanes = one row   two passes of 4 rounds; a round serves 8 envs, lane p of a group owns floats 4p..4p+3
-//                          of the env's 128-B feature row and coefficient row(s): every gather instruction covers
-//                          8 whole lines, a pass has 8..12 of them in flight per lane. fp64 FMA, DPP all-reduce
-//                          over the 8 lanes, logits to LDS; the lanes scatter their row fragment into the packed
-//                          observation tile (reference column order), flushed per pass as coalesced 16-B stores
+//   B  8 lanes = one row   8 rounds; a round serves 8 envs, lane p of a group owns floats 4p..4p+3 of the env's 128-B
+//                          feature row and baseline coefficient row: every gather instruction covers 8 whole lines.
+//                          ONE gather pass: the 16 row requests of the tile leave before the first wait and are all
+//                          consumed before the first store (s64_issue_rounds: a few instantiations keep two passes
+//                          of 4 rounds). Effectiveness rows only for the envs that need one, from a compact per-tile
+//                          list, 8 envs per list round. fp64 FMA, DPP all-reduce over the 8 lanes, logits to LDS; the
+//                          lanes scatter their row fragment into the packed observation tile (reference column
+//                          order), flushed per 32 envs as coalesced 16-B stores
 //   C  lane = env          sigmoid, reward, return accumulator; reward / done / state written as whole lines
 // What is computed is identical to k_step<false, WRITE_OBS, false, false> up to the order of the fp64 additions
 // (4-term chains + 8-lane tree instead of 8-term chains + 4-lane tree: ~1e-16 relative on the logits).
@@ -24,7 +27,8 @@
 #define S64_ENVS 64                 // envs per wave
 #define S64_WAVES (BLOCK / 64)
 #define S64_PASS_ENVS 32            // envs per observation flush (4 rounds of 8)
-#define S64_ROUNDS 4
+#define S64_ROUNDS 4                // rounds per observation flush
+#define S64_LIST_ROUNDS 4           // effectiveness-list rounds per trip of the loop behind the first one (s64_tile)
 
 // env.py:242-256 for one env from its packed state and today's action: budget gate, history, termination.
 // Shared by k_step64 and k_posterior_mean (which must agree on `actual` and the run-time fields).
@@ -71,6 +75,7 @@ struct S64WaveT {
   float4 rt[S64_ENVS];              // run-time fields alert_lag1, alert_streak, remaining_budget, alert_2wks (slots 24..27)
   float4 rt2[FIXES ? S64_ENVS : 1]; // FIXES / W2A_FIX_OBS: the same fields as the NEXT day's observation shows them
   float2 z[S64_ENVS];               // {(float) baseline logit, (float) effectiveness logit (-inf: gate closed)}
+  uint8_t elist[S64_ENVS];          // the tile's envs that need their effectiveness row today, compact, in lane order
   float tile[S64_PASS_ENVS * ROWF]; // packed observation rows of one pass (+ scratch words behind them)
 };
 
@@ -79,9 +84,6 @@ struct S64WaveT {
 // streamed outputs do not evict the coefficient rows the gathers want to find there. 0 = nt observation stores.
 #ifndef W2A_S64_SC1
 #define W2A_S64_SC1 0
-#endif
-#ifndef W2A_S64_SKIP_EFF
-#define W2A_S64_SKIP_EFF 1  // skip the effectiveness dot product in rounds where no env alerts today (A/B)
 #endif
 #ifndef W2A_S64_NT_STATE
 #define W2A_S64_NT_STATE 0  // A/B: bit 0 = hot3, bit 1 = stepc, bit 2 = the packed mirror's words loaded non-temporally
@@ -130,6 +132,15 @@ __device__ __forceinline__ uint32_t logical_block_rev(uint32_t b, uint32_t per_x
   return 8u * per_xcd - 1u - b;
 #endif
 }
+// Gather rounds a wave requests before its first wait (s64_tile, phase B): 8 = one pass per tile, 4 = two.
+template <bool WRITE_OBS, bool REWARD_GIVEN, bool AUTORESET, bool FIXES>
+__host__ __device__ constexpr int s64_issue_rounds() {
+  // Two passes where one would cost a wave per SIMD (tools/kernel_resources.py): the reward-only
+  // instantiations (no tile: 86-92 VGPRs and 5 waves per SIMD with 4 rounds in flight, 96-102 and 4 with 8), and FIXES with
+  // observations, which keeps a third row (xo) per round in flight (131-132 VGPRs and 3 waves instead of 128 and 4) --
+  // except with the in-kernel autoreset, where it has 3 waves per SIMD either way.
+  return (!WRITE_OBS || (FIXES && !AUTORESET)) ? S64_ROUNDS : 2 * S64_ROUNDS;
+}
 // One 64-env tile of one wave, phases A..C, from the tile's already loaded state words and action.
 // REWARD_GIVEN: a.reward already holds today's reward (w2a_posterior_mean_reward ran on the same state and actions):
 // no coefficient gather and no logits here, the rest of env.py:238-262 as usual.
@@ -170,6 +181,13 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
   uint32_t need_eff = actual;
   if (a.tb.gate_bits && actual)
     need_eff = (a.tb.gate_bits[t * (uint32_t)a.tb.gate_words + (c.b >> 5)] >> (c.b & 31u)) & 1u;
+  // About 6 % of the envs need the row, so it stays off the common path of phase B: the needing envs of the tile go into a
+  // compact list (lane numbers in lane order; a clamp lane that shadows the last env may stand in it, which is harmless)
+  // that phase B serves 8 envs per round behind its main gathers.
+  const unsigned long long eff_mask = REWARD_GIVEN ? 0ull : __ballot(need_eff != 0u);
+  const int n_eff = __popcll(eff_mask);  // wave-uniform
+  if (!REWARD_GIVEN && need_eff)
+    sw.elist[__builtin_amdgcn_mbcnt_hi((uint32_t)(eff_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)eff_mask, 0u))] = (uint8_t)lane;
   {
     // feature row of day t (pre-increment, Q6) and the env's coefficient rows, as float4 indices (32-bit: table
     // sizes are validated in w2a_create). The effectiveness row is fetched only on alert days (k_step).
@@ -190,45 +208,83 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
 
   // ---------------------------------------------------------------- phase B: 8 lanes = one 128-B row
   const int p = lane & 7;   // float4 of the row owned by this lane
-  const int g = lane >> 3;  // row group: env j = pass * 32 + round * 8 + g of the wave
+  const int g = lane >> 3;  // row group: env j = round * 8 + g of the wave (rounds 0..7)
   const int n_obs = a.tb.n_obs;
   // a finished env keeps its stale observation (env.py:257-262, Q6); W2A_FIX_OBS writes the last row instead
   const bool write_me = valid && (!done || fix_obs) && !restart_in;
   const uint32_t next_day = (uint32_t)(a.tb.S_w * a.tb.Y) * (ROWF / 4);  // float4 index distance to the next day's row
+  // Rounds whose feature and baseline rows are requested before the first wait. 8: the whole tile in ONE gather pass, the
+  // rounds of the second flush land while the first half is computed and flushed (64 VGPRs of rows in flight). 4: a second
+  // pass behind the first flush, one more dependent memory round trip per wave, for the instantiations that 8 would cost
+  // a wave per SIMD.
+  constexpr int NI = s64_issue_rounds<WRITE_OBS, REWARD_GIVEN, AUTORESET, FIXES>();
+  // One round of the effectiveness list: group g serves list entry idx = 8 k + g, lane p floats 4p..4p+3 of the env's
+  // feature row (requested again: the line is in L1 / L2 or still in flight) and of its effectiveness row. Branch-free:
+  // groups past the end of the list re-request the rows of env g, which round 0 has in flight (no extra fabric traffic),
+  // and their value is dropped. A conditional load would make the compiler wait for it (s_waitcnt vmcnt(0)) at the end of
+  // its branch.
+  auto eff_issue = [&](const int idx, float4 &xe, float4 &we, int &je) {
+    const bool has = idx < n_eff;
+    je = has ? (int)sw.elist[idx & (S64_ENVS - 1)] : g;
+    const uint2 ds = sw.desc[je];
+    xe = a.tb.X[(ds.x & 0x7FFFFFFFu) + p];
+    we = a.tb.W[(ds.y & 0x7FFFFFFFu) + (has ? ROWF / 4 : 0) + p];
+  };
+  // ... and its logit: the 4-term chain, gate and 8-lane tree of the row's own round (the same bits as when every round
+  // carried its effectiveness row)
+  auto eff_logit = [&](const int idx, float4 xe, const float4 we, const int je) {
+    if (p == RT_QUAD) xe = sw.rt[je];
+    if (FIXES && (fx & W2A_FIX_ALERTS_2WKS) && a.tb.slot_hist2w >= 0 && p == (a.tb.slot_hist2w >> 2))
+      set_comp4(xe, a.tb.slot_hist2w & 3, sw.rt[je].w);  // (Q1, as in the row's own round below)
+    double ze = (double)xe.x * (double)we.x;
+    ze = fma((double)xe.y, (double)we.y, ze);
+    ze = fma((double)xe.z, (double)we.z, ze);
+    ze = fma((double)xe.w, (double)we.w, ze);
+    // effectiveness gate heat_qi > 0.5 (env.py:218): slot 30 holds the 0/1 flag with a zero coefficient; a
+    // closed gate drives the logit to -inf so that the sigmoid is exactly 0
+    if (p == GATE_QUAD && !(xe.z > 0.5f)) ze = -__builtin_inf();
+    ze += dpp_f64<0xB1>(ze);
+    ze += dpp_f64<0x4E>(ze);
+    ze += dpp_f64<0x141>(ze);
+    if (p == 0 && idx < n_eff) sw.z[je].y = (float)ze;
+  };
+  // The first list round is unconditional and requested with the main gathers, before the first wait: between the rows
+  // of rounds 0..3 and those of rounds 4..7 in the one-pass body (72 VGPRs of rows in flight), in front of pass 0 in the
+  // two-pass body. Its logit is formed with those of the main rounds, before the first flush.
+  float4 lx0 = make_float4(0.f, 0.f, 0.f, 0.f), lw0 = lx0;
+  int lj0 = 0;
+  if (!REWARD_GIVEN && NI < 2 * S64_ROUNDS) eff_issue(g, lx0, lw0, lj0);
 #pragma unroll 1
-  for (int pass = 0; pass < S64_ENVS / S64_PASS_ENVS; ++pass) {
-    if (REWARD_GIVEN && !WRITE_OBS) break;               // nothing to gather at all
-    if (wave_env0 + pass * S64_PASS_ENVS >= a.n) break;  // wave-uniform
-    float4 x[S64_ROUNDS], wb[S64_ROUNDS], we[S64_ROUNDS], xo[FIXES ? S64_ROUNDS : 1];
-    bool need[S64_ROUNDS], nxt[S64_ROUNDS];
+  for (int r0 = 0; r0 < S64_ENVS / 8; r0 += NI) {
+    if (REWARD_GIVEN && !WRITE_OBS) break;    // nothing to gather at all
+    if (wave_env0 + r0 * 8 >= a.n) break;     // wave-uniform
+    float4 x[NI], wb[NI], xo[FIXES ? NI : 1];
+    bool nxt[NI];
+    // (lanes past the end of a ragged tile shadow the last env: every descriptor of the tile is valid)
 #pragma unroll
-    for (int r = 0; r < S64_ROUNDS; ++r) {
-      uint2 ds = sw.desc[pass * S64_PASS_ENVS + r * 8 + g];
-      need[r] = (ds.y >> 31) != 0u;
+    for (int r = 0; r < NI; ++r) {
+      uint2 ds = sw.desc[(r0 + r) * 8 + g];
       nxt[r] = FIXES && (ds.x >> 31) != 0u;
       if (FIXES) ds.x &= 0x7FFFFFFFu;
-      const uint32_t wq = ds.y & 0x7FFFFFFFu;
       x[r] = a.tb.X[ds.x + p];
       // W2A_FIX_OBS: the row the observation shows (the next day's; the same line again where it is today's)
       if (fix_obs) xo[r] = a.tb.X[ds.x + (nxt[r] ? next_day : 0u) + p];
-      wb[r] = we[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (!REWARD_GIVEN) {
-        wb[r] = a.tb.W[wq + p];
-        // branch-free: groups that do not need the effectiveness row re-request their baseline line (already in
-        // flight, no extra fabric traffic) and the value is dropped below. A conditional load would make the
-        // compiler wait for it (s_waitcnt vmcnt(0)) at the end of its branch, before the next round's loads issue:
-        // one exposed memory round trip per round with an alert.
-        we[r] = a.tb.W[wq + (need[r] ? ROWF / 4 : 0) + p];
-      }
+      wb[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!REWARD_GIVEN) wb[r] = a.tb.W[(ds.y & 0x7FFFFFFFu) + p];
+      if (!REWARD_GIVEN && NI == 2 * S64_ROUNDS && r == S64_ROUNDS - 1) eff_issue(g, lx0, lw0, lj0);
     }
 #if W2A_S64_PRIO
     // waves whose gathers are in flight or have landed are issued ahead of waves still in phase A: the rows they hold are
     // turned into stores sooner (measured: iid 34.4 -> 34.0 us, sorted 30.9 -> 30.3 us, always-alert 46.3 -> 44.5 us)
     __builtin_amdgcn_s_setprio(W2A_S64_PRIO);
 #endif
+    // Every requested row is consumed BEFORE the first observation store leaves: vmcnt counts loads and stores alike, so a
+    // row waited for behind a flush would also wait for that flush's stores to be acknowledged -- the dependent round trip
+    // the single pass is there to remove. Hence: the logits of all NI rounds (and of the first list round), then per 32
+    // envs the scatter into the tile and its flush, with no load outstanding.
 #pragma unroll
-    for (int r = 0; r < S64_ROUNDS; ++r) {
-      const int j = pass * S64_PASS_ENVS + r * 8 + g;
+    for (int r = 0; r < NI; ++r) {
+      const int j = (r0 + r) * 8 + g;
       if (p == RT_QUAD) x[r] = sw.rt[j];
       if (FIXES && (fx & W2A_FIX_ALERTS_2WKS) && a.tb.slot_hist2w >= 0) {
         // the agent's 14-day count also replaces the historical 'alerts_2wks' column, so it feeds the reward (Q1)
@@ -238,7 +294,8 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
       }
       if (fix_obs && p == RT_QUAD) xo[r] = nxt[r] ? sw.rt2[FIXES ? j : 0] : sw.rt[j];
       if (!REWARD_GIVEN) {
-      // env.py:207-217: two 28-term dot products, fp64 accumulation (products of f32 values are exact in fp64)
+      // env.py:207-217: the baseline's 28-term dot product, fp64 accumulation (products of f32 values are exact in
+      // fp64); the effectiveness logit of the few envs that need one comes from the list rounds (eff_logit)
       const double x0 = (double)x[r].x, x1 = (double)x[r].y, x2 = (double)x[r].z, x3 = (double)x[r].w;
       double zb = x0 * (double)wb[r].x;
       zb = fma(x1, (double)wb[r].y, zb);
@@ -247,28 +304,20 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
       zb += dpp_f64<0xB1>(zb);   // lane ^ 1
       zb += dpp_f64<0x4E>(zb);   // lane ^ 2
       zb += dpp_f64<0x141>(zb);  // row_half_mirror: the other quad of the 8-lane group
-      double ze = 0.0;
-#if W2A_S64_SKIP_EFF
-      if (__any(need[r]))  // wave-uniform: most rounds have no alert today (eff * actual = 0 whatever eff is)
-#endif
-      {
-        // groups without need carry their baseline row here: harmless, their ze is never used (phase C)
-        ze = x0 * (double)we[r].x;
-        ze = fma(x1, (double)we[r].y, ze);
-        ze = fma(x2, (double)we[r].z, ze);
-        ze = fma(x3, (double)we[r].w, ze);
-        // effectiveness gate heat_qi > 0.5 (env.py:218): slot 30 holds the 0/1 flag with a zero coefficient; a
-        // closed gate drives the logit to -inf so that the sigmoid is exactly 0
-        if (p == GATE_QUAD && !(x[r].z > 0.5f)) ze = -__builtin_inf();
-        ze += dpp_f64<0xB1>(ze);
-        ze += dpp_f64<0x4E>(ze);
-        ze += dpp_f64<0x141>(ze);
+      if (p == 0) sw.z[j].x = (float)zb;
       }
-      if (p == 0) sw.z[j] = make_float2((float)zb, (float)ze);
-      }
+    }
+    if (!REWARD_GIVEN && r0 == 0) eff_logit(g, lx0, lw0, lj0);
+#pragma unroll
+    for (int half = 0; half < NI / S64_ROUNDS; ++half) {
+    const int e_off = (r0 + half * S64_ROUNDS) * 8;  // first env of this flush within the tile: 0 or 32
+    if (half > 0 && wave_env0 + e_off >= a.n) break;  // wave-uniform: a ragged tile without a second half
+#pragma unroll
+    for (int rr = 0; rr < S64_ROUNDS; ++rr) {
+      const int r = half * S64_ROUNDS + rr;
       if (WRITE_OBS) {
         // branch-free scatter into the packed tile; slots that are not observation columns go to scratch words
-        const int base = (r * 8 + g) * n_obs;
+        const int base = (rr * 8 + g) * n_obs;
         const int trash = S64_PASS_ENVS * n_obs + (lane & 31);
         const float4 ov = fix_obs ? xo[FIXES ? r : 0] : x[r];
         sw.tile[so.x >= 0 ? base + so.x : trash] = ov.x;
@@ -281,11 +330,11 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int64_t env0 = wave_env0 + pass * S64_PASS_ENVS;
+      const int64_t env0 = wave_env0 + e_off;
       float *dst = reinterpret_cast<float *>(a.obs) + env0 * n_obs;
-      // which envs of this pass write: their phase-A lanes are pass*32 .. pass*32+31
+      // which envs of this flush write: their phase-A lanes are e_off .. e_off+31
       const unsigned long long wm_all = __ballot(write_me);
-      const uint32_t wm = (uint32_t)(wm_all >> (pass * S64_PASS_ENVS));
+      const uint32_t wm = (uint32_t)(wm_all >> e_off);
       const bool full = env0 + S64_PASS_ENVS <= a.n;
       if (full && wm == 0xFFFFFFFFu) {
         const int chunks = (S64_PASS_ENVS * n_obs) >> 2;  // 32 * n_obs floats: a multiple of 4
@@ -312,15 +361,28 @@ __device__ __forceinline__ void s64_tile(const StepArgs &a, S64WaveT<FIXES> &sw,
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();  // the tile is rewritten by the next pass
+      __builtin_amdgcn_wave_barrier();  // the tile is rewritten by the next flush
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+    }
   }
-  if (!WRITE_OBS) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (!REWARD_GIVEN) {
+    // More than 8 needing envs in the tile (about one tile in fifty under an iid 6 %; every tile under an always-alert
+    // policy): S64_LIST_ROUNDS further rounds per trip, requested together, behind both flushes -- one more memory round
+    // trip per trip, paid only by the tiles that have the rows to fetch.
+#pragma unroll 1
+    for (int k0 = 8; k0 < n_eff; k0 += 8 * S64_LIST_ROUNDS) {  // wave-uniform
+      float4 lx[S64_LIST_ROUNDS], lw[S64_LIST_ROUNDS];
+      int lj[S64_LIST_ROUNDS];
+#pragma unroll
+      for (int r = 0; r < S64_LIST_ROUNDS; ++r) eff_issue(k0 + r * 8 + g, lx[r], lw[r], lj[r]);
+#pragma unroll
+      for (int r = 0; r < S64_LIST_ROUNDS; ++r) eff_logit(k0 + r * 8 + g, lx[r], lw[r], lj[r]);
+    }
   }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();  // phase C reads the logits lane = env
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
 #if W2A_S64_PRIO
   __builtin_amdgcn_s_setprio(0);
