@@ -1075,6 +1075,69 @@ int w2a_q_gradient_mlp(w2a_env *env, const w2a_mlp_policy *q, const w2a_mlp_poli
                        int32_t double_q, int32_t loss, double huber_delta, int32_t bootstrap, float *td_error,
                        float *td_target, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Lookahead: learned policies that see the coming days' weather (the older reference env's incorp_forecasts / "D3" /
+ * "D10" inputs with zero forecast error; additions to ABI 18, nothing above changes). The row an agent holds on env day
+ * t is the table row of day r = max(t - 1, 0) (Q6). The w2a_lookahead_* entry points give its decision `days` more inputs
+ *     f_k = h(r + k) - h(r),   k = 1 .. days,       f_k = 0 where r + k >= n_days of that env,
+ * h(d) the f32 value of one table-sourced feature on day d of the env's episode, the difference one f32 subtraction.
+ *   series  device f32 [S_w * Y][stride]: h of every feature row (county_w * Y + year_i), one episode's days
+ *           contiguous (the feature's column of X, transposed); stride >= T floats
+ *   days    1 .. W2A_LOOKAHEAD_MAX_DAYS
+ *   weight  linear kind: device f32 [n_groups][W2A_LOOKAHEAD_PAD], k = 1 first, entries past `days` ignored. The logit
+ *           is w2a_rollout_linear's fp64 chain (bias, slots 0..29) continued by `days` more fp64 FMAs in order of k.
+ *           mlp kind: NULL; every block of `params` has W2A_MLP_LOOKAHEAD_STRIDE floats, the block above with
+ *           W1f[W2A_LOOKAHEAD_PAD][width] appended (row k - 1: input f_k, zero past `days` and past the real width),
+ *           and nothing before the tail moves. The first layer runs its 8 k-steps over the slots and then
+ *           ceil(days / 4) more over the lookahead inputs, in that order.
+ * The first decision's inputs are rebuilt from the state and `series` on entry, so calls of k and S - k days equal one
+ * of S days; with all lookahead weights zero every output, the state and obs are the bits of the call without them.
+ * w2a_lookahead_rollout_linear / w2a_lookahead_rollout_mlp take w2a_rollout_linear's / w2a_rollout_mlp's arguments
+ * and the block; the _gated forms also the gate of w2a_rollout_*_gated. No trajectory is recorded.
+ * w2a_lookahead_policy_gradient_linear and w2a_lookahead_imitation_gradient_linear take the arguments of
+ * w2a_policy_gradient_linear_gated / w2a_imitation_gradient_linear_gated with allowed_days nullable (NULL: no gate);
+ * grad is f32 [n_obs + 1 + days][num_envs], the lookahead inputs' rows after the bias row, k = 1 first.
+ * W2A_ERR_ARG where the entry point without lookahead refuses, then for a NULL block or series, days outside the
+ * range, stride < T and (linear) a NULL weight. */
+#define W2A_LOOKAHEAD_MAX_DAYS 10
+#define W2A_LOOKAHEAD_PAD 12
+#define W2A_MLP_LOOKAHEAD_STRIDE(width, n_layers) (W2A_MLP_STRIDE(width, n_layers) + W2A_LOOKAHEAD_PAD * (width))
+typedef struct w2a_lookahead {
+  const float *series;
+  int32_t stride;
+  int32_t days;
+  const float *weight;
+} w2a_lookahead;
+int w2a_lookahead_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                                 float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                 uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words, float *last_return,
+                                 float *ret_snapshot, void *stream, const w2a_lookahead *lookahead);
+int w2a_lookahead_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                                       float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                       uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words,
+                                       float *last_return, float *ret_snapshot, void *stream,
+                                       const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                       int32_t allowed_words);
+int w2a_lookahead_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                              int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                              uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                              void *stream, const w2a_lookahead *lookahead);
+int w2a_lookahead_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs,
+                                    float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                    uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words,
+                                    float *last_return, float *ret_snapshot, void *stream,
+                                    const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                    int32_t allowed_words);
+int w2a_lookahead_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline,
+                                         int32_t n_steps, const float *obs, float *grad, void *workspace,
+                                         size_t workspace_bytes, void *stream, const w2a_lookahead *lookahead,
+                                         const uint32_t *allowed_days, int32_t allowed_words);
+int w2a_lookahead_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                            int32_t mask_words, const float *env_weight, const float *day_weight,
+                                            int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                            float *loglik, int32_t *days, void *stream,
+                                            const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                            int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

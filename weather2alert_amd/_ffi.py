@@ -41,6 +41,9 @@ SYMBOLS = [
     "w2a_fisher_vector_product_linear", "w2a_fisher_vector_product_mlp_workspace_bytes",
     "w2a_fisher_vector_product_mlp",
     "w2a_q_gradient_mlp_workspace_bytes", "w2a_q_gradient_mlp",
+    "w2a_lookahead_rollout_linear", "w2a_lookahead_rollout_linear_gated", "w2a_lookahead_rollout_mlp",
+    "w2a_lookahead_rollout_mlp_gated", "w2a_lookahead_policy_gradient_linear",
+    "w2a_lookahead_imitation_gradient_linear",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -64,6 +67,11 @@ class MlpPolicy(C.Structure):
     _fields_ = [("params", C.c_void_p), ("group", C.c_void_p), ("order", C.c_void_p), ("n_groups", C.c_int32),
                 ("n_layers", C.c_int32), ("width", C.c_int32), ("activation", C.c_int32), ("sample", C.c_int32),
                 ("require_budget", C.c_int32), ("seed", C.c_uint64)]
+
+
+class Lookahead(C.Structure):
+    """w2a_lookahead: the series table, its stride, D and (linear kind) the lookahead weights [G][12]."""
+    _fields_ = [("series", C.c_void_p), ("stride", C.c_int32), ("days", C.c_int32), ("weight", C.c_void_p)]
 
 
 MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}  # W2A_MLP_TANH, W2A_MLP_RELU
@@ -287,6 +295,19 @@ def load(build_if_missing: bool = True):
                                        vp, C.c_double, i32, i32, C.c_double, i32, vp, vp, vp, C.c_size_t, vp]
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
+    look = [C.POINTER(Lookahead)]
+    lib.w2a_lookahead_rollout_linear.restype = C.c_int
+    lib.w2a_lookahead_rollout_linear.argtypes = lib.w2a_rollout_linear.argtypes + look
+    lib.w2a_lookahead_rollout_linear_gated.restype = C.c_int
+    lib.w2a_lookahead_rollout_linear_gated.argtypes = lib.w2a_rollout_linear.argtypes + look + [vp, i32]
+    lib.w2a_lookahead_rollout_mlp.restype = C.c_int
+    lib.w2a_lookahead_rollout_mlp.argtypes = lib.w2a_rollout_mlp.argtypes + look
+    lib.w2a_lookahead_rollout_mlp_gated.restype = C.c_int
+    lib.w2a_lookahead_rollout_mlp_gated.argtypes = lib.w2a_rollout_mlp.argtypes + look + [vp, i32]
+    lib.w2a_lookahead_policy_gradient_linear.restype = C.c_int
+    lib.w2a_lookahead_policy_gradient_linear.argtypes = lib.w2a_policy_gradient_linear.argtypes + look + [vp, i32]
+    lib.w2a_lookahead_imitation_gradient_linear.restype = C.c_int
+    lib.w2a_lookahead_imitation_gradient_linear.argtypes = lib.w2a_imitation_gradient_linear_weighted.argtypes + look + [vp, i32]
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

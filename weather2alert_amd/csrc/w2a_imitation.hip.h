@@ -34,7 +34,8 @@ struct ImitationArgs {
 struct ImLinearArgs {
   LinearRolloutArgs l;   // as w2a_rollout_linear builds it (r.pol: require_budget only); l.obs is only read
   ImitationArgs im;
-  float *grad;           // [n_obs + 1][n] per-env gradient: observation column j of env e at j * n + e, bias last
+  float *grad;           // [n_obs + 1][n] per-env gradient: observation column j of env e at j * n + e, bias last;
+                         // LOOK: [n_obs + 1 + D][n], lookahead input k at row n_obs + k (k = 1..D, after the bias)
 };
 
 struct ImMlpArgs {
@@ -73,7 +74,10 @@ __device__ __forceinline__ double im_log_pi(double z, uint32_t a) {
 // Registers: the policy row (32 f32), xv[] and 31 fp64 accumulators; two waves per SIMD leave 256 VGPRs.
 // GATE (w2a_imitation_gradient_linear_gated): ia.l.gate restricts the attempts; an alert the schedule asks for on a
 // disallowed day is attempted as 0 and the day is not scored. GATE = false compiles from the statements it had before.
-template <bool GATE>
+// LOOK (w2a_lookahead_imitation_gradient_linear; GATE when its nullable allowed_days is given): the logit chain goes on over the lookahead inputs of
+// the held row's day, as k_rollout_linear<.., LOOK>, and D more fp64 accumulators take c f_k. LOOK = false compiles
+// from the statements it had before.
+template <bool GATE, bool LOOK = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArgs ia) {
   const LinearRolloutArgs &la = ia.l;
   const RolloutArgs &a = la.r;
@@ -91,6 +95,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
   const uint32_t obs0 = e * (uint32_t)la.n_obs;
   const size_t n = (size_t)a.n;
   float wp[32];
+  float lw[W2A_LOOK_MAX], lf[W2A_LOOK_MAX];
   {
     int32_t g = la.group ? la.group[e] : 0;
     g = g < 0 ? 0 : (g >= la.n_groups ? la.n_groups - 1 : g);
@@ -103,7 +108,13 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
 #pragma unroll
     for (int k = 0; k < 32; ++k) wp[k] = ((la.obs_mask >> k) & 1u) ? wp[k] : 0.0f;
     wp[31] = la.bias[g];  // the bias rides in slot 31, as in k_rollout_linear
+    if constexpr (LOOK) look_weights(la.look, g, lw);
   }
+  const float *lser = nullptr;
+  if constexpr (LOOK) lser = look_series(la.look, cold.x);
+  double gl[W2A_LOOK_MAX];  // LOOK: the lookahead inputs' columns
+#pragma unroll
+  for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = 0.0;
   const double w_e = ia.im.env_weight ? (double)ia.im.env_weight[e] : 1.0;
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
   uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
@@ -121,6 +132,10 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
 #pragma unroll
     for (int k = 0; k < RO64_SLOTS; ++k)
       if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
+    if constexpr (LOOK) {
+      look_inputs(la.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+      z = look_logit(la.look, lf, lw, z);
+    }
     lab = im_label(ia.im, e, t, lab_word, lab_idx);
     scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
     if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
@@ -131,6 +146,10 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
       for (int k = 0; k < RO64_SLOTS; ++k)
         if (la.slot_obs[k] >= 0) g[k] = c * (double)la.obs[obs0 + la.slot_obs[k]];
       g[31] = c;
+      if constexpr (LOOK) {
+#pragma unroll
+        for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = c * (double)lf[k];
+      }
       ll = im_log_pi(z, lab);
       scored = 1;
     }
@@ -165,6 +184,10 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
       asm volatile("" : "+v"(wp[k]));  // keep the coefficients f32 (see k_rollout64)
       zp = fma((double)xv[k], (double)wp[k], zp);
     }
+    if constexpr (LOOK) {  // xv[] is day t's row
+      look_inputs(la.look, lser, t, ndays, lf);
+      zp = look_logit(la.look, lf, lw, zp);
+    }
     if (active) {
       const bool done = (t + 1 >= ndays);
       used = used2; hist = hist2;
@@ -182,6 +205,10 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
           for (int k = 0; k < RO64_SLOTS; ++k)
             if (la.slot_obs[k] >= 0) g[k] = fma(c, (double)xv[k], g[k]);
           g[31] += c;
+          if constexpr (LOOK) {
+#pragma unroll
+            for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = fma(c, (double)lf[k], gl[k]);
+          }
           ll += im_log_pi(zp, lab);
           scored += 1;
         }
@@ -194,6 +221,11 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
   for (int k = 0; k < RO64_SLOTS; ++k)
     if (la.slot_obs[k] >= 0) out[(size_t)la.slot_obs[k] * n] = (float)g[k];
   out[(size_t)la.n_obs * n] = (float)g[31];
+  if constexpr (LOOK) {
+#pragma unroll
+    for (int k = 0; k < W2A_LOOK_MAX; ++k)
+      if (k < la.look.days) out[(size_t)(la.n_obs + 1 + k) * n] = (float)gl[k];
+  }
   ia.im.loglik[e] = (float)ll;
   ia.im.days[e] = scored;
 }

@@ -49,6 +49,7 @@
 #include "w2a_posterior_i8.hip.h"
 #include "w2a_reset.hip.h"
 #include "w2a_rollout.hip.h"
+#include "w2a_lookahead.hip.h"
 #include "w2a_rollout_linear.hip.h"
 #include "w2a_rollout_mlp.hip.h"
 #include "w2a_rollout_i8.hip.h"

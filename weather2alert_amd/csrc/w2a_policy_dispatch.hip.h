@@ -190,6 +190,21 @@ static int check_gate(const char *fn, const w2a_env *env, const uint32_t *gate, 
   return W2A_OK;
 }
 
+// the lookahead block of the w2a_lookahead_* entry points: checked after the gate. needs_weight: the linear kind's rows
+// (the MLP kind keeps its lookahead rows at the tail of every parameter block)
+static int check_lookahead(const char *fn, const w2a_env *env, const w2a_lookahead *look, bool needs_weight) {
+  if (!look || !look->series) return fail(W2A_ERR_ARG, "%s: NULL lookahead or series", fn);
+  if (look->days < 1 || look->days > W2A_LOOKAHEAD_MAX_DAYS)
+    return fail(W2A_ERR_ARG, "%s: lookahead days must lie in 1..W2A_LOOKAHEAD_MAX_DAYS", fn);
+  if (look->stride < env->tb.T) return fail(W2A_ERR_ARG, "%s: lookahead stride must be at least T", fn);
+  if (needs_weight && !look->weight) return fail(W2A_ERR_ARG, "%s: NULL lookahead weight", fn);
+  return W2A_OK;
+}
+
+static void fill_lookahead(const w2a_lookahead *look, LookArgs &lk) {
+  lk.series = look->series; lk.stride = look->stride; lk.days = look->days; lk.weight = look->weight;
+}
+
 // REFUSE_WHILE_CAPTURING with the name at run time: every body's last refusal
 static int refuse_while_capturing(const char *fn, void *stream) {
   if (stream_is_capturing((hipStream_t)stream))
@@ -456,15 +471,17 @@ static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy 
                           int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
                           uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
                           void *stream, const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
-                          int32_t gate_words = 0) {
+                          int32_t gate_words = 0, bool looking = false, const w2a_lookahead *look = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_obs(fn, obs));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, (alert_mask || attempt_mask) ? MASK_ROLLOUT : MASK_NONE, mask_words));
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
+  if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   LinearRolloutArgs la;
   memset(&la, 0, sizeof(la));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, la));
+  if (looking) fill_lookahead(look, la.look);
   la.r.pol.require_budget = policy->require_budget;
   la.r.pol.seed = policy->seed;
   la.r.order = env->order;
@@ -485,7 +502,17 @@ static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy 
     if (gated) hipLaunchKernelGGL((k_rollout_linear<M, S, R, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr); \
     else hipLaunchKernelGGL((k_rollout_linear<M, S, R, false>), dim3(g64), dim3(BLOCK), 0, s, la, tr);      \
   } while (0)
-  if (traj) {
+#define W2A_LAUNCH_LINEAR_LOOK(M, S)                                                                                \
+  do {                                                                                                              \
+    if (gated) hipLaunchKernelGGL((k_rollout_linear<M, S, false, true, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr); \
+    else hipLaunchKernelGGL((k_rollout_linear<M, S, false, false, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr);      \
+  } while (0)
+  if (looking) {  // no trajectory: the w2a_lookahead_* exports take none
+    if (masks && policy->sample) W2A_LAUNCH_LINEAR_LOOK(true, true);
+    else if (masks) W2A_LAUNCH_LINEAR_LOOK(true, false);
+    else if (policy->sample) W2A_LAUNCH_LINEAR_LOOK(false, true);
+    else W2A_LAUNCH_LINEAR_LOOK(false, false);
+  } else if (traj) {
     if (masks && policy->sample) W2A_LAUNCH_LINEAR(true, true, true);
     else if (masks) W2A_LAUNCH_LINEAR(true, false, true);
     else if (policy->sample) W2A_LAUNCH_LINEAR(false, true, true);
@@ -497,6 +524,7 @@ static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy 
     else W2A_LAUNCH_LINEAR(false, false, false);
   }
 #undef W2A_LAUNCH_LINEAR
+#undef W2A_LAUNCH_LINEAR_LOOK
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
@@ -528,20 +556,48 @@ int w2a_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int3
                         mask_words, last_return, ret_snapshot, stream, traj, true, allowed_days, allowed_words);
 }
 
+int w2a_lookahead_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                                 float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                 uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words, float *last_return,
+                                 float *ret_snapshot, void *stream, const w2a_lookahead *lookahead) {
+  return rollout_linear("w2a_lookahead_rollout_linear", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask,
+                        attempt_mask, mask_words, last_return, ret_snapshot, stream, nullptr, false, nullptr, 0, true, lookahead);
+}
+
+int w2a_lookahead_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                                       float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                       uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words,
+                                       float *last_return, float *ret_snapshot, void *stream,
+                                       const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                       int32_t allowed_words) {
+  return rollout_linear("w2a_lookahead_rollout_linear_gated", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask,
+                        attempt_mask, mask_words, last_return, ret_snapshot, stream, nullptr, true, allowed_days, allowed_words, true,
+                        lookahead);
+}
+
 static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                        int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                        int32_t mask_words, float *last_return, float *ret_snapshot, void *stream,
                        const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
-                       int32_t gate_words = 0) {
+                       int32_t gate_words = 0, bool looking = false, const w2a_lookahead *look = nullptr) {
   W2A_CHECK(check_mlp_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_obs(fn, obs));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, (alert_mask || attempt_mask) ? MASK_ROLLOUT : MASK_NONE, mask_words));
   W2A_CHECK(check_mlp_stride(fn, policy));
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
+  if (looking) {
+    W2A_CHECK(check_lookahead(fn, env, look, false));
+    if ((int64_t)policy->n_groups * W2A_MLP_LOOKAHEAD_STRIDE((int64_t)policy->width, policy->n_layers) >= (1ll << 31))
+      return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
+  }
   W2A_CHECK(refuse_while_capturing(fn, stream));
   MlpRolloutArgs ma;
   memset(&ma, 0, sizeof(ma));
   W2A_CHECK(fill_mlp(fn, env, policy, n_steps, obs, gate, gate_words, ma));
+  if (looking) {  // the blocks carry W1f[12][width] at their tail
+    fill_lookahead(look, ma.look);
+    ma.stride = (int32_t)W2A_MLP_LOOKAHEAD_STRIDE((int64_t)policy->width, policy->n_layers);
+  }
   ma.r.pol.require_budget = policy->require_budget;
   ma.r.pol.seed = policy->seed;
   ma.r.order = policy->order ? mlp_own_order(policy) : env->order;  // the rollout writes state: the handle's order serves too
@@ -557,8 +613,12 @@ static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *polic
     // group-major order keeps the kernel's group loop short and the rows are stored directly
     if (policy->n_groups == 1) ma.r.order = nullptr;
   }
-  dispatch_mlp_shape(policy->width, policy->n_layers,
-                     [&](auto W, auto L) { launch_rollout_mlp<W(), L()>(ma, masks, smp, traj, g64, s); });
+  if (looking)
+    dispatch_mlp_shape(policy->width, policy->n_layers,
+                       [&](auto W, auto L) { launch_rollout_mlp_lookahead<W(), L()>(ma, masks, smp, g64, s); });
+  else
+    dispatch_mlp_shape(policy->width, policy->n_layers,
+                       [&](auto W, auto L) { launch_rollout_mlp<W(), L()>(ma, masks, smp, traj, g64, s); });
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
@@ -589,6 +649,25 @@ int w2a_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_
                      mask_words, last_return, ret_snapshot, stream, traj, true, allowed_days, allowed_words);
 }
 
+int w2a_lookahead_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                              int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                              uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                              void *stream, const w2a_lookahead *lookahead) {
+  return rollout_mlp("w2a_lookahead_rollout_mlp", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask,
+                     attempt_mask, mask_words, last_return, ret_snapshot, stream, nullptr, false, nullptr, 0, true, lookahead);
+}
+
+int w2a_lookahead_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs,
+                                    float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                    uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words,
+                                    float *last_return, float *ret_snapshot, void *stream,
+                                    const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                    int32_t allowed_words) {
+  return rollout_mlp("w2a_lookahead_rollout_mlp_gated", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask,
+                     attempt_mask, mask_words, last_return, ret_snapshot, stream, nullptr, true, allowed_days, allowed_words, true,
+                     lookahead);
+}
+
 // ---- policy gradients ------------------------------------------------------------------------------------------------
 // As found: these two bodies read the canonical state words (the rollout that follows would make them current itself),
 // change nothing else, and -- unlike the ten others -- do not call end_call.
@@ -603,17 +682,20 @@ static int check_policy_gradient(const char *fn, int32_t baseline, const float *
 
 static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
                                   const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
-                                  bool gated, const uint32_t *gate, int32_t gate_words) {
+                                  bool gated, const uint32_t *gate, int32_t gate_words, bool looking = false,
+                                  const w2a_lookahead *look = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_MUST_BE_1));
   W2A_CHECK(check_policy_gradient(fn, baseline, obs, grad, workspace));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_NONE, 0));
   if (workspace_bytes < w2a_policy_gradient_workspace_bytes(env->n, n_steps))
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_gradient_workspace_bytes", fn);
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
+  if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   PolicyGradArgs ga;
   memset(&ga, 0, sizeof(ga));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, ga.l));
+  if (looking) fill_lookahead(look, ga.l.look);
   ga.l.r.pol.require_budget = policy->require_budget;
   ga.l.r.pol.seed = policy->seed;
   ga.l.r.order = env->order;
@@ -624,7 +706,9 @@ static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear
   hipStream_t s = (hipStream_t)stream;
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = grid64(env);
-  if (gated) hipLaunchKernelGGL(k_policy_gradient_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ga);
+  if (looking && gated) hipLaunchKernelGGL((k_policy_gradient_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
+  else if (looking) hipLaunchKernelGGL((k_policy_gradient_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
+  else if (gated) hipLaunchKernelGGL(k_policy_gradient_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ga);
   else hipLaunchKernelGGL(k_policy_gradient_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ga);
   HIP_TRY(hipGetLastError());
   return W2A_OK;
@@ -641,6 +725,15 @@ int w2a_policy_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *poli
                                      void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
   return policy_gradient_linear("w2a_policy_gradient_linear_gated", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream, true,
                                 allowed_days, allowed_words);
+}
+
+// allowed_days nullable: NULL runs the ungated LOOK form
+int w2a_lookahead_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline,
+                                         int32_t n_steps, const float *obs, float *grad, void *workspace,
+                                         size_t workspace_bytes, void *stream, const w2a_lookahead *lookahead,
+                                         const uint32_t *allowed_days, int32_t allowed_words) {
+  return policy_gradient_linear("w2a_lookahead_policy_gradient_linear", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream,
+                                allowed_days != nullptr, allowed_days, allowed_words, true, lookahead);
 }
 
 static int policy_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
@@ -688,16 +781,19 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
                                      const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
                                      const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
                                      float *grad, float *loglik, int32_t *days, void *stream, bool gated = false,
-                                     const uint32_t *gate = nullptr, int32_t gate_words = 0) {
+                                     const uint32_t *gate = nullptr, int32_t gate_words = 0, bool looking = false,
+                                     const w2a_lookahead *look = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_imitation(fn, alert_mask, obs, grad, loglik, days));
   W2A_CHECK(check_day_weight(fn, day_weight, day_weight_days, n_steps));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_SCHEDULE, mask_words));
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
+  if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   ImLinearArgs ia;
   memset(&ia, 0, sizeof(ia));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, ia.l));
+  if (looking) fill_lookahead(look, ia.l.look);
   ia.l.r.pol.require_budget = policy->require_budget;
   ia.l.r.order = env->order;
   fill_imitation(ia.im, alert_mask, mask_words, env_weight, day_weight, loglik, days);
@@ -705,7 +801,9 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
   hipStream_t s = (hipStream_t)stream;
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = grid64(env);
-  if (gated) hipLaunchKernelGGL(k_imitation_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ia);
+  if (looking && gated) hipLaunchKernelGGL((k_imitation_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  else if (looking) hipLaunchKernelGGL((k_imitation_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  else if (gated) hipLaunchKernelGGL(k_imitation_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ia);
   else hipLaunchKernelGGL(k_imitation_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ia);
   HIP_TRY(hipGetLastError());
   end_call(env, s);
@@ -736,6 +834,18 @@ int w2a_imitation_gradient_linear_gated(w2a_env *env, const w2a_linear_policy *p
   return imitation_gradient_linear("w2a_imitation_gradient_linear_gated", env, policy, alert_mask, mask_words,
                                    env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
                                    true, allowed_days, allowed_words);
+}
+
+// day_weight and allowed_days nullable (= 1, = no gate)
+int w2a_lookahead_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                            int32_t mask_words, const float *env_weight, const float *day_weight,
+                                            int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                            float *loglik, int32_t *days, void *stream,
+                                            const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                            int32_t allowed_words) {
+  return imitation_gradient_linear("w2a_lookahead_imitation_gradient_linear", env, policy, alert_mask, mask_words,
+                                   env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
+                                   allowed_days != nullptr, allowed_days, allowed_words, true, lookahead);
 }
 
 static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy,

@@ -23,12 +23,16 @@ struct PolicyGradArgs {
   int32_t baseline;      // W2A_PG_BASELINE_*
   float2 *day;           // [n_steps][n] (delta_s, A_s) of the lane at visiting position `slot`
   uint8_t *day_alert;    // [n_steps][n] the alert issued on that call-day
-  float *grad;           // [n_obs + 1][n] per-env gradient: observation column j of env e at j * n + e, bias last
+  float *grad;           // [n_obs + 1][n] per-env gradient: observation column j of env e at j * n + e, bias last;
+                         // LOOK: [n_obs + 1 + D][n], lookahead input k at row n_obs + k (k = 1..D, after the bias)
 };
 
 // GATE (w2a_policy_gradient_linear_gated): ga.l.gate restricts the attempts, as in k_rollout_linear<.., GATE>; a
 // disallowed day is a forced choice, m_s = 0. GATE = false compiles from the statements it had before the gate existed.
-template <bool GATE>
+// LOOK (w2a_lookahead_policy_gradient_linear; GATE when its nullable allowed_days is given): pass 1 continues the logit chain over the lookahead
+// inputs as k_rollout_linear<.., LOOK> does; pass 2 rebuilds them for o_s from the series and keeps D more fp64
+// accumulators. LOOK = false compiles from the statements it had before.
+template <bool GATE, bool LOOK = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const PolicyGradArgs ga) {
   const LinearRolloutArgs &la = ga.l;
   const RolloutArgs &a = la.r;
@@ -47,10 +51,13 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
   const size_t n = (size_t)a.n;
   double total = 0.0;   // sum of A_s over the env's days of this call
   int32_t n_valid = 0;  // days the env steps in this call
+  const float *lser = nullptr;
+  if constexpr (LOOK) lser = look_series(la.look, cold.x);
   // ---------------------------------------------------------------- pass 1: k_rollout_linear's days
   {
     const uint32_t wrow = W_COL(cold.y) * (uint32_t)a.tb.n_samples + W_SAMPLE(cold.y);
     float wb[32], we[32], wp[32];
+    float lw[W2A_LOOK_MAX], lf[W2A_LOOK_MAX];
     {
       const float4 *wq = a.tb.W + (size_t)wrow * (2 * ROWF / 4);
       int32_t g = la.group ? la.group[e] : 0;
@@ -66,6 +73,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
 #pragma unroll
       for (int k = 0; k < 32; ++k) wp[k] = ((la.obs_mask >> k) & 1u) ? wp[k] : 0.0f;
       wp[31] = la.bias[g];
+      if constexpr (LOOK) look_weights(la.look, g, lw);
     }
     const uint64_t pstream = rng_stream(a.pol.seed ^ 0xA5A5A5A55A5A5A5Aull, (uint64_t)(a.gid0 + e), cold.w);
     uint32_t t = t0, used = used0, streak = streak0, hist = hist0;
@@ -79,6 +87,10 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
 #pragma unroll
       for (int k = 0; k < RO64_SLOTS; ++k)
         if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
+      if constexpr (LOOK) {
+        look_inputs(la.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+        z = look_logit(la.look, lf, lw, z);
+      }
     }
     for (int s = 0; s < a.n_steps; ++s) {
       if (!__any(active)) break;
@@ -120,6 +132,10 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
         ze = fma(xk, (double)we[k], ze);
         zp = fma(xk, (double)wp[k], zp);
       }
+      if constexpr (LOOK) {
+        look_inputs(la.look, lser, t, ndays, lf);
+        zp = look_logit(la.look, lf, lw, zp);
+      }
       if (!(xv[30] > 0.5f)) ze = -__builtin_inf();
       const float r = reward_from_logits(zb, ze, actual);
       // no alert issued: the effectiveness term is multiplied by 0, whatever its logit
@@ -144,6 +160,9 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
 #pragma unroll
   for (int k = 0; k < 32; ++k) g[k] = 0.0;  // slot k's column; the bias rides in slot 31, as in the policy row
   double prefix = 0.0;
+  double gl[W2A_LOOK_MAX];  // LOOK: the lookahead inputs' columns
+#pragma unroll
+  for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = 0.0;
   if (n_valid > 0) {  // s = 0: the row the env holds on entry
     const float2 da = ga.day[slot];
     const double c = (double)da.x * total;
@@ -151,6 +170,12 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
     for (int k = 0; k < RO64_SLOTS; ++k)
       if (la.slot_obs[k] >= 0) g[k] = c * (double)la.obs[obs0 + la.slot_obs[k]];
     g[31] = c;
+    if constexpr (LOOK) {
+      float lf[W2A_LOOK_MAX];
+      look_inputs(la.look, lser, t0 > 0 ? t0 - 1 : 0u, ndays, lf);
+#pragma unroll
+      for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = c * (double)lf[k];
+    }
     prefix = (double)da.y;
   }
   {
@@ -183,6 +208,12 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
       g[4 * RT_QUAD + 2] = fma(c, (double)(budget - (int32_t)used), g[4 * RT_QUAD + 2]);
       g[4 * RT_QUAD + 3] = fma(c, (double)__popc(hist), g[4 * RT_QUAD + 3]);
       g[31] += c;
+      if constexpr (LOOK) {  // o_s is day t's row
+        float lf[W2A_LOOK_MAX];
+        look_inputs(la.look, lser, t, ndays, lf);
+#pragma unroll
+        for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = fma(c, (double)lf[k], gl[k]);
+      }
       streak = actual ? streak + 1 : 0;  // call-day s - 1 was not terminal: the env stepped again on call-day s
       t = t + 1;
     }
@@ -194,6 +225,11 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
   for (int k = 0; k < RO64_SLOTS; ++k)
     if (la.slot_obs[k] >= 0) out[(size_t)la.slot_obs[k] * n] = (float)g[k];
   out[(size_t)la.n_obs * n] = (float)g[31];
+  if constexpr (LOOK) {
+#pragma unroll
+    for (int k = 0; k < W2A_LOOK_MAX; ++k)
+      if (k < la.look.days) out[(size_t)(la.n_obs + 1 + k) * n] = (float)gl[k];
+  }
 }
 
 #endif  // W2A_POLICY_GRADIENT_HIP_H

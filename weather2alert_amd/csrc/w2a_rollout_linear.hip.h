@@ -30,6 +30,8 @@ struct LinearRolloutArgs {
   const uint32_t *gate;    // [n][gate_words] allowed days (policy["allowed_days"]): bit (t & 31) of word t >> 5, the layout
                            // of alert_mask. Read by the GATE = true instantiations only (the *_gated entry points)
   int32_t gate_words;
+  LookArgs look;           // policy["lookahead"] (w2a_lookahead.hip.h): read by the LOOK = true instantiations only (the
+                           // w2a_lookahead_* entry points); zero otherwise
 };
 
 // the gate's bit of day t: on a day whose bit is clear the attempted action is forced to 0 before the budget test, and
@@ -131,7 +133,10 @@ __device__ __forceinline__ void traj_store_tile(const Args &pa, const w2a_trajec
 // RECORD = false compiles to the kernel without a trajectory (same registers, scratch and LDS).
 // GATE (w2a_rollout_linear_gated / _record_gated): la.gate restricts the attempts; GATE = false compiles from the
 // statements it had before the gate existed.
-template <bool MASKS, bool SAMPLE, bool RECORD, bool GATE>
+// LOOK (w2a_lookahead_rollout_linear and its _gated form): the logit chain goes on over la.look.days lookahead inputs of
+// the held row's day (w2a_lookahead.hip.h): on entry from the state and the series, then every day next to zp. LOOK =
+// false compiles from the statements it had before; there is no RECORD form.
+template <bool MASKS, bool SAMPLE, bool RECORD, bool GATE, bool LOOK = false>
 __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRolloutArgs la, const w2a_trajectory tr) {
   const RolloutArgs &a = la.r;
   const int64_t slot64 = (int64_t)logical_block(blockIdx.x, gridDim.x >> 3) * BLOCK + threadIdx.x;
@@ -168,6 +173,14 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
     for (int k = 0; k < 32; ++k) wp[k] = ((la.obs_mask >> k) & 1u) ? wp[k] : 0.0f;
     wp[31] = la.bias[g];  // slot 31 holds no observation column and no reward input: the bias rides there
   }
+  float lw[W2A_LOOK_MAX], lf[W2A_LOOK_MAX];
+  const float *lser = nullptr;
+  if constexpr (LOOK) {
+    int32_t g = la.group ? la.group[e] : 0;
+    g = g < 0 ? 0 : (g >= la.n_groups ? la.n_groups - 1 : g);
+    look_weights(la.look, g, lw);
+    lser = look_series(la.look, cold.x);
+  }
   const uint64_t pstream = SAMPLE ? rng_stream(a.pol.seed ^ 0xA5A5A5A55A5A5A5Aull, (uint64_t)(a.gid0 + e), cold.w) : 0ull;
   const uint32_t obs0 = e * (uint32_t)la.n_obs;  // first element of the env's observation row (host: n * n_obs < 2^31)
   if (RECORD && valid) traj_copy_row(la, tr, 0, e, obs0);  // slab 0: the row every env holds on entry
@@ -190,6 +203,10 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
 #pragma unroll
     for (int k = 0; k < RO64_SLOTS; ++k)
       if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
+    if constexpr (LOOK) {  // the held row is day max(t - 1, 0)'s: its lookahead inputs are rebuilt, never carried
+      look_inputs(la.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+      z = look_logit(la.look, lf, lw, z);
+    }
   }
   for (int s = 0; s < a.n_steps; ++s) {
     if (!__any(active)) break;
@@ -233,6 +250,10 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
       zb = fma(xk, (double)wb[k], zb);
       ze = fma(xk, (double)we[k], ze);
       zp = fma(xk, (double)wp[k], zp);
+    }
+    if constexpr (LOOK) {  // xv[] is day t's row: tomorrow's decision looks ahead from day t
+      look_inputs(la.look, lser, t, ndays, lf);
+      zp = look_logit(la.look, lf, lw, zp);
     }
     if (!(xv[30] > 0.5f)) ze = -__builtin_inf();
     const float r = reward_from_logits(zb, ze, actual);

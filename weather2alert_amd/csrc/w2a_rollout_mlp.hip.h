@@ -40,6 +40,9 @@ struct MlpRolloutArgs {
   const uint32_t *gate;    // [n][gate_words] allowed days, as LinearRolloutArgs::gate: read by the GATE = true
                            // instantiations only (the *_gated entry points); NULL selects GATE = false on the host
   int32_t gate_words;
+  LookArgs look;           // policy["lookahead"] (w2a_lookahead.hip.h; look.weight unused: the rows W1f[12][width] sit at
+                           // the tail of every block, w2a.h: W2A_MLP_LOOKAHEAD_STRIDE): read by the LOOK = true
+                           // instantiations only (the w2a_lookahead_* entry points); zero otherwise
 };
 
 #define MLP_XS 36  // LDS row of one env's input vector, in floats: 16-B aligned rows, conflict-free B-operand reads
@@ -60,8 +63,11 @@ __device__ __forceinline__ float mlp_act(float x, int activation) {
 }
 
 // the logit of every lane's env under group block p; xs holds the wave's 64 input rows
-template <int WIDTH, int LAYERS>
-__device__ __forceinline__ float mlp_logit(const float *__restrict__ p, const float *xs, int activation) {
+// LOOK: after the 8 k-steps over the slots the first layer runs ceil(look_days / 4) more over the wave's lookahead
+// rows xl ([64 envs][W2A_LOOK_PAD floats], zero past look_days) against W1f[W2A_LOOK_PAD][WIDTH] at the block's tail
+template <int WIDTH, int LAYERS, bool LOOK = false>
+__device__ __forceinline__ float mlp_logit(const float *__restrict__ p, const float *xs, int activation,
+                                           const float *xl = nullptr, int look_days = 0) {
   constexpr int NT = WIDTH / 16;  // hidden tiles
   constexpr int NB = 4 / NT;      // blocks of 16 envs per pass: NT * NB = 4 accumulator tiles
   const int l = threadIdx.x & 63, lo = l & 15, hi = l >> 4;
@@ -89,6 +95,23 @@ __device__ __forceinline__ float mlp_logit(const float *__restrict__ p, const fl
         const float a = W1[(4 * ks + hi) * WIDTH + 16 * t + lo];
 #pragma unroll
         for (int j = 0; j < NB; ++j) h[j][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[j], h[j][t], 0, 0, 0);
+      }
+    }
+    if constexpr (LOOK) {
+      const float *W1f = p + W2A_MLP_STRIDE(WIDTH, LAYERS);
+#pragma unroll
+      for (int ks = 0; ks < W2A_LOOK_PAD / 4; ++ks) {
+        if (4 * ks < look_days) {  // wave-uniform
+          float xb[NB];
+#pragma unroll
+          for (int j = 0; j < NB; ++j) xb[j] = xl[(16 * (b0 + j) + lo) * W2A_LOOK_PAD + 4 * ks + hi];
+#pragma unroll
+          for (int t = 0; t < NT; ++t) {
+            const float a = W1f[(4 * ks + hi) * WIDTH + 16 * t + lo];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) h[j][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[j], h[j][t], 0, 0, 0);
+          }
+        }
       }
     }
 #pragma unroll
@@ -140,13 +163,15 @@ __device__ __forceinline__ float mlp_logit(const float *__restrict__ p, const fl
 }
 
 // every lane's logit for the input rows in xs, over the distinct groups of the wave (wave-uniform loop)
-template <int WIDTH, int LAYERS>
-__device__ __forceinline__ float mlp_logit_groups(const MlpRolloutArgs &ma, int32_t g, const float *xs) {
+template <int WIDTH, int LAYERS, bool LOOK = false>
+__device__ __forceinline__ float mlp_logit_groups(const MlpRolloutArgs &ma, int32_t g, const float *xs,
+                                                  const float *xl = nullptr) {
   float z = 0.0f;
   uint64_t todo = __ballot(1);
   while (todo) {
     const int32_t gw = __builtin_amdgcn_readfirstlane(__shfl(g, __ffsll((unsigned long long)todo) - 1));
-    const float zg = mlp_logit<WIDTH, LAYERS>(ma.params + (size_t)gw * ma.stride, xs, ma.activation);
+    const float zg = mlp_logit<WIDTH, LAYERS, LOOK>(ma.params + (size_t)gw * ma.stride, xs, ma.activation, xl,
+                                                    LOOK ? ma.look.days : 0);
     if (g == gw) z = zg;
     todo &= ~__ballot(g == gw);
   }
@@ -158,7 +183,10 @@ __device__ __forceinline__ float mlp_logit_groups(const MlpRolloutArgs &ma, int3
 // kernel without one
 // GATE (w2a_rollout_mlp_gated): ma.gate restricts the attempts, as in k_rollout_linear; GATE = false compiles from the
 // statements it had before the gate existed
-template <int WIDTH, int LAYERS, bool MASKS, bool RECORD, bool GATE>
+// LOOK (w2a_lookahead_rollout_mlp and its _gated form): every lane also puts the lookahead inputs of the row it holds
+// (w2a_lookahead.hip.h) into a second LDS region next to xs, and the first layer runs on over them. LOOK = false
+// compiles from the statements it had before; there is no RECORD form.
+template <int WIDTH, int LAYERS, bool MASKS, bool RECORD, bool GATE, bool LOOK = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs ma, const int32_t sample,
                                                           const w2a_trajectory tr) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
@@ -211,12 +239,26 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
   bool snapped = false;
   uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   bool active = !fin && valid;
+  float *xl = nullptr, *xlrow = nullptr;  // the wave's lookahead rows and this lane's
+  const float *lser = nullptr;
+  if constexpr (LOOK) {
+    __shared__ __attribute__((aligned(16))) float s_xl[MLP_WAVES][64 * W2A_LOOK_PAD];
+    xl = s_xl[threadIdx.x >> 6];
+    xlrow = xl + (threadIdx.x & 63) * W2A_LOOK_PAD;
+    lser = look_series(ma.look, cold.x);
+  }
   // first day: the logit of the observation row the agent holds (zeros for lanes with no live env)
 #pragma unroll
   for (int k = 0; k < ROWF; ++k)
     xrow[k] = (k < RO64_SLOTS && ma.slot_obs[k] >= 0 && active) ? ma.obs[obs0 + ma.slot_obs[k]] : 0.0f;
+  if constexpr (LOOK) {  // the held row is day max(t - 1, 0)'s: its lookahead inputs are rebuilt, never carried
+    float lf[W2A_LOOK_MAX];
+    look_inputs(ma.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+#pragma unroll
+    for (int k = 0; k < W2A_LOOK_PAD; ++k) xlrow[k] = (k < W2A_LOOK_MAX && active) ? lf[k < W2A_LOOK_MAX ? k : 0] : 0.0f;
+  }
   mlp_wave_lds_sync();
-  float z = mlp_logit_groups<WIDTH, LAYERS>(ma, g, xs);
+  float z = mlp_logit_groups<WIDTH, LAYERS, LOOK>(ma, g, xs, xl);
   for (int s = 0; s < a.n_steps; ++s) {
     if (!__any(active)) break;
     // ---- policy: alert iff logit > 0, or u < sigmoid(logit) with the Bernoulli policy's uniform of (env, episode, day)
@@ -271,6 +313,12 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
       v.w = (active && ((ma.obs_mask >> (4 * q + 3)) & 1u)) ? xv[4 * q + 3] : 0.0f;
       reinterpret_cast<float4 *>(xrow)[q] = v;
     }
+    if constexpr (LOOK) {  // xv[] is day t's row: tomorrow's decision looks ahead from day t
+      float lf[W2A_LOOK_MAX];
+      look_inputs(ma.look, lser, t, ndays, lf);
+#pragma unroll
+      for (int k = 0; k < W2A_LOOK_PAD; ++k) xlrow[k] = (k < W2A_LOOK_MAX && active) ? lf[k < W2A_LOOK_MAX ? k : 0] : 0.0f;
+    }
     if (active) {
       const bool done = (t + 1 >= ndays);
       ret += r;
@@ -315,7 +363,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
     if (RECORD && stage) traj_store_tile(ma, tr, s, (uint32_t)(slot64 - (threadIdx.x & 63)), stage);
     if (s + 1 < a.n_steps) {  // wave-uniform: the logit of the row each env now holds, for tomorrow
       mlp_wave_lds_sync();
-      z = mlp_logit_groups<WIDTH, LAYERS>(ma, g, xs);
+      z = mlp_logit_groups<WIDTH, LAYERS, LOOK>(ma, g, xs, xl);
     }
   }
   if (RECORD && valid) traj_copy_row(ma, tr, a.n_steps, e, obs0);  // slab n_steps: the buffer as the call leaves it
@@ -351,6 +399,17 @@ static void launch_rollout_mlp(const MlpRolloutArgs &ma, bool masks, int32_t sam
   else if (masks) W2A_LAUNCH_MLP(true, false);
   else W2A_LAUNCH_MLP(false, false);
 #undef W2A_LAUNCH_MLP
+}
+
+// the 24 LOOK instantiations (w2a_lookahead_rollout_mlp and its gated form): no trajectory
+template <int WIDTH, int LAYERS>
+static void launch_rollout_mlp_lookahead(const MlpRolloutArgs &ma, bool masks, int32_t sample, unsigned grid, hipStream_t s) {
+  w2a_trajectory tr;
+  memset(&tr, 0, sizeof(tr));
+  if (ma.gate && masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else if (ma.gate) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else if (masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false, false, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false, false, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
 }
 
 #endif  // W2A_ROLLOUT_MLP_HIP_H

@@ -39,6 +39,22 @@ except ImportError:
     _AutoresetMode = None
 
 
+def _check_learned(env, policy: dict):
+    """check_linear_policy / check_mlp_policy with what the "lookahead" key's feature check needs from the env (module
+    level, as _refuse_lookahead: the entry points read nothing of the env but its tables and settings before they refuse)."""
+    ct = env.ct
+    check = _policy.check_linear_policy if policy.get("kind") == "linear" else _policy.check_mlp_policy
+    return check(policy, ct.n_obs, env.num_envs, ct.obs_slot, env.device, ct.feature_names, env.fixes,
+                 ct.slot_of.get("alerts_2wks", -1))
+
+
+def _refuse_lookahead(policy, who: str):
+    """The learners whose kernels do not read the lookahead inputs yet."""
+    if isinstance(policy, dict) and policy.get("lookahead") is not None:
+        raise ValueError(f"{who} does not take a 'lookahead' policy yet: its kernels do not read the lookahead "
+                         "inputs (rollout(), rollout(linear, policy_gradient=...) and imitation_gradient(linear) do)")
+
+
 def _autoreset_metadata(mode: str):
     """metadata["autoreset_mode"]: gymnasium's AutoresetMode member when the package has one, else the plain string."""
     if _AutoresetMode is None:
@@ -251,6 +267,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         self._done_bool = self._done.view(torch.bool)
         self._sort_ws = None
         self._order_ws = None
+        self._look_tables = {}  # feature -> f32 [S_w * Y, T] series table (lookahead_table(); built on first use)
         self._group_ws = None
         if reward_mode == "posterior_mean":
             with torch.cuda.device(dev):
@@ -380,6 +397,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
             torch.cuda.synchronize(self.device)
             self._lib.w2a_destroy(self._h)
             self._h = None
+        self._look_tables = {}  # the series tables of lookahead_table()
         self.closed = True
 
     def __del__(self):  # pragma: no cover
@@ -907,8 +925,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
             if self.fixes - {"budget"}:
                 raise ValueError(f"rollout(kind={kind!r}) needs faithful observations; fixes {sorted(self.fixes - {'budget'})} "
                                  "change what the observation is")
-            check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
-            lin = check(policy, ct.n_obs, self.num_envs, ct.obs_slot, self.device)
+            if policy.get("lookahead") is not None:
+                if record:
+                    raise ValueError("rollout(record=True) does not take a 'lookahead' policy: the recorded rows would "
+                                     "lack the lookahead inputs (a later addition)")
+                if pg is not None and kind == "mlp":
+                    raise ValueError("rollout(policy_gradient=...) takes 'lookahead' with kind 'linear' only; the mlp "
+                                     "kind's gradient kernels do not read the lookahead inputs yet")
+            lin = _check_learned(self, policy)
         elif kind not in _ffi.POLICY_KINDS:
             raise ValueError(f"policy kind {kind!r}")
         if self._pending_reset:  # next_step autoreset in lock step: the finished batch restarts before anything runs
@@ -941,6 +965,53 @@ class HeatAlertVecEnv(_VectorEnvBase):
             p.table, p.table_R = keep.data_ptr(), int(keep.shape[1])
         return self._rollout_run(p, None, n_steps, alert_mask, keep, posterior_returns=pr, hindsight=hs)
 
+    def lookahead_table(self, feature: str = "heat_qi") -> torch.Tensor:
+        """f32 [S_w * Y, T] on the device: the value of the table-sourced observation column `feature` on every day of
+        every (county, year) episode -- that column of the feature table X, transposed so that one episode's days are
+        contiguous (a lookahead decision reads D + 1 consecutive floats of one series). Built once per feature and
+        kept on the env until close(); it does not depend on the env's state. ValueError, as every other lookahead
+        check, for a name that is no observation column and for a column that is not table-sourced (the rule of
+        alert_gate())."""
+        ct = self.ct
+        cache = self._look_tables
+        if feature in cache:
+            return cache[feature]
+        if feature not in ct.feature_names:
+            raise ValueError(f"lookahead_table(feature={feature!r}): no observation column of that name")
+        slot = int(_policy.slot_map(ct.obs_slot, ct.n_obs)[ct.feature_names.index(feature)])
+        if 24 <= slot <= 27 or ("alert_2wks" in self.fixes and slot == ct.slot_of.get("alerts_2wks", -1)):
+            raise ValueError(f"lookahead_table(feature={feature!r}): lookahead reads table-sourced columns only")
+        cache[feature] = self.dtables.X[:, :, slot].t().contiguous()  # [T, R] -> [R, T]
+        return cache[feature]
+
+    def lookahead_features(self, spec: dict) -> torch.Tensor:
+        """f32 [N, D]: the lookahead inputs of the rows the envs hold right now, for ``spec = {"feature": name,
+        "days": D}`` (a policy's "lookahead" value): f_k = h(r + k) - h(r), k = 1..D, with h the series of
+        lookahead_table(feature) for the env's (county, year), r = max(t - 1, 0) the day of the row step() returned last
+        (Q6), and 0 where r + k >= n_days of the env. What the kernels of a lookahead policy form themselves: a torch
+        policy driven through step() acts on ``cat(obs, env.lookahead_features(spec))``."""
+        if self._needs_reset:
+            raise RuntimeError("call reset() before lookahead_features()")
+        feature, D = _policy.check_lookahead({"lookahead": spec}, "lookahead_features()", self.ct.feature_names,
+                                             self.ct.obs_slot, self.ct.n_obs, self.fixes,
+                                             self.ct.slot_of.get("alerts_2wks", -1))
+        tab = self.lookahead_table(feature)
+        st = self._state_packed(("t", "n_days", "county_w", "year_i"))[1]
+        row = (st["county_w"].long() * self.ct.Y + st["year_i"].long())[:, None]
+        r = (st["t"].long() - 1).clamp_(min=0)[:, None]
+        d = r + torch.arange(1, D + 1, device=self.device)[None, :]
+        ok = d < st["n_days"].long()[:, None]
+        h = tab[row, torch.where(ok, d, r)]
+        return torch.where(ok, h - tab[row, r], torch.zeros((), dtype=torch.float32, device=self.device))
+
+    def _lookahead_struct(self, pol):
+        """The w2a_lookahead block of a checked lookahead policy (linear: with its weight rows), and what it points to."""
+        tab = self.lookahead_table(pol.look_feature)
+        lk = _ffi.Lookahead()
+        lk.series, lk.stride, lk.days = tab.data_ptr(), int(tab.shape[1]), pol.look_days
+        lk.weight = pol.look_weight.data_ptr() if getattr(pol, "look_weight", None) is not None else None
+        return lk
+
     def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
                         policy_gradient=None, gate=None) -> dict:
         """rollout(kind="linear"): w2a_rollout_linear on the checked policy (weather2alert_amd/policy.py)."""
@@ -958,7 +1029,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if policy_gradient is not None:
             # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
             g = _policy.group_mean_columns(out.pop("_policy_gradient_env"), lin.group, lin.n_groups)
-            out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
+            no = self.ct.n_obs  # rows: the observation columns, the bias, then the lookahead inputs
+            out["policy_gradient"] = {"weight": torch.cat([g[:, :no], g[:, no + 1:]], dim=1).contiguous(),
+                                      "bias": g[:, no].contiguous()}
         return out
 
     def _rollout_mlp(self, mlp, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
@@ -998,6 +1071,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         ct = self.ct
         n, dev = self.num_envs, self.device
         steps = int(n_steps) if n_steps is not None else ct.T
+        # a lookahead policy (rollout() has refused record=True): the w2a_lookahead_* entry points
+        look = self._lookahead_struct(keep) if getattr(keep, "look_days", 0) else None
         out = {"return": torch.empty(n, dtype=torch.float32, device=dev),
                "alerts": torch.empty(n, dtype=torch.int32, device=dev),
                "attempts_over_budget": torch.empty(n, dtype=torch.int32, device=dev)}
@@ -1049,16 +1124,31 @@ class HeatAlertVecEnv(_VectorEnvBase):
                     _ffi.check(self._lib.w2a_policy_gradient_mlp_gated(*pgm_args, gate.data_ptr(), int(gate.shape[1])),
                                "w2a_policy_gradient_mlp_gated")
             elif policy_gradient is not None:
-                out["_policy_gradient_env"] = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
+                out["_policy_gradient_env"] = torch.empty((ct.n_obs + 1 + keep.look_days, n), dtype=torch.float32,
+                                                          device=dev)
                 ws = torch.empty(self._lib.w2a_policy_gradient_workspace_bytes(n, steps), dtype=torch.uint8, device=dev)
                 pg_args = (self._h, C.byref(lp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
                            out["_policy_gradient_env"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
-                if gate is None:
+                if look is not None:
+                    _ffi.check(self._lib.w2a_lookahead_policy_gradient_linear(
+                        *pg_args, C.byref(look), None if gate is None else gate.data_ptr(),
+                        0 if gate is None else int(gate.shape[1])), "w2a_lookahead_policy_gradient_linear")
+                elif gate is None:
                     _ffi.check(self._lib.w2a_policy_gradient_linear(*pg_args), "w2a_policy_gradient_linear")
                 else:
                     _ffi.check(self._lib.w2a_policy_gradient_linear_gated(*pg_args, gate.data_ptr(), int(gate.shape[1])),
                                "w2a_policy_gradient_linear_gated")
-            if lp is not None and gate is not None:
+            if look is not None:
+                fn = "w2a_lookahead_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_lookahead_rollout_linear"
+                args = (self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
+                        out["alerts"].data_ptr(), out["attempts_over_budget"].data_ptr(),
+                        None if mask is None else mask.data_ptr(), None if amask is None else amask.data_ptr(), words,
+                        self._fr_ptr, None if snap is None else snap.data_ptr(), self._stream(), C.byref(look))
+                if gate is not None:
+                    fn += "_gated"
+                    args += (gate.data_ptr(), int(gate.shape[1]))
+                _ffi.check(getattr(self._lib, fn)(*args), fn)
+            elif lp is not None and gate is not None:
                 fn = "w2a_rollout_mlp_gated" if isinstance(lp, _ffi.MlpPolicy) else "w2a_rollout_linear_gated"
                 _ffi.check(getattr(self._lib, fn)(
                     self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
@@ -1202,8 +1292,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
         kind = policy.get("kind") if isinstance(policy, dict) else None
         ct, n, dev = self.ct, self.num_envs, self.device
         mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes)
-        check = _policy.check_linear_policy if kind == "linear" else _policy.check_mlp_policy
-        pol = check(policy, ct.n_obs, n, ct.obs_slot, dev)  # every argument is checked before anything runs
+        if kind == "mlp" and policy.get("lookahead") is not None:
+            raise ValueError("imitation_gradient() takes 'lookahead' with kind 'linear' only; the mlp kind's gradient "
+                             "kernels do not read the lookahead inputs yet")
+        pol = _check_learned(self, policy)  # every argument is checked before anything runs
         dw = _policy.check_day_weight(day_weight, min(steps, 2**31 - 1), n, dev)
         gate = _policy.check_allowed_days(policy, n, ct.T, dev, "imitation_gradient()")
         if self._needs_reset:
@@ -1222,8 +1314,16 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 lp.weight, lp.bias = pol.weight_slots.data_ptr(), pol.bias.data_ptr()
                 lp.group = None if pol.group is None else pol.group.data_ptr()
                 lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
-                rows = torch.empty((ct.n_obs + 1, n), dtype=torch.float32, device=dev)
-                if gate is not None:
+                rows = torch.empty((ct.n_obs + 1 + pol.look_days, n), dtype=torch.float32, device=dev)
+                if pol.look_days:
+                    look = self._lookahead_struct(pol)
+                    _ffi.check(self._lib.w2a_lookahead_imitation_gradient_linear(
+                        self._h, C.byref(lp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
+                        0 if dw is None else int(dw.shape[0]), steps, self._obs.data_ptr(), rows.data_ptr(),
+                        out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream(), C.byref(look),
+                        None if gate is None else gate.data_ptr(), 0 if gate is None else int(gate.shape[1])),
+                        "w2a_lookahead_imitation_gradient_linear")
+                elif gate is not None:
                     _ffi.check(self._lib.w2a_imitation_gradient_linear_gated(
                         self._h, C.byref(lp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
                         0 if dw is None else int(dw.shape[0]), steps, self._obs.data_ptr(), rows.data_ptr(),
@@ -1241,7 +1341,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
                         self._stream()), "w2a_imitation_gradient_linear_weighted")
                 # per-env gradients -> per-group mean, in a fixed order (a sort and an fp64 scan along each column)
                 g = _policy.group_mean_columns(rows, pol.group, pol.n_groups)
-                out["policy_gradient"] = {"weight": g[:, :-1].contiguous(), "bias": g[:, -1].contiguous()}
+                # rows: the observation columns, the bias, then the lookahead inputs
+                out["policy_gradient"] = {"weight": torch.cat([g[:, :ct.n_obs], g[:, ct.n_obs + 1:]], dim=1).contiguous(),
+                                          "bias": g[:, ct.n_obs].contiguous()}
             else:
                 mp = _ffi.MlpPolicy()
                 mp.params = pol.params.data_ptr()
@@ -1322,6 +1424,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         calls give identical bits. Needs the observation buffer current (RuntimeError as imitation_gradient()) and
         faithful observations. Value-loss clipping and minibatches inside a call are not offered.
         w2a_surrogate_gradient_linear / _mlp (include/w2a.h)."""
+        _refuse_lookahead(policy, "surrogate_gradient()")
         kind = policy.get("kind") if isinstance(policy, dict) else None
         ct, n, dev = self.ct, self.num_envs, self.device
         mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,
@@ -1431,6 +1534,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         and the RNG are only read. No floating-point atomics: two identical calls give identical bits. Needs the
         observation buffer current (RuntimeError as surrogate_gradient()) and faithful observations.
         w2a_fisher_vector_product_linear / _mlp (include/w2a.h)."""
+        _refuse_lookahead(policy, "fisher_vector_product()")
         kind = policy.get("kind") if isinstance(policy, dict) else None
         ct, n, dev = self.ct, self.num_envs, self.device
         mask, w, steps = _policy.check_imitation_args(kind, alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,
@@ -1543,6 +1647,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         "sq_error" is sum_s c_s^2, "advantage" holds A_s, "return" stays the UNDISCOUNTED sum_s r_s, "days" and
         "group_loss" as above. Advantage normalisation and a clipped value loss stay with the caller (clipped ratios:
         surrogate_gradient()). w2a_value_gradient_linear_gae / _mlp_gae (include/w2a.h)."""
+        _refuse_lookahead(value, "value_gradient()")
         kind = value.get("kind") if isinstance(value, dict) else None
         ct, n, dev = self.ct, self.num_envs, self.device
         # with targets given no reward enters: the reward mode does not matter then (as for imitation_gradient())
@@ -1672,6 +1777,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         value_gradient() refuses: rewards enter here). w2a_q_gradient_mlp (include/w2a.h)."""
         who = "q_gradient()"
         ct, n, dev = self.ct, self.num_envs, self.device
+        _refuse_lookahead(q, who)
+        _refuse_lookahead(target_net, who)
         if not isinstance(q, dict) or q.get("kind") != "mlp":
             raise ValueError(f"{who} needs kind 'mlp', got {q.get('kind') if isinstance(q, dict) else q!r}")
         mask, w, steps = _policy.check_imitation_args("mlp", alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,

@@ -25,8 +25,10 @@ import torch
 
 ROW_FLOATS = 32
 LOGIT_SLOTS = 30  # slots the day loop multiplies (0..29); an observation column elsewhere cannot be served
-KEYS = {"kind", "weight", "bias", "group", "sample", "seed", "require_budget", "allowed_days"}
+KEYS = {"kind", "weight", "bias", "group", "sample", "seed", "require_budget", "allowed_days", "lookahead"}
 GATE_KINDS = ("linear", "mlp")  # the kinds whose kernels take "allowed_days"
+LOOKAHEAD_MAX_DAYS = 10  # w2a.h: W2A_LOOKAHEAD_MAX_DAYS (the older reference env's "D10")
+LOOKAHEAD_PAD = 12       # w2a.h: W2A_LOOKAHEAD_PAD, floats per lookahead weight row
 
 
 @dataclass
@@ -40,6 +42,40 @@ class LinearPolicyArgs:
     sample: bool
     seed: int
     require_budget: bool
+    look_feature: str | None = None          # "lookahead": the feature's name, None without the key
+    look_days: int = 0                       # D
+    look_weight: torch.Tensor | None = None  # f32 [G, LOOKAHEAD_PAD], k = 1 first, zero past D
+
+
+def check_lookahead(policy: dict, who: str, feature_names=None, obs_slot=None, n_obs: int | None = None, fixes=(),
+                    slot_alerts_2wks: int = -1):
+    """The ``"lookahead"`` key of a linear or mlp policy dict: None when it is absent or None, else (feature, D) from
+    ``{"feature": name, "days": D}``. The decision then gets D more inputs f_k = h(r + k) - h(r), k = 1..D, after the
+    observation columns: h the f32 table value of `feature` along the env's episode, r the day of the row the agent
+    holds, 0 past the env's last day. ValueError for another structure, a D that is not an int in 1..10, a feature that
+    is no observation column and -- the rule of alert_gate() -- one that is not table-sourced (run-time slots 24..27, and
+    alerts_2wks under the "alert_2wks" fix). The name is checked when `feature_names` is given."""
+    if not isinstance(policy, dict) or policy.get("lookahead") is None:
+        return None
+    la = policy["lookahead"]
+    if not isinstance(la, dict) or set(la) != {"feature", "days"}:
+        raise ValueError(f"{who}: 'lookahead' must be {{'feature': name, 'days': D}}, got {la!r}")
+    feature, D = la["feature"], la["days"]
+    if not isinstance(feature, str):
+        raise ValueError(f"{who}: lookahead feature must be a column name, got {feature!r}")
+    if isinstance(D, (bool, np.bool_)) or not isinstance(D, (int, np.integer)):
+        raise ValueError(f"{who}: lookahead days must be an int in 1..{LOOKAHEAD_MAX_DAYS}, got {D!r}")
+    if not 1 <= int(D) <= LOOKAHEAD_MAX_DAYS:
+        raise ValueError(f"{who}: lookahead days must lie in 1..{LOOKAHEAD_MAX_DAYS}, got {D}")
+    if feature_names is not None:
+        if feature not in list(feature_names):
+            raise ValueError(f"{who}: lookahead feature {feature!r} is no observation column")
+        if obs_slot is not None and n_obs is not None:
+            slot = int(slot_map(obs_slot, n_obs)[list(feature_names).index(feature)])
+            if 24 <= slot <= 27 or ("alert_2wks" in set(fixes) and slot == slot_alerts_2wks):
+                raise ValueError(f"{who}: lookahead feature {feature!r} is not table-sourced (lookahead reads "
+                                 "table-sourced columns only)")
+    return feature, int(D)
 
 
 def slot_map(obs_slot, n_obs: int) -> np.ndarray:
@@ -69,16 +105,24 @@ def _tensor(x, name: str, device) -> torch.Tensor:
     return t.to(device)
 
 
-def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device) -> LinearPolicyArgs:
+def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device, feature_names=None, fixes=(),
+                        slot_alerts_2wks: int = -1) -> LinearPolicyArgs:
     """Validate a {"kind": "linear", ...} policy (ValueError on anything the kernel could not run as asked) and bring its
-    parameters into the kernel's form on `device`. One host reduction: the range of the group ids."""
+    parameters into the kernel's form on `device`. One host reduction: the range of the group ids. With "lookahead"
+    (check_lookahead; `feature_names`, `fixes` and `slot_alerts_2wks` serve its feature check) the weight is
+    [G, n_obs + D]: the D lookahead columns last, k = 1 first."""
     unknown = set(policy) - KEYS
     if unknown:
         raise ValueError(f"linear policy: unknown key(s) {sorted(unknown)}; choose from {sorted(KEYS)}")
+    look = check_lookahead(policy, "linear policy", feature_names, obs_slot, n_obs, fixes, slot_alerts_2wks)
+    D = 0 if look is None else look[1]
     w = _tensor(policy.get("weight"), "weight", device)
     if w.is_complex() or not (w.is_floating_point() or w.dtype in (torch.int32, torch.int64)):
         raise ValueError(f"linear policy: weight must be real numbers, got {w.dtype}")
-    if w.dim() != 2 or w.shape[1] != n_obs or w.shape[0] < 1:
+    if D and (w.dim() != 2 or w.shape[1] != n_obs + D or w.shape[0] < 1):
+        raise ValueError(f"linear policy: with lookahead days={D} weight must be [G, n_obs + D = {n_obs + D}] (the "
+                         f"lookahead columns last), got {tuple(w.shape)}")
+    if w.dim() != 2 or w.shape[1] != n_obs + D or w.shape[0] < 1:
         raise ValueError(f"linear policy: weight must be [G, n_obs={n_obs}], got {tuple(w.shape)}")
     G = int(w.shape[0])
     w = w.to(torch.float32)
@@ -110,8 +154,12 @@ def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, devic
     seed = policy.get("seed", 0)
     if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
         raise ValueError("linear policy: 'seed' must be an int")
-    return LinearPolicyArgs(to_slot_order(w, obs_slot, n_obs).contiguous(), b, g, G, bool(sample),
+    args = LinearPolicyArgs(to_slot_order(w[:, :n_obs], obs_slot, n_obs).contiguous(), b, g, G, bool(sample),
                             int(seed) & (2**64 - 1), bool(rb))
+    if look is not None:
+        args.look_feature, args.look_days = look
+        args.look_weight = torch.nn.functional.pad(w[:, n_obs:], (0, LOOKAHEAD_PAD - D)).contiguous()
+    return args
 
 
 PG_BASELINES = ("none", "no_alert")
@@ -360,7 +408,8 @@ def group_mean_columns(values_t: torch.Tensor, group: torch.Tensor | None, n_gro
 # One or two hidden layers of width 1..64; the first takes the n_obs observation columns in observation order; the
 # output has one row (the logit) or two (SB3's two action values: logit = row1 - row0, folded here in fp64).
 
-MLP_KEYS = {"kind", "layers", "activation", "group", "order", "sample", "seed", "require_budget", "allowed_days"}
+MLP_KEYS = {"kind", "layers", "activation", "group", "order", "sample", "seed", "require_budget", "allowed_days",
+            "lookahead"}
 MLP_WIDTHS = (16, 32, 64)  # the kernel's padded hidden widths
 MLP_MAX_HIDDEN = 2
 MLP_ACTIVATIONS = ("tanh", "relu")
@@ -369,6 +418,12 @@ MLP_ACTIVATIONS = ("tanh", "relu")
 def mlp_stride(width: int, n_layers: int) -> int:
     """Floats per group block of the packed parameters (w2a.h: W2A_MLP_STRIDE)."""
     return ROW_FLOATS * width + width + (width * width + width if n_layers == 2 else 0) + width + 4
+
+
+def mlp_lookahead_stride(width: int, n_layers: int) -> int:
+    """Floats per group block of a lookahead policy (w2a.h: W2A_MLP_LOOKAHEAD_STRIDE): the block of mlp_stride with
+    W1f[LOOKAHEAD_PAD][width], the first layer's rows of the lookahead inputs, appended."""
+    return mlp_stride(width, n_layers) + LOOKAHEAD_PAD * width
 
 
 def mlp_width(hidden) -> int:
@@ -394,6 +449,8 @@ class MlpPolicyArgs:
     hidden: tuple = ()           # the real (unpadded) hidden widths
     n_out: int = 1               # rows of the output layer as given (2: folded into row1 - row0)
     group_major: bool = False    # `order` is group_order(group), built here (no "order" key in the policy)
+    look_feature: str | None = None  # "lookahead": the feature's name, None without the key
+    look_days: int = 0               # D: params then has mlp_lookahead_stride floats per block
 
 
 def _real(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -402,12 +459,13 @@ def _real(t: torch.Tensor, what: str) -> torch.Tensor:
     return t.to(torch.float64)
 
 
-def _mlp_layers(layers, n_obs: int):
-    """The layers as fp64 [G or 1, out, in] / [G or 1, out] tensors, checked, and G."""
+def _mlp_layers(layers, n_obs: int, look_days: int = 0):
+    """The layers as fp64 [G or 1, out, in] / [G or 1, out] tensors, checked, and G. look_days = D > 0: the first layer
+    takes n_obs + D inputs, the D lookahead columns last."""
     if not isinstance(layers, (list, tuple)) or not 2 <= len(layers) <= MLP_MAX_HIDDEN + 1:
         raise ValueError(f"mlp policy: 'layers' must be a list of 2..{MLP_MAX_HIDDEN + 1} (weight, bias) pairs "
                          f"(1..{MLP_MAX_HIDDEN} hidden layers and the output layer)")
-    out, G, fan_in = [], None, n_obs
+    out, G, fan_in = [], None, n_obs + look_days
     for i, layer in enumerate(layers):
         if not isinstance(layer, (list, tuple)) or len(layer) != 2:
             raise ValueError(f"mlp policy: layer {i} must be a (weight, bias) pair")
@@ -441,14 +499,16 @@ def _mlp_layers(layers, n_obs: int):
     return out, (G or 1)
 
 
-def pack_mlp(layers, obs_slot, n_obs: int):
+def pack_mlp(layers, obs_slot, n_obs: int, look_days: int = 0):
     """Pack checked or raw layers into the kernel's layout (w2a.h: w2a_mlp_policy): f32 [G, stride] on the CPU, with
-    (width, n_layers, G). A two-row output is folded into logit = row1 - row0 in fp64 before rounding to f32."""
-    L, G = _mlp_layers(layers, n_obs)
+    (width, n_layers, G). A two-row output is folded into logit = row1 - row0 in fp64 before rounding to f32.
+    look_days = D > 0 (policy["lookahead"]): the first layer's weight is [out, n_obs + D]; its last D columns go, k = 1
+    first, into W1f[LOOKAHEAD_PAD][width] at the block's tail (mlp_lookahead_stride; nothing before the tail moves)."""
+    L, G = _mlp_layers(layers, n_obs, look_days)
     hidden = [int(W.shape[1]) for W, _ in L[:-1]]
     nl, w = len(hidden), mlp_width(hidden)
     s = torch.as_tensor(slot_map(obs_slot, n_obs))
-    P = torch.zeros((G, mlp_stride(w, nl)), dtype=torch.float64)
+    P = torch.zeros((G, mlp_lookahead_stride(w, nl) if look_days else mlp_stride(w, nl)), dtype=torch.float64)
     off = 0
 
     def put(dst_shape, src):
@@ -459,7 +519,7 @@ def pack_mlp(layers, obs_slot, n_obs: int):
 
     W1, b1 = (x.expand(G, *x.shape[1:]) for x in L[0])
     W1s = torch.zeros((G, ROW_FLOATS, w), dtype=torch.float64)
-    W1s[:, s, :hidden[0]] = W1.transpose(1, 2)
+    W1s[:, s, :hidden[0]] = W1[:, :, :n_obs].transpose(1, 2)
     put((ROW_FLOATS, w), W1s)
     put((w,), torch.nn.functional.pad(b1, (0, w - hidden[0])))
     if nl == 2:
@@ -473,22 +533,27 @@ def pack_mlp(layers, obs_slot, n_obs: int):
         Wo, bo = Wo[:, 1:] - Wo[:, :1], bo[:, 1:] - bo[:, :1]
     put((w,), torch.nn.functional.pad(Wo[:, 0], (0, w - hidden[-1])))
     P[:, off] = bo[:, 0]
+    if look_days:
+        tail = mlp_stride(w, nl)
+        P[:, tail:].view(G, LOOKAHEAD_PAD, w)[:, :look_days, :hidden[0]] = W1[:, :, n_obs:].transpose(1, 2)
     P = P.to(torch.float32)
     if not bool(torch.isfinite(P).all()):
         raise ValueError("mlp policy: the folded output row (row1 - row0) is not finite as float32")
     return P, w, nl, G
 
 
-def unpack_mlp_grad(P, obs_slot, n_obs: int, hidden, n_out: int = 1):
+def unpack_mlp_grad(P, obs_slot, n_obs: int, hidden, n_out: int = 1, look_days: int = 0):
     """A gradient in the kernel's block layout (f32 or f64 [G, mlp_stride(width, n_layers)], as w2a_policy_gradient_mlp
     writes it) -> layers [(dW [G, out, in], db [G, out]), ...] in torch's Linear convention with the real widths
     `hidden` and `n_out` output rows: the adjoint of pack_mlp's placement, <pack(L), P> = <L, unpack(P)>. Padding units
     and non-observation slots are dropped; a two-row output gets +g on row 1 and -g on row 0 (the adjoint of the fold
-    logit = row1 - row0)."""
+    logit = row1 - row0). look_days = D > 0: P has mlp_lookahead_stride floats per block and the first layer's dW is
+    [G, out, n_obs + D], the lookahead columns (from the tail W1f) last."""
     hidden = [int(h) for h in hidden]
     nl, w = len(hidden), mlp_width(hidden)
-    if P.dim() != 2 or P.shape[1] != mlp_stride(w, nl):
-        raise ValueError(f"unpack_mlp_grad: expected [G, {mlp_stride(w, nl)}] for hidden widths {hidden}, got {tuple(P.shape)}")
+    want = mlp_lookahead_stride(w, nl) if look_days else mlp_stride(w, nl)
+    if P.dim() != 2 or P.shape[1] != want:
+        raise ValueError(f"unpack_mlp_grad: expected [G, {want}] for hidden widths {hidden}, got {tuple(P.shape)}")
     if n_out not in (1, 2):
         raise ValueError(f"unpack_mlp_grad: n_out must be 1 or 2, got {n_out}")
     G = int(P.shape[0])
@@ -503,7 +568,11 @@ def unpack_mlp_grad(P, obs_slot, n_obs: int, hidden, n_out: int = 1):
         return v
 
     W1s = take((ROW_FLOATS, w))
-    layers = [(W1s[:, s, :hidden[0]].transpose(1, 2).contiguous(), take((w,))[:, :hidden[0]].contiguous())]
+    dW1 = W1s[:, s, :hidden[0]].transpose(1, 2)
+    if look_days:
+        W1f = P[:, mlp_stride(w, nl):].reshape(G, LOOKAHEAD_PAD, w)
+        dW1 = torch.cat([dW1, W1f[:, :look_days, :hidden[0]].transpose(1, 2)], dim=2)
+    layers = [(dW1.contiguous(), take((w,))[:, :hidden[0]].contiguous())]
     if nl == 2:
         W2p = take((w, w))
         layers.append((W2p[:, :hidden[0], :hidden[1]].transpose(1, 2).contiguous(), take((w,))[:, :hidden[1]].contiguous()))
@@ -719,18 +788,22 @@ def group_order(group: torch.Tensor) -> torch.Tensor:
     return torch.sort(group, stable=True).indices.to(torch.int32).contiguous()
 
 
-def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device) -> MlpPolicyArgs:
+def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device, feature_names=None, fixes=(),
+                     slot_alerts_2wks: int = -1) -> MlpPolicyArgs:
     """Validate a {"kind": "mlp", ...} policy (ValueError on anything the kernel could not run as asked) and bring its
-    parameters into the kernel's layout on `device`."""
+    parameters into the kernel's layout on `device`. With "lookahead" (check_lookahead; `feature_names`, `fixes` and
+    `slot_alerts_2wks` serve its feature check) the first layer takes n_obs + D inputs."""
     unknown = set(policy) - MLP_KEYS
     if unknown:
         raise ValueError(f"mlp policy: unknown key(s) {sorted(unknown)}; choose from {sorted(MLP_KEYS)}")
+    look = check_lookahead(policy, "mlp policy", feature_names, obs_slot, n_obs, fixes, slot_alerts_2wks)
+    D = 0 if look is None else look[1]
     act = policy.get("activation", "tanh")
     if act not in MLP_ACTIVATIONS:
         raise ValueError(f"mlp policy: activation must be one of {MLP_ACTIVATIONS}, got {act!r}")
     if "layers" not in policy:
         raise ValueError("mlp policy: 'layers' is required")
-    P, width, nl, G = pack_mlp(policy["layers"], obs_slot, n_obs)
+    P, width, nl, G = pack_mlp(policy["layers"], obs_slot, n_obs, D)
     g = policy.get("group")
     if g is None:
         if G != 1:
@@ -766,7 +839,8 @@ def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device) 
         raise ValueError("mlp policy: 'seed' must be an int")
     shapes = [tuple(np.shape(W)) for W, _ in policy["layers"]]
     return MlpPolicyArgs(P.to(device).contiguous(), g, order, G, nl, width, act, bool(sample), int(seed) & (2**64 - 1),
-                         bool(rb), tuple(int(sh[-2]) for sh in shapes[:-1]), int(shapes[-1][-2]), group_major)
+                         bool(rb), tuple(int(sh[-2]) for sh in shapes[:-1]), int(shapes[-1][-2]), group_major,
+                         None if look is None else look[0], D)
 
 
 def mlp_from_module(module: torch.nn.Module, group=None) -> dict:
