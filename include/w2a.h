@@ -1138,6 +1138,57 @@ int w2a_lookahead_imitation_gradient_linear(w2a_env *env, const w2a_linear_polic
                                             const w2a_lookahead *lookahead, const uint32_t *allowed_days,
                                             int32_t allowed_words);
 
+/* Hindsight values along a GIVEN schedule (additions to ABI 18, nothing above changes): what the DP of
+ * w2a_hindsight_optimum says in the states a caller's schedule reaches, not only on the optimum's own path -- the
+ * expert labels of DAgger / hindsight relabelling and the share of every day's decision in the regret.
+ * The env is walked from `start` along alert_mask for H = min(n_steps, n_days - t) days. The bits are ATTEMPTS: with
+ * allowed_days an attempt on a closed day is 0 before the budget test, and an attempt with used + j == budget issues
+ * nothing, as everywhere else. Let (j_s, streak_s) be the state on call-day s. With the recurrence, the fp64 values,
+ * the bit-identical f32 rewards and the strict comparison of w2a_hindsight_optimum (under the same gate),
+ *     Q0 = r0 + V_{d+1}(j, 0),    Q1 = r1 + V_{d+1}(j + 1, streak + 1)   (Q1 only while used + j < budget on an allowed day)
+ *   start, n_steps   as w2a_hindsight_optimum
+ *   alert_mask   device u32 [num_envs][mask_words], the schedule (w2a_rollout's or w2a_hindsight_optimum's format)
+ *   allowed_days, allowed_words   nullable gate (NULL: every day is allowed and allowed_words is not read)
+ *   gain_out     device f32 [min(n_steps, T)][num_envs] by call-day and ENV ID: (float)(Q1 - Q0), the difference in
+ *                fp64; NaN where no alert is possible that day (budget spent, day closed) and on call-days s >= H
+ *   expert_mask  device u32 [num_envs][mask_words]: bit t + s is set iff Q1 > Q0 in fp64 -- the DP's own decision in
+ *                that state; 0 where no alert is possible
+ *   regret_out   device f32 [num_envs]: the fp64 sum, in day order, of V_d(state) - Q_{a_s}, a_s the alert ISSUED on
+ *                call-day s, rounded once: V_0(start) less what the schedule earns
+ *   value_out    nullable f32 [min(n_steps, T)][num_envs]: (float)V_d(state) = max(Q0, Q1); 0 for s >= H
+ *   loss_out     nullable f32 [min(n_steps, T)][num_envs]: (float)(V_d(state) - Q_{a_s}) >= 0, exactly +0 where the
+ *                alert issued is the expert's bit; 0 for s >= H
+ *   workspace    as w2a_hindsight_optimum: w2a_hindsight_workspace_bytes(env, n_steps, max_remaining, 1) bytes
+ * Envs finished on entry (or with t >= n_days) get 0, NaN gains and an empty bitmap; a start state outside the tables
+ * gives NaN in every float output and an empty bitmap.
+ * Numerics contract: the backward sweep is w2a_hindsight_optimum's, statement for statement, so along that call's own
+ * schedule expert_mask is the schedule, every loss is +0 and the regret is 0; the values of a state do not depend on
+ * the start the DP was run from, so rows s >= k equal the rows of a call from the state reached after k days, bit for
+ * bit. One lane writes each output, the regret is added by one lane in day order, and there are no atomics on outputs:
+ * identical calls give identical bits.
+ * Synchronises `stream` and refuses as w2a_hindsight_optimum (every refusal before any output is written); reads the
+ * tables and the caller's arrays only. */
+int w2a_hindsight_along(w2a_env *env, const w2a_state_view *start, int32_t n_steps, const uint32_t *alert_mask,
+                        int32_t mask_words, const uint32_t *allowed_days, int32_t allowed_words, float *gain_out,
+                        uint32_t *expert_mask, float *regret_out, float *value_out, float *loss_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* Imitation with the labels apart from the schedule (DAgger): the arguments of w2a_imitation_gradient_linear_gated /
+ * w2a_imitation_gradient_mlp_gated with `labels`, a second bitmap in alert_mask's format, after mask_words, and
+ * allowed_days nullable (NULL: no gate). The env is still forced along alert_mask -- rows, budget, streak, gate and
+ * require_budget exactly as there, and the same days are scored -- while delta_s = labels_s - sigmoid(z_s) and the
+ * log-likelihood term take labels_s. With labels == alert_mask every output is the sibling's, bit for bit.
+ * The checks of the sibling in the same order, then W2A_ERR_ARG for NULL labels. */
+int w2a_relabel_imitation_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                 int32_t mask_words, const uint32_t *labels, const float *env_weight,
+                                 const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
+                                 float *grad, float *loglik, int32_t *days, void *stream, const uint32_t *allowed_days,
+                                 int32_t allowed_words);
+int w2a_relabel_imitation_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                              int32_t mask_words, const uint32_t *labels, const float *env_weight,
+                              const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
+                              float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                              void *stream, const uint32_t *allowed_days, int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ SYMBOLS = [
     "w2a_lookahead_rollout_linear", "w2a_lookahead_rollout_linear_gated", "w2a_lookahead_rollout_mlp",
     "w2a_lookahead_rollout_mlp_gated", "w2a_lookahead_policy_gradient_linear",
     "w2a_lookahead_imitation_gradient_linear",
+    "w2a_hindsight_along", "w2a_relabel_imitation_linear", "w2a_relabel_imitation_mlp",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -308,6 +309,18 @@ def load(build_if_missing: bool = True):
     lib.w2a_lookahead_policy_gradient_linear.argtypes = lib.w2a_policy_gradient_linear.argtypes + look + [vp, i32]
     lib.w2a_lookahead_imitation_gradient_linear.restype = C.c_int
     lib.w2a_lookahead_imitation_gradient_linear.argtypes = lib.w2a_imitation_gradient_linear_weighted.argtypes + look + [vp, i32]
+    # hindsight values along a schedule: start, n_steps, the schedule, the nullable gate, gain, expert bitmap, regret,
+    # the nullable value and loss, the workspace and the stream
+    lib.w2a_hindsight_along.restype = C.c_int
+    lib.w2a_hindsight_along.argtypes = [vp, C.POINTER(StateView), i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp,
+                                        C.c_size_t, vp]
+    # the gated imitation calls with the labels after mask_words
+    lib.w2a_relabel_imitation_linear.restype = C.c_int
+    lib.w2a_relabel_imitation_linear.argtypes = [vp, C.POINTER(LinearPolicy), vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
+                                                 vp, vp] + gate
+    lib.w2a_relabel_imitation_mlp.restype = C.c_int
+    lib.w2a_relabel_imitation_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp,
+                                              vp, C.c_size_t, vp] + gate
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

@@ -1,4 +1,5 @@
-// w2a_hindsight.hip.h -- k_hs_plan / k_hs_scatter / k_hs_dp: every env's best alert schedule in hindsight, by exact DP
+// w2a_hindsight.hip.h -- k_hs_plan / k_hs_scatter / k_hs_dp: every env's best alert schedule in hindsight, by exact DP;
+// k_hs_along: the same DP's values and decisions in the states a given schedule reaches
 // Part of libw2a.so; included only by w2a_kernels.hip (one translation unit, see the file comment there).
 #ifndef W2A_HINDSIGHT_HIP_H
 #define W2A_HINDSIGHT_HIP_H
@@ -276,6 +277,199 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
   if (lane == 0) {
     a.ret[e] = ret;
     a.alerts[e] = (int32_t)n_alerts;
+  }
+}
+
+// ----------------------------------------------------------------------------------------
+// hindsight values along a GIVEN schedule (w2a_hindsight_along)
+// ----------------------------------------------------------------------------------------
+// The backward sweep above forms Q_d(state, no alert) and Q_d(state, alert) of every reachable state and keeps only
+// what the optimum's own path needs. k_hs_along runs the same sweep (the same statements: the same rewards, the same
+// fp64 values, the same strict comparison) and keeps, per day, the values of the ONE state a caller's schedule
+// reaches: the labels DAgger fits to and the per-day share of the regret.
+//   Forward first: every lane walks the schedule (attempts; closed days and attempts without budget are no-ops) and
+//   lane 0 leaves the day's state index and the alert issued in the fourth float of tl[d] (bit 31 the alert, bits
+//   0..29 the index), so LDS and workspace are those of k_hs_dp (the decision words' room is simply not used).
+//   In the sweep the lane whose idx is the path's holds q0, q1 and best: it writes the day's outputs, sets bit 30 of
+//   the word (the DP's decision in that state) and puts the fp64 loss where the day's prefix pz[d].x was (day d's
+//   statics are not read again). Afterwards every lane assembles the expert bitmap as the backtrack assembles its own,
+//   and lane 0 adds the losses in fp64 in day order. No atomics: identical calls give identical bits.
+struct HsAlongArgs {
+  HsArgs h;               // ret = regret_out, mask = expert_mask, alerts unused (NULL); gate NULL: GATE = false
+  const uint32_t *sched;  // [n][mask_words] the schedule: attempts by day of the episode
+  float *gain;            // [hb][n] by call-day and env id
+  float *value;           // [hb][n], nullable
+  float *loss;            // [hb][n], nullable
+};
+
+// k_hs_scatter for w2a_hindsight_along: the same counting sort; envs without a DP get 0 (NaN: a start outside the
+// tables) in every float output, NaN in every gain and an empty bitmap
+__global__ __launch_bounds__(256) void k_hs_along_scatter(const HsAlongArgs aa) {
+  const HsArgs &a = aa.h;
+  __shared__ uint32_t cnt[HS_BINS];
+  const uint32_t nb = (uint32_t)a.hb + 1u;
+  for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
+  __syncthreads();
+  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  uint32_t U = e < (uint64_t)a.n ? a.u_env[e] : HS_NONE;
+  if (U == HS_NONE || U == HS_BAD) {
+    if (e < (uint64_t)a.n) {
+      const float nan = __builtin_nanf(""), fill = U == HS_BAD ? nan : 0.0f;
+      a.ret[e] = fill;
+      for (int w = 0; w < a.mask_words; ++w) a.mask[e * (uint32_t)a.mask_words + w] = 0u;
+      for (uint32_t s = 0; s < (uint32_t)a.hb; ++s) {
+        const size_t o = (size_t)s * (size_t)a.n + e;
+        aa.gain[o] = nan;
+        if (aa.value) aa.value[o] = fill;
+        if (aa.loss) aa.loss[o] = fill;
+      }
+    }
+    U = HS_NONE;
+  }
+  const uint32_t rank = U != HS_NONE ? atomicAdd(&cnt[U], 1u) : 0u;
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nb; b += 256)
+    if (cnt[b]) cnt[b] = atomicAdd(&a.cursor[b], cnt[b]);
+  __syncthreads();
+  if (U != HS_NONE) a.order[cnt[U] + rank] = (uint32_t)e;
+}
+
+#define HS_PATH_ALERT 0x80000000u   // the alert the schedule issues that day
+#define HS_PATH_EXPERT 0x40000000u  // the DP's decision in the state the schedule reaches
+#define HS_PATH_IDX 0x3FFFFFFFu
+
+// one env per 64-lane workgroup, as k_hs_dp (GLOBAL, GATE, list, U, pool as there)
+template <bool GLOBAL, bool GATE>
+__global__ __launch_bounds__(HS_BLOCK) void k_hs_along(const HsAlongArgs aa, const uint32_t *list, uint32_t U, char *pool,
+                                                       size_t pool_stride) {
+  extern __shared__ __attribute__((aligned(16))) char hs_lds[];
+  const HsArgs &a = aa.h;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t e = list[blockIdx.x];
+  const HsEnv h = hs_env(a, e);
+  const uint32_t H = h.H, hb = (uint32_t)a.hb;
+  double2 *pz = reinterpret_cast<double2 *>(hs_lds);               // [hb] prefixes over slots 0..23 (b, e); .x: the loss
+  float4 *tl = reinterpret_cast<float4 *>(hs_lds + 16 * (size_t)hb);  // [hb] x28, x29, gate, the path's word
+  char *dp = GLOBAL ? pool + (size_t)blockIdx.x * pool_stride : hs_lds + hs_day_bytes(hb);
+  double *V0 = reinterpret_cast<double *>(dp);
+  double *V1 = V0 + hs_ns(U);
+
+  // the env's own coefficient rows (wave-uniform), f32 as stored
+  const float4 *wq = a.tb.W + (size_t)h.wrow * (2 * ROWF / 4);
+  // ---- day statics: lanes over days
+  const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
+  for (uint32_t d = lane; d < H; d += HS_BLOCK) {
+    const float4 *xp = a.tb.X + (size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4);
+    double zb = 0.0, ze = 0.0;
+#pragma unroll
+    for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
+      const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
+      zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
+      zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
+      zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
+      zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
+    }
+    const float4 x7 = xp[GATE_QUAD];
+    pz[d] = make_double2(zb, ze);
+    tl[d] = make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
+  }
+  HsCoef c;
+  {
+    const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
+    c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
+    c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
+  }
+  const int32_t rem0 = h.budget - (int32_t)h.used;  // remaining budget at the start; an alert needs j < rem0
+  for (uint32_t i = lane; i < hs_ns(U); i += HS_BLOCK) V1[i] = 0.0;  // V_H = 0
+  __syncthreads();
+
+  // ---- forward along the schedule from (0, s0): the state of every day (every lane the same path)
+  {
+    uint32_t j = 0, k = h.s0 > 0 ? 1u : 0u;
+    uint32_t sch_word = 0, sch_idx = 0xFFFFFFFFu, gate_word = 0, gate_idx = 0xFFFFFFFFu;
+    for (uint32_t d = 0; d < H; ++d) {
+      const uint32_t tt = h.t0 + d;
+      uint32_t act = im_label_bits(aa.sched, a.mask_words, e, tt, sch_word, sch_idx);
+      if (GATE && !gate_allows(a.gate, a.gate_words, e, tt, gate_word, gate_idx)) act = 0u;  // before the budget test
+      if ((int32_t)j >= rem0) act = 0u;  // an attempt with no budget left issues nothing
+      if (lane == 0) reinterpret_cast<uint32_t *>(tl + d)[3] = (j * (j + 3u) / 2u + k) | (act ? HS_PATH_ALERT : 0u);
+      j += act;
+      k = act ? k + 1u : 0u;
+    }
+  }
+  __syncthreads();
+
+  // ---- backward DP (k_hs_dp's, statement for statement): V_{d+1} in vn, V_d into vc
+  double *vn = V1, *vc = V0;
+  uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
+  const size_t n = (size_t)a.n;
+  for (int32_t d = (int32_t)H - 1; d >= 0; --d) {
+    const bool open = !GATE || gate_allows(a.gate, a.gate_words, e, h.t0 + (uint32_t)d, gate_word, gate_idx);
+    const uint32_t J = min((uint32_t)d, U);
+    const uint32_t nsd = hs_ns(J);
+    const double2 p = pz[d];
+    const float4 tq = tl[d];
+    const uint32_t path = __float_as_uint(tq.w);
+    const bool day0 = (h.t0 + (uint32_t)d) == 0u, gate = tq.z != 0.0f;
+    bool mine = false, mine_alert = false;  // this lane holds the path's state of day d
+    double mine_loss = 0.0;
+    for (uint32_t c0 = 0; c0 < nsd; c0 += HS_BLOCK) {
+      const uint32_t idx = c0 + lane;
+      const bool valid = idx < nsd;
+      if (valid) {
+        const uint32_t j = hs_row(idx), k = idx - j * (j + 3u) / 2u;
+        const float s = (float)(k == j + 1u ? h.s0 + j : k);
+        const int32_t rem = h.budget - (int32_t)(h.used + j);
+        const bool allowed = (int32_t)j < rem0 && open;
+        const float r0 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem, 0u);
+        const double q0 = (double)r0 + vn[j * (j + 3u) / 2u];
+        double best = q0, q1 = q0;
+        bool alert = false;
+        if (allowed) {
+          const float r1 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem - 1, 1u);
+          q1 = (double)r1 + vn[(j + 1u) * (j + 4u) / 2u + k + 1u];
+          alert = q1 > q0;
+          best = alert ? q1 : q0;
+        }
+        vc[idx] = best;
+        if (idx == (path & HS_PATH_IDX)) {
+          const size_t o = (size_t)d * n + e;
+          mine = true;
+          mine_alert = alert;
+          mine_loss = best - ((path & HS_PATH_ALERT) ? q1 : q0);  // an issued alert was allowed: q1 is its value
+          aa.gain[o] = allowed ? (float)(q1 - q0) : __builtin_nanf("");
+          if (aa.value) aa.value[o] = (float)best;
+          if (aa.loss) aa.loss[o] = (float)mine_loss;
+        }
+      }
+    }
+    if (mine) {  // day d's statics have been read by every lane: their room takes the day's results
+      pz[d].x = mine_loss;
+      reinterpret_cast<uint32_t *>(tl + d)[3] = path | (mine_alert ? HS_PATH_EXPERT : 0u);
+    }
+    __syncthreads();
+    double *tmp = vn; vn = vc; vc = tmp;
+  }
+
+  // ---- the expert's bits along the path (every lane the same days), the regret in fp64 in day order
+  uint32_t word = 0;
+  for (uint32_t d = 0; d < H; ++d) {
+    const uint32_t tt = h.t0 + d;
+    const uint32_t path = reinterpret_cast<const uint32_t *>(tl + d)[3];
+    if ((path & HS_PATH_EXPERT) && lane == (tt >> 5)) word |= 1u << (tt & 31u);
+  }
+  for (uint32_t w = lane; w < (uint32_t)a.mask_words; w += HS_BLOCK)
+    a.mask[(size_t)e * (uint32_t)a.mask_words + w] = w < HS_BLOCK && w == lane ? word : 0u;
+  if (lane == 0) {
+    double regret = 0.0;
+    for (uint32_t d = 0; d < H; ++d) regret += pz[d].x;
+    a.ret[e] = (float)regret;
+  }
+  for (uint32_t s = H + lane; s < hb; s += HS_BLOCK) {  // call-days the env does not step
+    const size_t o = (size_t)s * n + e;
+    aa.gain[o] = __builtin_nanf("");
+    if (aa.value) aa.value[o] = 0.0f;
+    if (aa.loss) aa.loss[o] = 0.0f;
   }
 }
 

@@ -29,6 +29,8 @@ struct ImitationArgs {
   const float *day_weight;     // [n_steps][n] d_{s,e} by call-day and ENV ID (nullable = 1): c_s = w_e delta_s d_{s,e}
   float *loglik;               // [n] sum_s m_s log pi(a*_s | o_s)
   int32_t *days;               // [n] sum_s m_s
+  const uint32_t *labels;      // [n][mask_words] the LABELS forms only (w2a_relabel_imitation_*): a*_s, while alert_mask
+                               // still forces the env (DAgger: the learner's states, the expert's actions)
 };
 
 struct ImLinearArgs {
@@ -59,6 +61,14 @@ __device__ __forceinline__ uint32_t im_label(const ImitationArgs &im, uint32_t e
   return im_label_bits(im.alert_mask, im.mask_words, e, t, word, idx);
 }
 
+// a*_s of the decision of day t: the schedule's own bit `lab`, or with LABELS the bit of im.labels (its word cached apart)
+template <bool LABELS>
+__device__ __forceinline__ uint32_t im_target(const ImitationArgs &im, uint32_t e, uint32_t t, uint32_t lab,
+                                              uint32_t &word, uint32_t &idx) {
+  if constexpr (LABELS) return im_label_bits(im.labels, im.mask_words, e, t, word, idx);
+  else return lab;
+}
+
 // c_s = w_e delta_s, times the day's weight where the caller gave one (the products are fp64)
 __device__ __forceinline__ double im_coef(const ImitationArgs &im, double w_e, float delta, size_t day_env) {
   const double c = w_e * (double)delta;
@@ -77,7 +87,9 @@ __device__ __forceinline__ double im_log_pi(double z, uint32_t a) {
 // LOOK (w2a_lookahead_imitation_gradient_linear; GATE when its nullable allowed_days is given): the logit chain goes on over the lookahead inputs of
 // the held row's day, as k_rollout_linear<.., LOOK>, and D more fp64 accumulators take c f_k. LOOK = false compiles
 // from the statements it had before.
-template <bool GATE, bool LOOK = false>
+// LABELS (w2a_relabel_imitation_linear): the schedule still forces the env and decides m_s; delta_s and the
+// log-likelihood take a*_s from ia.im.labels. LABELS = false scores the schedule's own bit, as before.
+template <bool GATE, bool LOOK = false, bool LABELS = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArgs ia) {
   const LinearRolloutArgs &la = ia.l;
   const RolloutArgs &a = la.r;
@@ -117,6 +129,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
   for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = 0.0;
   const double w_e = ia.im.env_weight ? (double)ia.im.env_weight[e] : 1.0;
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
+  uint32_t tgt_word = 0, tgt_idx = 0xFFFFFFFFu;
   uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   double g[32];
 #pragma unroll
@@ -140,7 +153,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
     scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
     if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
     if (scores) {
-      const float delta = (float)lab - sigmoid_f32((float)z);
+      const uint32_t tgt = im_target<LABELS>(ia.im, e, t, lab, tgt_word, tgt_idx);
+      const float delta = (float)tgt - sigmoid_f32((float)z);
       const double c = im_coef(ia.im, w_e, delta, e);
 #pragma unroll
       for (int k = 0; k < RO64_SLOTS; ++k)
@@ -150,7 +164,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
 #pragma unroll
         for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = c * (double)lf[k];
       }
-      ll = im_log_pi(z, lab);
+      ll = im_log_pi(z, tgt);
       scored = 1;
     }
   }
@@ -199,7 +213,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
         scores = !(a.pol.require_budget && budget - (int32_t)used <= 0);
         if (GATE && !gate_allows(la.gate, la.gate_words, e, t, gate_word, gate_idx)) scores = false;
         if (scores) {
-          const float delta = (float)lab - sigmoid_f32((float)zp);
+          const uint32_t tgt = im_target<LABELS>(ia.im, e, t, lab, tgt_word, tgt_idx);
+          const float delta = (float)tgt - sigmoid_f32((float)zp);
           const double c = im_coef(ia.im, w_e, delta, (size_t)(s + 1) * n + e);
 #pragma unroll
           for (int k = 0; k < RO64_SLOTS; ++k)
@@ -209,7 +224,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
 #pragma unroll
             for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = fma(c, (double)lf[k], gl[k]);
           }
-          ll += im_log_pi(zp, lab);
+          ll += im_log_pi(zp, tgt);
           scored += 1;
         }
       }
@@ -232,8 +247,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
 
 // ------------------------------------------------------------------------------------------------ MLP: pass 1
 // GATE (w2a_imitation_gradient_mlp_gated): as k_imitation_linear<GATE>; GATE = false compiles from the statements it
-// had before the gate existed
-template <int WIDTH, int LAYERS, bool GATE>
+// had before the gate existed. LABELS (w2a_relabel_imitation_mlp): as k_imitation_linear<.., LABELS>
+template <int WIDTH, int LAYERS, bool GATE, bool LABELS = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
   const MlpGradArgs &ga = ia.g;
@@ -259,6 +274,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
   const size_t n = (size_t)a.n;
   const double w_e = ia.im.env_weight ? (double)ia.im.env_weight[e] : 1.0;
   uint32_t lab_word = 0, lab_idx = 0xFFFFFFFFu;
+  uint32_t tgt_word = 0, tgt_idx = 0xFFFFFFFFu;
   double ll = 0.0;
   int32_t scored = 0, n_valid = 0;
   uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
@@ -273,7 +289,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
     const uint32_t lab = active ? im_label(ia.im, e, t, lab_word, lab_idx) : 0u;  // a*_s: the schedule's bit
     const float p = sigmoid_f32(z);
     int32_t act = (int32_t)lab;
-    float delta = (float)act - p;
+    const uint32_t tgt = active ? im_target<LABELS>(ia.im, e, t, lab, tgt_word, tgt_idx) : 0u;  // a*_s
+    float delta = (float)(LABELS ? (int32_t)tgt : act) - p;
     bool scores = true;
     if (a.pol.require_budget && budget - (int32_t)used <= 0) { act = 0; delta = 0.0f; scores = false; }  // m_s = 0: forced
     if (GATE && active && !gate_allows(ma.gate, ma.gate_words, e, t, gate_word, gate_idx)) { act = 0; delta = 0.0f; scores = false; }
@@ -312,7 +329,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
       const size_t d = (size_t)s * n + slot;
       ga.day[d] = make_float2((float)im_coef(ia.im, w_e, delta, (size_t)s * n + e), 0.0f);  // pass 2: c_s = day.x (1 - 0)
       ga.day_alert[d] = (uint8_t)actual;
-      if (scores) { ll += im_log_pi((double)z, lab); scored += 1; }
+      if (scores) { ll += im_log_pi((double)z, tgt); scored += 1; }
       n_valid = s + 1;
       used = used2; hist = hist2;
       if (!done) { streak = actual ? streak + 1 : 0; t = t + 1; }
@@ -334,7 +351,9 @@ __global__ __launch_bounds__(BLOCK, 2) void k_im_pass1(const ImMlpArgs ia) {
 template <int WIDTH, int LAYERS>
 static void launch_im(const ImMlpArgs &ia, unsigned grid1, hipStream_t s) {
   const MlpGradArgs &ga = ia.g;
-  if (ga.m.gate) hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, true>), dim3(grid1), dim3(BLOCK), 0, s, ia);
+  if (ia.im.labels && ga.m.gate) hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, true, true>), dim3(grid1), dim3(BLOCK), 0, s, ia);
+  else if (ia.im.labels) hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, false, true>), dim3(grid1), dim3(BLOCK), 0, s, ia);
+  else if (ga.m.gate) hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, true>), dim3(grid1), dim3(BLOCK), 0, s, ia);
   else hipLaunchKernelGGL((k_im_pass1<WIDTH, LAYERS, false>), dim3(grid1), dim3(BLOCK), 0, s, ia);
   hipLaunchKernelGGL(k_pgm_count, dim3(ga.n_chunks), dim3(64), 0, s, ga);
   hipLaunchKernelGGL(k_pgm_scan, dim3(1), dim3(1024), 0, s, ga);

@@ -894,9 +894,12 @@ size_t w2a_hindsight_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_
 
 static int hindsight_optimum(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
                              uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
-                             size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words) {
+                             size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words,
+                             const HsAlongArgs *along = nullptr) {
+  // `along` (w2a_hindsight_along): the schedule to walk and the per-day outputs; ret_out is then the regret, alert_mask
+  // the expert's bitmap, and alerts_out is not written
   // what can be checked without the handle first (so that it is checked on any machine)
-  if (!start || !ret_out || !alert_mask || !alerts_out || !workspace)
+  if (!start || !ret_out || !alert_mask || (!alerts_out && !along) || !workspace || (along && (!along->sched || !along->gain)))
     return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
   if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
       !start->year_i || !start->coef_col || !start->sample || !start->finished)
@@ -964,11 +967,42 @@ static int hindsight_optimum(const char *fn, w2a_env *env, const w2a_state_view 
       return fail(W2A_ERR_ARG, "%s: workspace too small for the largest budget in the batch "
                                "(w2a_hindsight_workspace_bytes(env, n_steps, max(budget - used), 1) suffices)", fn);
   HIP_TRY(hipMemcpyAsync(a.cursor, off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
+  HsAlongArgs aa;
+  if (along) {
+    aa = *along;
+    aa.h = a;
+    hipLaunchKernelGGL(k_hs_along_scatter, dim3(grid), dim3(256), 0, s, aa);
+  } else {
+    hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
+  }
   HIP_TRY(hipGetLastError());
   for (uint32_t u = 0; u <= hb; ++u) {
     if (!hist[u]) continue;
     const size_t need = hs_day_bytes(hb) + hs_dp_bytes(u, hb);
+    if (along) {  // the same split between LDS and the pool, the same launches
+      if (need <= HS_LDS_CAP) {
+        if (gated)
+          hipLaunchKernelGGL((k_hs_along<false, true>), dim3(hist[u]), dim3(HS_BLOCK), need, s, aa, a.order + off[u], u, nullptr, (size_t)0);
+        else
+          hipLaunchKernelGGL((k_hs_along<false, false>), dim3(hist[u]), dim3(HS_BLOCK), need, s, aa, a.order + off[u], u, nullptr, (size_t)0);
+        HIP_TRY(hipGetLastError());
+        continue;
+      }
+      const size_t stride = align256(hs_dp_bytes(u, hb));
+      const size_t fit = pool_bytes / stride;
+      const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
+      for (uint32_t i = 0; i < hist[u]; i += per) {
+        const uint32_t cnt = min(per, hist[u] - i);
+        if (gated)
+          hipLaunchKernelGGL((k_hs_along<true, true>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, aa, a.order + off[u] + i, u,
+                             pool, stride);
+        else
+          hipLaunchKernelGGL((k_hs_along<true, false>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, aa, a.order + off[u] + i, u,
+                             pool, stride);
+        HIP_TRY(hipGetLastError());
+      }
+      continue;
+    }
     if (need <= HS_LDS_CAP) {
       if (gated)
         hipLaunchKernelGGL((k_hs_dp<false, true>), dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
@@ -1009,6 +1043,17 @@ int w2a_hindsight_optimum_gated(w2a_env *env, const w2a_state_view *start, int32
                                 int32_t allowed_words) {
   return hindsight_optimum("w2a_hindsight_optimum_gated", env, start, n_steps, ret_out, alert_mask, mask_words, alerts_out, workspace, workspace_bytes,
                            stream, true, allowed_days, allowed_words);
+}
+
+int w2a_hindsight_along(w2a_env *env, const w2a_state_view *start, int32_t n_steps, const uint32_t *alert_mask,
+                        int32_t mask_words, const uint32_t *allowed_days, int32_t allowed_words, float *gain_out,
+                        uint32_t *expert_mask, float *regret_out, float *value_out, float *loss_out, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+  HsAlongArgs along;
+  memset(&along, 0, sizeof(along));
+  along.sched = alert_mask; along.gain = gain_out; along.value = value_out; along.loss = loss_out;
+  return hindsight_optimum("w2a_hindsight_along", env, start, n_steps, regret_out, expert_mask, mask_words, nullptr, workspace,
+                           workspace_bytes, stream, allowed_days != nullptr, allowed_days, allowed_words, &along);
 }
 
 int w2a_alert_gate(w2a_env *env, int32_t obs_col, float threshold, const float *thresholds, int32_t n_steps,

@@ -782,7 +782,8 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
                                      const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
                                      float *grad, float *loglik, int32_t *days, void *stream, bool gated = false,
                                      const uint32_t *gate = nullptr, int32_t gate_words = 0, bool looking = false,
-                                     const w2a_lookahead *look = nullptr) {
+                                     const w2a_lookahead *look = nullptr, bool relabel = false,
+                                     const uint32_t *labels = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_imitation(fn, alert_mask, obs, grad, loglik, days));
   W2A_CHECK(check_day_weight(fn, day_weight, day_weight_days, n_steps));
@@ -790,6 +791,7 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
   if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
   W2A_CHECK(refuse_while_capturing(fn, stream));
+  if (relabel && !labels) return fail(W2A_ERR_ARG, "%s: NULL labels (the actions to score along the schedule)", fn);
   ImLinearArgs ia;
   memset(&ia, 0, sizeof(ia));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, ia.l));
@@ -797,11 +799,14 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
   ia.l.r.pol.require_budget = policy->require_budget;
   ia.l.r.order = env->order;
   fill_imitation(ia.im, alert_mask, mask_words, env_weight, day_weight, loglik, days);
+  ia.im.labels = labels;
   ia.grad = grad;
   hipStream_t s = (hipStream_t)stream;
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = grid64(env);
-  if (looking && gated) hipLaunchKernelGGL((k_imitation_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  if (relabel && gated) hipLaunchKernelGGL((k_imitation_linear<true, false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  else if (relabel) hipLaunchKernelGGL((k_imitation_linear<false, false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  else if (looking && gated) hipLaunchKernelGGL((k_imitation_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
   else if (looking) hipLaunchKernelGGL((k_imitation_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
   else if (gated) hipLaunchKernelGGL(k_imitation_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ia);
   else hipLaunchKernelGGL(k_imitation_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ia);
@@ -848,12 +853,23 @@ int w2a_lookahead_imitation_gradient_linear(w2a_env *env, const w2a_linear_polic
                                    allowed_days != nullptr, allowed_days, allowed_words, true, lookahead);
 }
 
+// labels scored along the schedule that forces the env (DAgger); day_weight and allowed_days nullable (= 1, = no gate)
+int w2a_relabel_imitation_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                 int32_t mask_words, const uint32_t *labels, const float *env_weight,
+                                 const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
+                                 float *grad, float *loglik, int32_t *days, void *stream, const uint32_t *allowed_days,
+                                 int32_t allowed_words) {
+  return imitation_gradient_linear("w2a_relabel_imitation_linear", env, policy, alert_mask, mask_words, env_weight,
+                                   day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
+                                   allowed_days != nullptr, allowed_days, allowed_words, false, nullptr, true, labels);
+}
+
 static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy,
                                   const uint32_t *alert_mask, int32_t mask_words, const float *env_weight,
                                   const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
                                   float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
                                   void *stream, bool gated = false, const uint32_t *gate = nullptr,
-                                  int32_t gate_words = 0) {
+                                  int32_t gate_words = 0, bool relabel = false, const uint32_t *labels = nullptr) {
   W2A_CHECK(check_mlp_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_imitation(fn, alert_mask, obs, grad, loglik, days));
   W2A_CHECK(check_workspace_pointer(fn, workspace));
@@ -864,6 +880,7 @@ static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_po
                                 "%s: workspace smaller than w2a_imitation_gradient_mlp_workspace_bytes", L));
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
   W2A_CHECK(refuse_while_capturing(fn, stream));
+  if (relabel && !labels) return fail(W2A_ERR_ARG, "%s: NULL labels (the actions to score along the schedule)", fn);
   ImMlpArgs ia;
   memset(&ia, 0, sizeof(ia));
   W2A_CHECK(fill_mlp(fn, env, policy, n_steps, obs, gate, gate_words, ia.g.m));
@@ -871,6 +888,7 @@ static int imitation_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_po
   ia.g.m.r.order = mlp_own_order(policy);
   bind_pgm_workspace(ia.g, L, workspace, grad);
   fill_imitation(ia.im, alert_mask, mask_words, env_weight, day_weight, loglik, days);
+  ia.im.labels = labels;
   hipStream_t s = (hipStream_t)stream;
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = grid64(env);
@@ -907,6 +925,17 @@ int w2a_imitation_gradient_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy,
   return imitation_gradient_mlp("w2a_imitation_gradient_mlp_gated", env, policy, alert_mask, mask_words, env_weight,
                                 day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
                                 workspace_bytes, stream, true, allowed_days, allowed_words);
+}
+
+int w2a_relabel_imitation_mlp(w2a_env *env, const w2a_mlp_policy *policy, const uint32_t *alert_mask,
+                              int32_t mask_words, const uint32_t *labels, const float *env_weight,
+                              const float *day_weight, int32_t day_weight_days, int32_t n_steps, const float *obs,
+                              float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
+                              void *stream, const uint32_t *allowed_days, int32_t allowed_words) {
+  return imitation_gradient_mlp("w2a_relabel_imitation_mlp", env, policy, alert_mask, mask_words, env_weight,
+                                day_weight, day_weight_days, n_steps, obs, grad, loglik, days, workspace,
+                                workspace_bytes, stream, allowed_days != nullptr, allowed_days, allowed_words, true,
+                                labels);
 }
 
 // ---- surrogate gradients: read the canonical state words, change nothing else ---------------------------------------

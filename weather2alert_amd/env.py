@@ -1253,7 +1253,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
 
     # ------------------------------------------------------------------ imitation: likelihood of a given schedule
     def imitation_gradient(self, policy: dict, alert_days, env_weight=None, n_steps: int | None = None,
-                           day_weight=None) -> dict:
+                           day_weight=None, labels=None) -> dict:
         """The gradient of the log-likelihood of a GIVEN alert schedule under a linear or MLP policy: the supervised
         counterpart of rollout(policy_gradient=...). Every env is forced along its own schedule from its current state
         and the policy is evaluated on the rows it would have held (teacher forcing), all inside the kernel: behaviour
@@ -1276,6 +1276,12 @@ class HeatAlertVecEnv(_VectorEnvBase):
                       of that rollout with a learned baseline -- exactly so only under require_budget=True, where
                       attempts and issued alerts agree on every scored day; without it rollout(policy_gradient=...)
                       scores an attempt at the budget as a_s = 1 while "alert_days" holds 0 there
+          labels      optional second schedule, bool [N, T] or its packed int32 words (ValueError otherwise): the
+                      actions to SCORE, while alert_days still forces the env -- rows, budget, streak, gate and
+                      require_budget exactly as without it, and the same days are scored. delta_s = labels_s -
+                      sigmoid(z_s) and the log-likelihood takes labels_s: DAgger / hindsight relabelling with
+                      alert_days the learner's own rollout and labels hindsight_values(alert_days)["expert_alert_days"].
+                      labels equal to alert_days is the call without it, bit for bit. Not with "lookahead" (ValueError)
         Returns
           "policy_gradient"       linear: {"weight" f32 [G, n_obs], "bias" f32 [G]}; mlp: {"layers": [(dW, db), ...]}: the
                                   gradient of "group_log_likelihood" (shapes, column order and NaN for a group without
@@ -1295,9 +1301,13 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if kind == "mlp" and policy.get("lookahead") is not None:
             raise ValueError("imitation_gradient() takes 'lookahead' with kind 'linear' only; the mlp kind's gradient "
                              "kernels do not read the lookahead inputs yet")
+        if labels is not None and policy.get("lookahead") is not None:
+            raise ValueError("imitation_gradient(labels=...) does not take a 'lookahead' policy: the kernels that score "
+                             "labels apart from the schedule do not read the lookahead inputs")
         pol = _check_learned(self, policy)  # every argument is checked before anything runs
         dw = _policy.check_day_weight(day_weight, min(steps, 2**31 - 1), n, dev)
         gate = _policy.check_allowed_days(policy, n, ct.T, dev, "imitation_gradient()")
+        lab = None if labels is None else _policy.check_schedule(labels, "labels", n, ct.T, dev, "imitation_gradient()")
         if self._needs_reset:
             raise RuntimeError("call reset() before imitation_gradient()")
         if not self._obs_current:
@@ -1315,7 +1325,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 lp.group = None if pol.group is None else pol.group.data_ptr()
                 lp.n_groups, lp.sample, lp.require_budget, lp.seed = pol.n_groups, 0, int(pol.require_budget), 0
                 rows = torch.empty((ct.n_obs + 1 + pol.look_days, n), dtype=torch.float32, device=dev)
-                if pol.look_days:
+                if lab is not None:
+                    _ffi.check(self._lib.w2a_relabel_imitation_linear(
+                        self._h, C.byref(lp), mask.data_ptr(), words, lab.data_ptr(), wp,
+                        None if dw is None else dw.data_ptr(), 0 if dw is None else int(dw.shape[0]), steps,
+                        self._obs.data_ptr(), rows.data_ptr(), out["log_likelihood"].data_ptr(), out["days"].data_ptr(),
+                        self._stream(), None if gate is None else gate.data_ptr(),
+                        0 if gate is None else int(gate.shape[1])), "w2a_relabel_imitation_linear")
+                elif pol.look_days:
                     look = self._lookahead_struct(pol)
                     _ffi.check(self._lib.w2a_lookahead_imitation_gradient_linear(
                         self._h, C.byref(lp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
@@ -1358,7 +1375,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                      device=dev)
                 ws = torch.empty(self._lib.w2a_imitation_gradient_mlp_workspace_bytes(
                     n, steps, pol.n_groups, pol.width, pol.n_layers), dtype=torch.uint8, device=dev)
-                if gate is not None:
+                if lab is not None:
+                    _ffi.check(self._lib.w2a_relabel_imitation_mlp(
+                        self._h, C.byref(mp), mask.data_ptr(), words, lab.data_ptr(), wp,
+                        None if dw is None else dw.data_ptr(), 0 if dw is None else int(dw.shape[0]), steps,
+                        self._obs.data_ptr(), blocks.data_ptr(), out["log_likelihood"].data_ptr(),
+                        out["days"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream(),
+                        None if gate is None else gate.data_ptr(), 0 if gate is None else int(gate.shape[1])),
+                        "w2a_relabel_imitation_mlp")
+                elif gate is not None:
                     _ffi.check(self._lib.w2a_imitation_gradient_mlp_gated(
                         self._h, C.byref(mp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
                         0 if dw is None else int(dw.shape[0]), steps, self._obs.data_ptr(), blocks.data_ptr(),
@@ -1876,6 +1901,87 @@ class HeatAlertVecEnv(_VectorEnvBase):
         bits = torch.arange(32, device=dev, dtype=torch.int32)
         days = (((mask.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()
         return {"return": ret, "alert_days": days, "alerts": alerts}
+
+    def hindsight_values(self, alert_days, start_state: dict | None = None, n_steps: int | None = None,
+                         allowed_days=None, value: bool = False, loss: bool = False) -> dict:
+        """What hindsight_optimum()'s DP says in the states a GIVEN schedule reaches: the expert's action on every day
+        of a learner's own rollout (the labels of DAgger / hindsight relabelling, see imitation_gradient(labels=...))
+        and each day's share of the regret. The env is walked from start_state (a state() dict; default: the current
+        state) along alert_days for n_steps days (default: to the end of every episode), H_e = min(n_steps, n_days - t)
+        days per env.
+          alert_days    bool [N, T] by day of the episode or its packed int32 words (hindsight_optimum()["alert_days"],
+                        rollout(alert_mask=True)["alert_days"]): the actions ATTEMPTED; an attempt with no budget left
+                        is a no-op, as in step()
+          allowed_days  as hindsight_optimum(): an attempt on a closed day is 0 before the budget test, and the DP
+                        may alert only on allowed days
+        In the state of call-day s, with the recurrence, the fp64 values, the bit-identical rewards and the strict
+        comparison of hindsight_optimum(): Q0 = r0 + V(no alert), Q1 = r1 + V(alert), the latter only while budget is
+        left on an allowed day. Returns device tensors, [S, N] by call-day and env id as value_gradient()'s "advantage":
+            "alert_gain"         f32 [S, N]  Q1 - Q0 (the difference in fp64); NaN where no alert is possible (budget
+                                             spent, day closed, s >= H_e)
+            "expert_alert_days"  bool [N, T] day t0 + s is set iff Q1 > Q0: the DP's own decision in that state
+            "regret"             f32 [N]     the fp64 sum over the env's days of V(state) - Q(issued alert): the
+                                             optimum's value from start_state less what the schedule earns
+            "value"  (value=True) f32 [S, N] V(state) = max(Q0, Q1); 0 for s >= H_e
+            "loss"   (loss=True)  f32 [S, N] V(state) - Q(issued alert) >= 0, exactly 0 where the alert issued is the
+                                             expert's; 0 for s >= H_e
+        Along hindsight_optimum()'s own schedule the expert bits are the schedule and every loss and the regret are 0.
+        Envs finished in start_state give 0, NaN gains and no bits; a start state outside the tables gives NaN. Refuses
+        what hindsight_optimum() refuses, before anything is written; reads start_state, the tables and the schedule
+        only: the env's state, observation buffer and bookkeeping are untouched. w2a_hindsight_along (include/w2a.h)."""
+        who = "hindsight_values()"
+        self._check_hindsight(who)
+        ct, n, dev = self.ct, self.num_envs, self.device
+        mask = _policy.check_schedule(alert_days, "alert_days", n, ct.T, dev, who)
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        if start_state is None:
+            st = self._state_packed(_HS_FIELDS)[1]
+        else:
+            st = {}
+            for k in _HS_FIELDS:
+                if k not in start_state:
+                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
+                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
+                if st[k].shape != (n,):
+                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
+        if n_steps is not None and (isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer))):
+            raise ValueError(f"{who}: n_steps must be an int, got {n_steps!r}")
+        steps = int(n_steps) if n_steps is not None else ct.T
+        if steps <= 0:
+            raise ValueError(f"{who}: n_steps must be positive")
+        words = mask.shape[1]
+
+        def rows(fill):  # the library writes the first min(steps, T) call-days
+            if steps > ct.T:
+                return torch.full((steps, n), fill, dtype=torch.float32, device=dev)
+            return torch.empty((steps, n), dtype=torch.float32, device=dev)
+
+        gain = rows(float("nan"))
+        val = rows(0.0) if value else None
+        los = rows(0.0) if loss else None
+        expert = torch.empty((n, words), dtype=torch.int32, device=dev)
+        regret = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            live = (st["finished"] == 0) & (st["t"] < st["n_days"])
+            rem = 0
+            if n and not torch.cuda.is_current_stream_capturing():  # (a capture is refused by the library itself)
+                rem = int(torch.where(live, st["budget"] - st["used"], 0).max().item())
+            ws_bytes = self._lib.w2a_hindsight_workspace_bytes(self._h, steps, max(0, min(rem, 1 << 30)), _HS_BIG_ENVS)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            v = _ffi.StateView()
+            for k in _HS_FIELDS:
+                setattr(v, k, st[k].data_ptr())
+            _ffi.check(self._lib.w2a_hindsight_along(
+                self._h, C.byref(v), steps, mask.data_ptr(), words, None if gate is None else gate.data_ptr(),
+                0 if gate is None else int(gate.shape[1]), gain.data_ptr(), expert.data_ptr(), regret.data_ptr(),
+                None if val is None else val.data_ptr(), None if los is None else los.data_ptr(), ws.data_ptr(),
+                ws_bytes, self._stream()), "w2a_hindsight_along")
+        out = {"alert_gain": gain, "expert_alert_days": _policy.unpack_alert_days(expert, ct.T), "regret": regret}
+        if value:
+            out["value"] = val
+        if loss:
+            out["loss"] = los
+        return out
 
     def _check_hindsight(self, who: str):
         if self.fixes - {"budget"}:

@@ -249,6 +249,19 @@ def pack_alert_days(alert_days: torch.Tensor, words: int) -> torch.Tensor:
     return (a32 << shifts).sum(-1, dtype=torch.int32).contiguous()
 
 
+def check_schedule(days, name: str, num_envs: int, T: int, device, who: str) -> torch.Tensor:
+    """A schedule by day of the episode (hindsight_values()'s ``alert_days``, imitation_gradient()'s ``labels``) as the
+    packed bitmap int32 [num_envs, ceil(T / 32)] on `device`: a bool [num_envs, T] array is packed, words that are already
+    packed (a torch int32 tensor of that shape) are taken as they are, as check_allowed_days does. ValueError for None,
+    another dtype or another shape."""
+    if days is None:
+        raise ValueError(f"{who}: {name} is required")
+    words = (T + 31) // 32
+    if torch.is_tensor(days) and days.dtype == torch.int32 and tuple(days.shape) == (num_envs, words):
+        return days.to(device).contiguous()
+    return pack_alert_days(check_day_bitmap(days, name, num_envs, T, who).to(device), words)
+
+
 def check_imitation_args(kind, alert_days, env_weight, n_steps, num_envs: int, T: int, device, fixes=(),
                          who: str = "imitation_gradient()"):
     """The arguments of ``imitation_gradient()`` that are not the policy itself: ValueError for a kind other than linear
