@@ -1074,6 +1074,59 @@ int w2a_q_gradient_mlp(w2a_env *env, const w2a_mlp_policy *q, const w2a_mlp_poli
                        const float *obs, float *grad, float *loss_out, int32_t *days, float *ret, double gamma,
                        int32_t double_q, int32_t loss, double huber_delta, int32_t bootstrap, float *td_error,
                        float *td_target, void *workspace, size_t workspace_bytes, void *stream);
+/* Shared-trunk actor-critic: the ascent direction of PPO's objective for ONE network whose output layer keeps two rows,
+ * row 0 the policy logit z and row 1 the state value V, along a GIVEN alert schedule, reduced per group (additions to
+ * ABI 18). `net` points to blocks in the TWO-HEAD layout above. The env is forced along its schedule exactly as in
+ * w2a_surrogate_gradient_mlp_gated (the same bitmap, the same attempted-versus-issued rule, the same rows o_s, the same
+ * scored days m_s: a day net->require_budget forces, or allowed_days closes, is attempted as 0 and has no policy
+ * score; the value term still applies there). allowed_days = NULL: no gate, allowed_words is not read. Per group
+ *   J_g     = (1 / N_g) sum_e w_e sum_s [ m_s (L^clip_s + entropy_coef H_s) - (vf_coef / 2) (T_s - V_s)^2 ]
+ *   grad[g] = dJ_g/dtheta_g = (1 / N_g) sum_e sum_s ( c_pi,s dz_s/dtheta + c_v,s dV_s/dtheta ),
+ *   c_pi,s  = w2a_surrogate_gradient_mlp's coefficient, statement for statement (0 where m_s = 0)
+ *   c_v,s   = w_e vf_coef (T_s - V_s)
+ * The value loss carries the factor 1/2: stable-baselines3 takes vf_coef * mean (T - V)^2, whose gradient is twice this
+ * one's, so its vf_coef = 0.5 is vf_coef = 1.0 here.
+ * COLLECT (advantage, value_target and old_log_prob all NULL): the rewards are formed by w2a_value_gradient_mlp_gae's
+ * statements, delta_s = r_s + gamma Vn_s - V_s and A_s = delta_s + gamma lambda A_{s+1} come from the net's own row 1
+ * (Vn_s and bootstrap as there), T_s = A_s + V_s, rho_s = 1, nothing is clipped and T_s - V_s = A_s.
+ *   advantage_out, value_target_out, log_prob_out   f32 [n_steps][num_envs] by call-day and ENV ID, required: A_s and
+ *               T_s on stepped days, log pi(a_s | z_s) on scored days, 0 elsewhere (zero-filled on `stream` first).
+ *               Bit for bit w2a_value_gradient_mlp_gae's advantage / value_target for the one-output net (hidden layers
+ *               and row 1) and w2a_surrogate_gradient_mlp's log_prob for (hidden layers and row 0).
+ *   ret         f32 [num_envs], required: sum_s r_s (undiscounted)
+ *   grad        NULL: the first pass and the backward sweep alone (the arrays above and the per-env sums)
+ * EPOCH (all three given, f32 [>= n_steps][num_envs] by call-day and env id, *_days rows each): advantages and targets
+ * are fixed, rho_s = exp(lp_s - old_log_prob[s, e]) and the clip test are formed in the kernel, no reward is formed.
+ * advantage_out, value_target_out, log_prob_out and ret must be NULL, gamma = lambda = 1 and bootstrap = 0.
+ * Both modes:
+ *   grad        device f32 [n_groups][W2A_MLP_HEADS_STRIDE(width, n_layers)] in the two-head layout; a group without
+ *               envs gives a block of NaN; envs finished on entry contribute zero and count
+ *   surrogate, approx_kl, entropy f32 [num_envs], clipped_days, days i32 [num_envs]: as w2a_surrogate_gradient_mlp
+ *   value_loss  f32 [num_envs]: sum_s 1/2 (T_s - V_s)^2, unweighted by vf_coef
+ *   workspace   w2a_actor_critic_mlp_workspace_bytes(...) bytes, 256-B aligned: the layout of w2a_q_gradient_mlp (the
+ *               partial blocks at the two-head stride) followed by one f32 column [n_steps][num_envs], rounded up to
+ *               256 B, that holds z_s between a collect call's kernels. A smaller one is refused; nothing is written
+ *               past it.
+ * Numerics contract: both rows of a day come from ONE evaluation of the hidden layers and are, bit for bit, the f32
+ * logits k_rollout_mlp forms for the two one-output nets. delta_s is stored as f32; A_s, lp_s, rho_s, the clip test, the
+ * entropy and both coefficients are fp64; c_pi,s and c_v,s are rounded to f32 once and the second pass (one row
+ * rebuild, one forward, one backward: dh_last = (c_pi w_out0 + c_v w_out1) act') is w2a_policy_gradient_mlp's with both
+ * output rows fed; the fp64 sums over tiles and the reduction run unchanged. No atomics: identical calls give
+ * identical bits. Nothing is written but the outputs and the workspace.
+ * W2A_ERR_ARG for a NULL handle first, then where w2a_surrogate_gradient_mlp_gated refuses, in its order (the inputs'
+ * checks include: one or two of the three epoch arrays, outputs that the mode does not form, gamma or lambda outside
+ * [0, 1], a vf_coef that is negative or not finite); W2A_ERR_STATE while `stream` is recording a hipGraph. */
+size_t w2a_actor_critic_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                            int32_t n_layers);
+int w2a_actor_critic_mlp(w2a_env *env, const w2a_mlp_policy *net, const uint32_t *alert_mask, int32_t mask_words,
+                         const float *env_weight, const float *advantage, int32_t advantage_days,
+                         const float *value_target, int32_t value_target_days, const float *old_log_prob,
+                         int32_t old_log_prob_days, double clip, double vf_coef, double entropy_coef, double gamma,
+                         double lambda, int32_t bootstrap, int32_t n_steps, const float *obs, float *grad,
+                         float *surrogate, float *value_loss, int32_t *clipped_days, float *approx_kl, float *entropy,
+                         int32_t *days, float *ret, float *advantage_out, float *value_target_out, float *log_prob_out,
+                         void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                         int32_t allowed_words);
 
 /* Lookahead: learned policies that see the coming days' weather (the older reference env's incorp_forecasts / "D3" /
  * "D10" inputs with zero forecast error; additions to ABI 18, nothing above changes). The row an agent holds on env day

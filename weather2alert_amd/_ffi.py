@@ -41,6 +41,7 @@ SYMBOLS = [
     "w2a_fisher_vector_product_linear", "w2a_fisher_vector_product_mlp_workspace_bytes",
     "w2a_fisher_vector_product_mlp",
     "w2a_q_gradient_mlp_workspace_bytes", "w2a_q_gradient_mlp",
+    "w2a_actor_critic_mlp_workspace_bytes", "w2a_actor_critic_mlp",
     "w2a_lookahead_rollout_linear", "w2a_lookahead_rollout_linear_gated", "w2a_lookahead_rollout_mlp",
     "w2a_lookahead_rollout_mlp_gated", "w2a_lookahead_policy_gradient_linear",
     "w2a_lookahead_imitation_gradient_linear",
@@ -294,6 +295,14 @@ def load(build_if_missing: bool = True):
     lib.w2a_q_gradient_mlp.restype = C.c_int
     lib.w2a_q_gradient_mlp.argtypes = [vp, C.POINTER(MlpPolicy), C.POINTER(MlpPolicy), vp, i32, vp, i32, vp, vp, vp, vp,
                                        vp, C.c_double, i32, i32, C.c_double, i32, vp, vp, vp, C.c_size_t, vp]
+    # shared-trunk actor-critic: the net, the schedule, env_weight, the three epoch inputs with their day counts, clip,
+    # vf_coef, entropy_coef, gamma, lambda, bootstrap, n_steps, obs, grad, the six per-env sums, ret, the three collect
+    # outputs, the workspace, the stream and the nullable gate
+    lib.w2a_actor_critic_mlp_workspace_bytes.restype = C.c_size_t
+    lib.w2a_actor_critic_mlp_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+    lib.w2a_actor_critic_mlp.restype = C.c_int
+    lib.w2a_actor_critic_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, i32, vp, vp, i32, vp, i32, vp, i32] + \
+        [C.c_double] * 5 + [i32, i32, vp, vp] + [vp] * 6 + [vp] * 4 + [vp, C.c_size_t, vp] + gate
     lib.w2a_policy_actions.restype = C.c_int
     lib.w2a_policy_actions.argtypes = [vp, C.POINTER(Policy), vp, vp, vp, vp, vp, i32, vp]
     look = [C.POINTER(Lookahead)]

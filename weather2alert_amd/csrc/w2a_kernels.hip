@@ -63,6 +63,7 @@
 #include "w2a_value.hip.h"
 #include "w2a_gae.hip.h"
 #include "w2a_qlearn.hip.h"
+#include "w2a_actor_critic.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"

@@ -3,7 +3,8 @@
 // included only by w2a_kernels.hip inside its extern "C" block. No device code lives here.
 //
 // Twelve bodies serve those exports, two more the Fisher-vector products (w2a_fisher_vector_product_linear / _mlp,
-// which take their nullable gate directly) and one w2a_q_gradient_mlp (a second, nullable parameter struct: the target net). What they share is written once, in the helpers of the first half of this file:
+// which take their nullable gate directly) one w2a_q_gradient_mlp (a second, nullable parameter struct: the target net) and one w2a_actor_critic_mlp (the two-row
+// net of a shared trunk; nullable gate, nullable epoch inputs). What they share is written once, in the helpers of the first half of this file:
 //   check_linear_policy_struct / check_mlp_policy_struct   the checks of the policy struct (and n_steps): need no handle
 //   check_handle_common      NULL handle, the schedule's word count, corrected-semantics flags, 2^31 observation offsets
 //   check_mlp_stride / check_mlp_workspace                 2^31 floats of parameters; the PgmLayout workspace's size
@@ -1338,6 +1339,108 @@ int w2a_q_gradient_mlp(w2a_env *env, const w2a_mlp_policy *q, const w2a_mlp_poli
   W2A_CHECK(clear_day_rows(env, n_steps, td_target, s));
   const unsigned g64 = grid64(env);
   dispatch_mlp_shape(q->width, q->n_layers, [&](auto W, auto L_) { launch_qg<W(), L_()>(qa, g64, s); });
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
+}
+
+// ---- shared-trunk actor-critic ---------------------------------------------------------------------------------------
+// w2a_q_gradient_mlp's layout (the partial blocks at the two-head stride), then the collect call's z_s column
+static PgmLayout ac_layout(int64_t n, int32_t n_steps, int32_t n_groups, int32_t width, int32_t n_layers, size_t &day_z) {
+  PgmLayout L = pgm_layout(n, n_steps, n_groups, width, n_layers, 2);
+  day_z = L.bytes;
+  L.bytes += align256(sizeof(float) * (size_t)n * (size_t)n_steps);
+  return L;
+}
+
+size_t w2a_actor_critic_mlp_workspace_bytes(int64_t num_envs, int32_t n_steps, int32_t n_groups, int32_t width,
+                                            int32_t n_layers) {
+  if (num_envs <= 0 || n_steps <= 0 || n_groups <= 0) return 0;
+  if ((width != 16 && width != 32 && width != 64) || (n_layers != 1 && n_layers != 2)) return 0;
+  size_t day_z;
+  return ac_layout(num_envs, n_steps, n_groups, width, n_layers, day_z).bytes;
+}
+
+// The handle first (a new export: its name is the first thing a caller learns), then w2a_surrogate_gradient_mlp_gated's
+// checks in its order -- the struct, the schedule, obs and the outputs, the workspace pointer, the inputs and scalars, the
+// handle's own, the workspace's size, the gate (only when one is given: allowed_days = NULL is the ungated call), the
+// stream.
+int w2a_actor_critic_mlp(w2a_env *env, const w2a_mlp_policy *net, const uint32_t *alert_mask, int32_t mask_words,
+                         const float *env_weight, const float *advantage, int32_t advantage_days,
+                         const float *value_target, int32_t value_target_days, const float *old_log_prob,
+                         int32_t old_log_prob_days, double clip, double vf_coef, double entropy_coef, double gamma,
+                         double lambda, int32_t bootstrap, int32_t n_steps, const float *obs, float *grad,
+                         float *surrogate, float *value_loss, int32_t *clipped_days, float *approx_kl, float *entropy,
+                         int32_t *days, float *ret, float *advantage_out, float *value_target_out, float *log_prob_out,
+                         void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                         int32_t allowed_words) {
+  const char *fn = "w2a_actor_critic_mlp";
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if (!net) return fail(W2A_ERR_ARG, "%s: NULL net (the two-row actor-critic network)", fn);
+  W2A_CHECK(check_mlp_policy_struct(fn, net, n_steps, SAMPLE_0_OR_1));
+  if (!alert_mask) return fail(W2A_ERR_ARG, "%s: NULL alert_mask (the schedule to follow)", fn);
+  W2A_CHECK(check_obs(fn, obs));
+  if (!surrogate || !value_loss || !clipped_days || !approx_kl || !entropy || !days)
+    return fail(W2A_ERR_ARG, "%s: NULL surrogate, value_loss, clipped_days, approx_kl, entropy or days", fn);
+  W2A_CHECK(check_workspace_pointer(fn, workspace));
+  const bool epoch = advantage || value_target || old_log_prob;
+  if (epoch) {
+    if (!advantage || !value_target || !old_log_prob)
+      return fail(W2A_ERR_ARG, "%s: advantage, value_target and old_log_prob come together (an epoch) or not at all", fn);
+    if (advantage_days < n_steps) return fail(W2A_ERR_ARG, "%s: advantage holds fewer call-days than n_steps", fn);
+    if (value_target_days < n_steps) return fail(W2A_ERR_ARG, "%s: value_target holds fewer call-days than n_steps", fn);
+    if (old_log_prob_days < n_steps) return fail(W2A_ERR_ARG, "%s: old_log_prob holds fewer call-days than n_steps", fn);
+    if (advantage_out || value_target_out || log_prob_out || ret)
+      return fail(W2A_ERR_ARG, "%s: advantage_out, value_target_out, log_prob_out and ret are not formed in an epoch", fn);
+    if (gamma != 1.0 || lambda != 1.0 || bootstrap)
+      return fail(W2A_ERR_ARG, "%s: gamma, lambda and bootstrap have no meaning in an epoch", fn);
+    if (!grad) return fail(W2A_ERR_ARG, "%s: NULL grad (only a collect call may leave the gradient out)", fn);
+  } else {
+    if (!advantage_out || !value_target_out || !log_prob_out || !ret)
+      return fail(W2A_ERR_ARG, "%s: NULL advantage_out, value_target_out, log_prob_out or ret (a collect call)", fn);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(W2A_ERR_ARG, "%s: gamma must lie in [0, 1]", fn);
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(W2A_ERR_ARG, "%s: lambda must lie in [0, 1]", fn);
+    if (bootstrap != 0 && bootstrap != 1) return fail(W2A_ERR_ARG, "%s: bootstrap must be 0 or 1", fn);
+  }
+  if (!isfinite(clip) || clip < 0.0) return fail(W2A_ERR_ARG, "%s: clip must be finite and not negative", fn);
+  if (!isfinite(entropy_coef)) return fail(W2A_ERR_ARG, "%s: entropy_coef must be finite", fn);
+  if (!isfinite(vf_coef) || vf_coef < 0.0) return fail(W2A_ERR_ARG, "%s: vf_coef must be finite and not negative", fn);
+  W2A_CHECK(check_handle_common(fn, env, epoch ? FIXES_CHANGE_OBS : FIXES_CHANGE_OBS_AND_REWARD, MASK_SCHEDULE, mask_words));
+  if ((int64_t)net->n_groups * W2A_MLP_HEADS_STRIDE((int64_t)net->width, net->n_layers) >= (1ll << 31))
+    return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
+  size_t day_z;
+  const PgmLayout L = ac_layout(env->n, n_steps, net->n_groups, net->width, net->n_layers, day_z);
+  if (workspace_bytes < L.bytes)
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_actor_critic_mlp_workspace_bytes", fn);
+  if (allowed_days) W2A_CHECK(check_gate(fn, env, allowed_days, allowed_words));
+  W2A_CHECK(refuse_while_capturing(fn, stream));
+  AcMlpArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  W2A_CHECK(fill_mlp(fn, env, net, n_steps, obs, allowed_days, allowed_days ? allowed_words : 0, xa.g.m));
+  xa.g.m.stride = (int32_t)W2A_MLP_HEADS_STRIDE((int64_t)net->width, net->n_layers);  // below 2^31: checked above
+  xa.g.m.r.pol.require_budget = net->require_budget;
+  xa.g.m.r.order = mlp_own_order(net);
+  bind_pgm_workspace(xa.g, L, workspace, grad);
+  fill_surrogate(xa.ac.sg, alert_mask, mask_words, env_weight, advantage, old_log_prob, clip, entropy_coef, log_prob_out,
+                 surrogate, clipped_days, approx_kl, entropy, days);
+  xa.ac.value_target = value_target;
+  xa.ac.vf_coef = vf_coef;
+  xa.ac.gamma = gamma;
+  xa.ac.gl = gamma * lambda;
+  xa.ac.bootstrap = bootstrap;
+  xa.ac.advantage_out = advantage_out;
+  xa.ac.value_target_out = value_target_out;
+  xa.ac.value_loss = value_loss;
+  xa.ac.ret = ret;
+  xa.ac.day_z = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + day_z);
+  hipStream_t s = (hipStream_t)stream;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  W2A_CHECK(clear_day_rows(env, n_steps, advantage_out, s));
+  W2A_CHECK(clear_day_rows(env, n_steps, value_target_out, s));
+  W2A_CHECK(clear_day_rows(env, n_steps, log_prob_out, s));
+  const unsigned g64 = grid64(env);
+  dispatch_mlp_shape(net->width, net->n_layers,
+                     [&](auto W, auto L_) { launch_ac<W(), L_()>(xa, epoch, grad != nullptr, g64, s); });
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;

@@ -7,9 +7,20 @@
 // from, and dw_out / db_out are accumulated per head (a head's env-days feed 0 into the other head's chain). Nothing new
 // goes through LDS: the bank argument and the fragment layouts hold as they are. Every HEADS == 2 branch is a
 // compile-time constant, so HEADS = 1 compiles to the statements the kernel had before the parameter existed.
+// PGM_PASS2_BOTH (defined by w2a_actor_critic.hip.h for k_ac_pass2, with HEADS = 2): BOTH output rows receive a
+// coefficient on every env-day. The day record is read as the two coefficients themselves, day = (c_pi, c_v): no
+// total - prefix, ga.total is not read, and the alert byte is only the alert issued. dh_last = (c_pi w_out0 + c_v w_out1)
+// act', dw_out0 += c_pi h, dw_out1 += c_v h, db_out0 += c_pi, db_out1 += c_v. Every BOTH branch is a compile-time
+// constant as well: without the macro the kernels compile from the statements they had before it existed.
 template <int WIDTH, int LAYERS>
 __global__ __launch_bounds__(64, 1) void PGM_PASS2_KERNEL(const MlpGradArgs ga) {
   constexpr int HEADS = PGM_PASS2_HEADS;
+#ifdef PGM_PASS2_BOTH
+  constexpr bool BOTH = true;
+  static_assert(HEADS == 2, "PGM_PASS2_BOTH needs the two-head block");
+#else
+  constexpr bool BOTH = false;
+#endif
   constexpr int NT = WIDTH / 16;           // hidden tiles
   constexpr int NB = 4 / NT;               // blocks of 16 envs per pass
   constexpr int ND = WIDTH == 16 ? 2 : 1;  // copies of every weight-gradient tile (even / odd k-steps)
@@ -43,7 +54,7 @@ __global__ __launch_bounds__(64, 1) void PGM_PASS2_KERNEL(const MlpGradArgs ga) 
     const int32_t budget = (int32_t)hot.w;
     const uint32_t obs0 = e * (uint32_t)ma.n_obs;
     const int32_t g = valid ? pgm_group(ma, e) : -1;
-    const double total = valid ? ga.total[slot] : 0.0;
+    const double total = (!BOTH && valid) ? ga.total[slot] : 0.0;
     const int32_t nv_all = valid ? ga.n_valid[slot] : 0;
     uint64_t todo = __ballot(valid);
     while (todo) {
@@ -99,11 +110,12 @@ __global__ __launch_bounds__(64, 1) void PGM_PASS2_KERNEL(const MlpGradArgs ga) 
 #pragma unroll
         for (int k = 0; k < 32; ++k) xv[k] = 0.0f;
         float c = 0.0f;
+        float cv = 0.0f;  // BOTH: the second output row's coefficient
         int head = 0;  // HEADS = 2: the output row of the action taken on call-day s
         if (live) {
           const size_t d = (size_t)s * n + slot;
           const float2 da = ga.day[d];
-          if (HEADS == 2) head = ga.day_alert[d];
+          if (HEADS == 2 && !BOTH) head = ga.day_alert[d];
           if (s == 0) {  // the row the env holds on entry
 #pragma unroll
             for (int k = 0; k < RO64_SLOTS; ++k)
@@ -128,10 +140,18 @@ __global__ __launch_bounds__(64, 1) void PGM_PASS2_KERNEL(const MlpGradArgs ga) 
             streak = actual ? streak + 1 : 0;  // call-day s - 1 was not terminal: the env stepped again on call-day s
             t = t + 1;
           }
-          c = (float)((double)da.x * (total - prefix));  // delta_s Q_s
-          prefix += (double)da.y;
+          if (BOTH) {
+            c = da.x;
+            cv = da.y;
+          } else {
+            c = (float)((double)da.x * (total - prefix));  // delta_s Q_s
+            prefix += (double)da.y;
+          }
         }
-        if (HEADS == 2) {
+        if (BOTH) {
+          dbo += c;
+          dbo_b += cv;
+        } else if (HEADS == 2) {
           dbo += head ? 0.0f : c;
           dbo_b += head ? c : 0.0f;
         } else {
@@ -203,24 +223,31 @@ __global__ __launch_bounds__(64, 1) void PGM_PASS2_KERNEL(const MlpGradArgs ga) 
 #pragma unroll
           for (int j = 0; j < NB; ++j) {
             const float cb = __shfl(c, 16 * (b0 + j) + lo);
-            const int hb = HEADS == 2 ? __shfl(head, 16 * (b0 + j) + lo) : 0;
+            const float cvb = BOTH ? __shfl(cv, 16 * (b0 + j) + lo) : 0.0f;
+            const int hb = (HEADS == 2 && !BOTH) ? __shfl(head, 16 * (b0 + j) + lo) : 0;
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt) {
               mlp_f4 wv = *reinterpret_cast<const mlp_f4 *>(wo + 16 * tt + 4 * hi);
+              mlp_f4 wv_2 = wv;  // BOTH: the second output row
               if (HEADS == 2) {
                 const mlp_f4 wv_b = *reinterpret_cast<const mlp_f4 *>(wo + WIDTH + 16 * tt + 4 * hi);
-                wv = hb ? wv_b : wv;
+                if (BOTH) wv_2 = wv_b;
+                else wv = hb ? wv_b : wv;
               }
 #pragma unroll
               for (int i = 0; i < 4; ++i) {
                 const float hl = LAYERS == 2 ? h2[j][tt][i] : h1[j][tt][i];
-                if (HEADS == 2) {
+                if (BOTH) {
+                  dwo[tt][i] = fmaf(cb, hl, dwo[tt][i]);
+                  dwo_b[tt][i] = fmaf(cvb, hl, dwo_b[tt][i]);
+                } else if (HEADS == 2) {
                   dwo[tt][i] = fmaf(hb ? 0.0f : cb, hl, dwo[tt][i]);
                   dwo_b[tt][i] = fmaf(hb ? cb : 0.0f, hl, dwo_b[tt][i]);
                 } else {
                   dwo[tt][i] = fmaf(cb, hl, dwo[tt][i]);
                 }
-                const float dv = cb * wv[i] * pgm_dact(hl, activation);
+                const float dv = BOTH ? fmaf(cvb, wv_2[i], cb * wv[i]) * pgm_dact(hl, activation)
+                                      : cb * wv[i] * pgm_dact(hl, activation);
                 if (LAYERS == 2) h2[j][tt][i] = dv;  // h2 now holds dh2
                 else dh1[j][tt][i] = dv;
               }

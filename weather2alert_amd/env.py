@@ -1858,6 +1858,110 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 out["group_loss"] = _policy.group_mean(wl, pol.group, pol.n_groups)
         return out
 
+    # ------------------------------------------------------------------ shared-trunk actor-critic (PPO)
+    def actor_critic_gradient(self, net: dict, alert_days, advantage=None, value_target=None, old_log_prob=None,
+                              clip: float = 0.2, vf_coef: float = 0.5, entropy_coef: float = 0.0, gamma: float = 1.0,
+                              gae_lambda: float = 1.0, bootstrap: bool = False, env_weight=None,
+                              n_steps: int | None = None, gradient: bool = True) -> dict:
+        """PPO for ONE network with a shared trunk: the ascent direction of the clipped surrogate, the entropy bonus and
+        the value loss together, along a GIVEN alert schedule, with one row rebuild, one forward and one backward pass
+        per env-day where value_gradient() plus surrogate_gradient() on two networks take two of each.
+          net         a kind="mlp" dict as surrogate_gradient() takes it (hidden shapes, tanh or ReLU, "group",
+                      "require_budget", "allowed_days") whose output layer has exactly TWO rows: row 0 is the policy
+                      logit z, row 1 the state value V. A linear kind, another number of rows, "lookahead": ValueError.
+          alert_days, env_weight, n_steps   as surrogate_gradient()
+        Every env is forced along its own schedule exactly as in surrogate_gradient() / value_gradient(): the same rows
+        o_s, the same scored days (a day "require_budget" forces or "allowed_days" closes is attempted as 0 and has no
+        policy score; the value term still applies there). Per group the call returns the ASCENT direction of
+          J_g = (1/n_g) sum_e w_e sum_s [ L^clip_s + entropy_coef H_s - (vf_coef / 2) (T_s - V_s)^2 ]
+        with the per-day coefficients c_pi,s = surrogate_gradient()'s on dz_s/dtheta and c_v,s = w_e vf_coef (T_s - V_s)
+        on dV_s/dtheta. The value loss carries the factor 1/2: stable-baselines3's vf_coef multiplies mean (T - V)^2, whose
+        gradient is twice this one's, so SB3's vf_coef = 0.5 is vf_coef = 1.0 here.
+        COLLECT (advantage, value_target and old_log_prob all None): the rewards are those step() pays; with V the net's
+        own row 1, delta_s = r_s + gamma Vn_s - V_s, A_s = delta_s + gamma gae_lambda A_{s+1} (GAE(lambda); Vn_s and
+        bootstrap as in value_gradient()), T_s = A_s + V_s; rho = 1, nothing is clipped, T_s - V_s = A_s. Always returns
+          "advantage", "value_target", "log_prob"  f32 [S, N] by call-day and ENV ID (0 where the env does not step / is
+                      not scored): bit for bit value_gradient()'s and surrogate_gradient(log_prob=True)'s for the two
+                      one-output nets made of the trunk and row 1 / row 0
+          "return"    f32 [N]  sum_s r_s (undiscounted)
+        gradient=False skips the second pass and returns no "gradient" and no "group_objective" (the first pass is the
+        cheap part). reward_mode="posterior_mean": ValueError, as value_gradient().
+        EPOCH (all three given, float [S >= n_steps, N]; one or two: ValueError): advantages and targets are fixed (the
+        caller may normalise the advantages in between), the clipped ratio is formed in the kernel from old_log_prob, no
+        reward is formed -- reward_mode="posterior_mean" is accepted, as value_gradient(target=). gamma, gae_lambda and
+        bootstrap must stay at their defaults.
+        Both modes return
+          "gradient"         {"layers": [(dW, db), ...]} in the net's own shapes, the output layer with its two rows
+                             (policy.mlp_heads_grad_to_module writes it into a module); NaN for a group without envs
+          "surrogate", "entropy", "approx_kl", "clipped_days", "days"   per env, as surrogate_gradient()
+          "value_loss"       f32 [N]  sum_s 1/2 (T_s - V_s)^2, unweighted by vf_coef
+          "group_objective"  f32 [G]  mean over the group's envs of w_e (surrogate + entropy_coef entropy - vf_coef value_loss)
+        No side effects: the state, the tables, the observation buffer and the RNG are only read. No floating-point
+        atomics: two identical calls give identical bits. Needs the observation buffer current (RuntimeError as
+        surrogate_gradient()) and faithful observations. w2a_actor_critic_mlp (include/w2a.h)."""
+        who = "actor_critic_gradient()"
+        _refuse_lookahead(net, who)
+        ct, n, dev = self.ct, self.num_envs, self.device
+        pol = _policy.check_actor_critic_net(net, ct.n_obs, n, ct.obs_slot, dev, who)
+        mask, w, steps = _policy.check_imitation_args("mlp", alert_days, env_weight, n_steps, n, ct.T, dev, self.fixes,
+                                                      who=who)
+        adv, vt, old, clip, vf_coef, beta, gamma, lam = _policy.check_actor_critic_args(
+            advantage, value_target, old_log_prob, clip, vf_coef, entropy_coef, gamma, gae_lambda, bootstrap, gradient,
+            min(steps, 2**31 - 1), n, dev, who)
+        epoch = adv is not None
+        if not epoch and self.reward_mode != "sampled":
+            raise ValueError(f"{who} needs reward_mode='sampled' to collect (rewards enter; an epoch on given "
+                             "advantages and targets does not)")
+        gate = _policy.check_allowed_days(net, n, ct.T, dev, who)
+        if self._needs_reset:
+            raise RuntimeError("call reset() before actor_critic_gradient()")
+        if not self._obs_current:
+            raise RuntimeError("actor_critic_gradient() reads the observation buffer, which does not hold the agents' "
+                               "current rows (write_obs=False, a built-in rollout or load_state_dict since the last "
+                               "step()/reset()): call step() or reset() first")
+        words = mask.shape[1]
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"surrogate": torch.empty(n, **f32), "value_loss": torch.empty(n, **f32),
+               "clipped_days": torch.empty(n, dtype=torch.int32, device=dev), "approx_kl": torch.empty(n, **f32),
+               "entropy": torch.empty(n, **f32), "days": torch.empty(n, dtype=torch.int32, device=dev)}
+        if not epoch:
+            out["return"] = torch.empty(n, **f32)
+            for key in ("advantage", "value_target", "log_prob"):
+                out[key] = torch.empty((steps, n), **f32)  # zero-filled by the library
+        ptr = lambda key: out[key].data_ptr() if key in out else None  # noqa: E731
+        rows = lambda t: (None, 0) if t is None else (t.data_ptr(), int(min(t.shape[0], 2**31 - 1)))  # noqa: E731
+        with torch.cuda.device(dev):
+            mp = _ffi.MlpPolicy()
+            mp.params = pol.params.data_ptr()
+            mp.group = None if pol.group is None else pol.group.data_ptr()
+            mp.order = None if pol.group is None else pol.order.data_ptr()  # group-major: check_actor_critic_net
+            mp.n_groups, mp.n_layers, mp.width = pol.n_groups, pol.n_layers, pol.width
+            mp.activation = _ffi.MLP_ACTIVATIONS[pol.activation]
+            mp.sample, mp.require_budget, mp.seed = 0, int(pol.require_budget), 0
+            blocks = None
+            if gradient:
+                blocks = torch.empty((pol.n_groups, _policy.mlp_heads_stride(pol.width, pol.n_layers)), **f32)
+            ws = torch.empty(self._lib.w2a_actor_critic_mlp_workspace_bytes(n, steps, pol.n_groups, pol.width,
+                                                                            pol.n_layers), dtype=torch.uint8, device=dev)
+            _ffi.check(self._lib.w2a_actor_critic_mlp(
+                self._h, C.byref(mp), mask.data_ptr(), words, None if w is None else w.data_ptr(), *rows(adv), *rows(vt),
+                *rows(old), clip, vf_coef, beta, gamma, lam, int(bootstrap), steps, self._obs.data_ptr(),
+                None if blocks is None else blocks.data_ptr(), ptr("surrogate"), ptr("value_loss"), ptr("clipped_days"),
+                ptr("approx_kl"), ptr("entropy"), ptr("days"), ptr("return"), ptr("advantage"), ptr("value_target"),
+                ptr("log_prob"), ws.data_ptr(), ws.numel(), self._stream(),
+                None if gate is None else gate.data_ptr(), 0 if gate is None else int(gate.shape[1])),
+                "w2a_actor_critic_mlp")
+            if gradient:
+                out["gradient"] = {"layers": _policy.unpack_mlp_heads_grad(blocks, ct.obs_slot, ct.n_obs, pol.hidden)}
+                obj = out["surrogate"].double() + beta * out["entropy"].double() - vf_coef * out["value_loss"].double()
+                if w is not None:
+                    obj = w.double() * obj
+                if pol.group is None:  # one group: the fp64 mean, rounded once
+                    out["group_objective"] = obj.mean().to(torch.float32).reshape(1)
+                else:
+                    out["group_objective"] = _policy.group_mean(obj, pol.group, pol.n_groups)
+        return out
+
     # ------------------------------------------------------------------ hindsight optimum
     def hindsight_optimum(self, start_state: dict | None = None, n_steps: int | None = None,
                           allowed_days=None) -> dict:

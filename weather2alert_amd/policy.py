@@ -710,6 +710,73 @@ def check_q_args(gamma, double, loss, huber_delta, bootstrap, td_error, td_targe
     return float(gamma), float(huber_delta)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Shared-trunk actor-critic: actor_critic_gradient() (csrc/w2a_actor_critic.hip.h). Row 0 of the output layer is the
+# policy logit, row 1 the state value; the block is the two-head layout above.
+# ----------------------------------------------------------------------------------------------------------------------
+def check_actor_critic_net(net, n_obs: int, num_envs: int, obs_slot, device, who: str = "actor_critic_gradient()"):
+    """The network of ``actor_critic_gradient()``: a kind="mlp" dict as surrogate_gradient() takes it (hidden shapes,
+    activation, "group", "require_budget", "allowed_days") whose output layer has exactly two rows -- ValueError for a
+    linear kind and for another number of output rows. Returns MlpPolicyArgs with `params` in the two-head layout
+    (pack_mlp_heads) and `order` group-major whatever "order" says (the gradient kernels' partial blocks are sized for
+    it, as in surrogate_gradient())."""
+    kind = net.get("kind") if isinstance(net, dict) else None
+    if kind != "mlp":
+        raise ValueError(f"{who} needs kind 'mlp' (one trunk with a policy row and a value row), got {kind!r}")
+    pol = check_mlp_policy(net, n_obs, num_envs, obs_slot, device)
+    if pol.n_out != 2:
+        raise ValueError(f"{who}: the output layer must have exactly 2 rows (row 0 the policy logit, row 1 the state "
+                         f"value), got {pol.n_out}")
+    pol.params = pack_mlp_heads(net["layers"], obs_slot, n_obs)[0].to(device).contiguous()
+    if pol.group is not None and not pol.group_major:
+        pol.order, pol.group_major = group_order(pol.group), True
+    return pol
+
+
+def check_actor_critic_args(advantage, value_target, old_log_prob, clip, vf_coef, entropy_coef, gamma, gae_lambda,
+                            bootstrap, gradient, n_steps: int, num_envs: int, device,
+                            who: str = "actor_critic_gradient()"):
+    """The arguments of ``actor_critic_gradient()`` beyond the net and the schedule, with the checks of
+    check_surrogate_args and check_gae_args: advantage, value_target and old_log_prob all None (collect) or all given
+    (epoch; each through check_day_weight, a log-probability above zero refused); clip and vf_coef finite and not
+    negative, entropy_coef finite; gamma and gae_lambda finite in [0, 1]; bootstrap and gradient plain bools. In an epoch
+    gamma, gae_lambda and bootstrap must stay at their defaults (they have no meaning there, as value_gradient(target=))
+    and gradient must be True. ValueError otherwise. Returns (advantage, value_target, old_log_prob -- contiguous f32
+    [S, num_envs] on `device` or None --, clip, vf_coef, entropy_coef, gamma, gae_lambda)."""
+    given = [x is not None for x in (advantage, value_target, old_log_prob)]
+    if any(given) and not all(given):
+        raise ValueError(f"{who}: advantage, value_target and old_log_prob come together (an epoch on a collect call's "
+                         "outputs) or not at all (collect)")
+    for nm, v in (("clip", clip), ("vf_coef", vf_coef), ("entropy_coef", entropy_coef)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{who}: {nm} must be a finite number, got {v!r}")
+    if clip < 0:
+        raise ValueError(f"{who}: clip must not be negative, got {clip!r}")
+    if vf_coef < 0:
+        raise ValueError(f"{who}: vf_coef must not be negative, got {vf_coef!r}")
+    for nm, v in (("gamma", gamma), ("gae_lambda", gae_lambda)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{who}: {nm} must be a finite number in [0, 1], got {v!r}")
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{who}: {nm} must lie in [0, 1], got {v!r}")
+    for nm, v in (("bootstrap", bootstrap), ("gradient", gradient)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{who}: {nm} must be a bool, got {v!r}")
+    adv = vt = old = None
+    if all(given):
+        if float(gamma) != 1.0 or float(gae_lambda) != 1.0 or bootstrap:
+            raise ValueError(f"{who}: gamma, gae_lambda and bootstrap have no meaning in an epoch (the advantages and "
+                             "targets are given)")
+        if not gradient:
+            raise ValueError(f"{who}: gradient=False is a collect call's option (an epoch forms nothing else)")
+        adv = check_day_weight(advantage, n_steps, num_envs, device, who=who, name="advantage")
+        vt = check_day_weight(value_target, n_steps, num_envs, device, who=who, name="value_target")
+        old = check_day_weight(old_log_prob, n_steps, num_envs, device, who=who, name="old_log_prob")
+        if bool((old > 0).any()):
+            raise ValueError(f"{who}: old_log_prob holds a log-probability above zero")
+    return adv, vt, old, float(clip), float(vf_coef), float(entropy_coef), float(gamma), float(gae_lambda)
+
+
 def check_fisher_args(kind, vector, pol, n_obs: int, obs_slot, device):
     """The ``vector`` of ``fisher_vector_product()``, which has the shape of the "policy_gradient" the gradient calls
     return for the checked policy `pol` (LinearPolicyArgs or MlpPolicyArgs): linear {"weight": [G, n_obs], "bias": [G]},
