@@ -1242,6 +1242,53 @@ int w2a_relabel_imitation_mlp(w2a_env *env, const w2a_mlp_policy *policy, const 
                               float *grad, float *loglik, int32_t *days, void *workspace, size_t workspace_bytes,
                               void *stream, const uint32_t *allowed_days, int32_t allowed_words);
 
+/* The hindsight budget curve (additions to ABI 18, nothing above changes): w2a_hindsight_optimum for EVERY remaining
+ * budget b = 0 .. max_budget at once -- what one more alert would have been worth to each env, and where alerts stop
+ * paying. The reward of a day reads the agent through alert_lag1, the streak and the REMAINING budget only, so with
+ * r = alerts remaining and s = the streak one table
+ *     V_d(r, s) = max( r0 + V_{d+1}(r, 0),  r1 + V_{d+1}(r - 1, s + 1) ),  V_H = 0,  the alert only while r > 0,
+ * is exact for every starting budget, and column b is V_0(b, streak): the optimum over H = min(n_steps, n_days - t)
+ * days from the env's start day, streak and draw HAD ITS REMAINING BUDGET AT THE START BEEN b -- w2a_hindsight_optimum
+ * of the twin whose budget is used + b. The env's own budget and used are not read; budget - used selects the env's
+ * own column when it is <= max_budget. (max_budget + 1)(max_budget + 2) states per day.
+ *   start, n_steps  as w2a_hindsight_optimum
+ *   max_budget      0 .. 1023, the same for every env of the call
+ *   ret_out         device f32 [num_envs][max_budget + 1]: the return of budget b's schedule. NOT monotone in b in
+ *                   general: the remaining budget enters the reward of days without an alert too
+ *   alerts_out      device i32 [num_envs][max_budget + 1]: alerts in that schedule (<= b)
+ *   alert_masks     NULL (mask_words is then not read), or device u32 [num_envs][max_budget + 1][mask_words]: the
+ *                   schedules, in w2a_hindsight_optimum's format; mask_words * 32 >= T
+ *   workspace       device memory of workspace_bytes >= w2a_hindsight_curve_workspace_bytes(env, n_steps, max_budget,
+ *                   1) bytes, 256-B aligned: 256 B, and a pool only if 32 B per day + 16 B per state + 8 B per day and
+ *                   64 states exceed 64 KiB of LDS (max_budget above 40 at 153 days); `big_envs` sizes the pool for that
+ *                   many envs per launch (speed only)
+ *   allowed_days, allowed_words  (w2a_hindsight_curve_gated) the gate of w2a_hindsight_optimum_gated: every column is
+ *                   the best schedule UNDER the restriction
+ * Envs finished on entry (or with t >= n_days) get rows of 0, 0 alerts and empty bitmaps; a start state outside the
+ * tables gives a row of NaN, 0 alerts and empty bitmaps.
+ * Numerics contract: the backward sweep is w2a_hindsight_optimum's, statement for statement, on the same reward bits
+ * (rem = r without an alert, r - 1 with one: the integers that call passes for the twin), and each budget's
+ * schedule is backtracked and its rewards re-added in f32 in day order as there: ret_out[e][b], alerts_out[e][b] and
+ * alert_masks[e][b] are BIT-IDENTICAL to w2a_hindsight_optimum's outputs for the twin with budget = used + b (under
+ * the same gate), and so to w2a_posterior_returns of that schedule. No atomics: identical calls give identical bits.
+ * Synchronises `stream` once (the slot-27 flag comes to the host before anything is written), then queues its launches
+ * and returns without waiting for them: max_budget is uniform, so nothing is binned on the host. Reads the tables and
+ * the caller's arrays only: the handle's state and bookkeeping are untouched.
+ * Refuses where w2a_hindsight_optimum refuses, in its order and before any output is written: W2A_ERR_ARG for NULL
+ * pointers, n_steps <= 0, mask_words <= 0 with alert_masks, max_budget outside 0..1023 (checked on the host, before the
+ * handle), mask_words * 32 < T with alert_masks, a handle with corrected-semantics flags, a workspace smaller than
+ * w2a_hindsight_curve_workspace_bytes(env, n_steps, max_budget, 1), tables where some coefficient row has a nonzero
+ * slot-27 term; W2A_ERR_STATE while `stream` is recording a hipGraph. w2a_hindsight_curve_workspace_bytes returns 0 for
+ * a NULL handle and for arguments the entry refuses. */
+size_t w2a_hindsight_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget, int32_t big_envs);
+int w2a_hindsight_curve(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget, float *ret_out,
+                        int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int w2a_hindsight_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                              float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words,
+                              void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                              int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

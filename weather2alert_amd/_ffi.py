@@ -46,6 +46,7 @@ SYMBOLS = [
     "w2a_lookahead_rollout_mlp_gated", "w2a_lookahead_policy_gradient_linear",
     "w2a_lookahead_imitation_gradient_linear",
     "w2a_hindsight_along", "w2a_relabel_imitation_linear", "w2a_relabel_imitation_mlp",
+    "w2a_hindsight_curve_workspace_bytes", "w2a_hindsight_curve", "w2a_hindsight_curve_gated",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -330,6 +331,14 @@ def load(build_if_missing: bool = True):
     lib.w2a_relabel_imitation_mlp.restype = C.c_int
     lib.w2a_relabel_imitation_mlp.argtypes = [vp, C.POINTER(MlpPolicy), vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp,
                                               vp, C.c_size_t, vp] + gate
+    # the hindsight budget curve: start, n_steps, max_budget, returns, alerts, the nullable schedules and their words, the
+    # workspace and the stream
+    lib.w2a_hindsight_curve_workspace_bytes.restype = C.c_size_t
+    lib.w2a_hindsight_curve_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    lib.w2a_hindsight_curve.restype = C.c_int
+    lib.w2a_hindsight_curve.argtypes = [vp, C.POINTER(StateView), i32, i32, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    lib.w2a_hindsight_curve_gated.restype = C.c_int
+    lib.w2a_hindsight_curve_gated.argtypes = lib.w2a_hindsight_curve.argtypes + gate
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

@@ -65,6 +65,7 @@
 #include "w2a_qlearn.hip.h"
 #include "w2a_actor_critic.hip.h"
 #include "w2a_hindsight.hip.h"
+#include "w2a_hindsight_curve.hip.h"
 #include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1055,6 +1056,113 @@ int w2a_hindsight_along(w2a_env *env, const w2a_state_view *start, int32_t n_ste
   along.sched = alert_mask; along.gain = gain_out; along.value = value_out; along.loss = loss_out;
   return hindsight_optimum("w2a_hindsight_along", env, start, n_steps, regret_out, expert_mask, mask_words, nullptr, workspace,
                            workspace_bytes, stream, allowed_days != nullptr, allowed_days, allowed_words, &along);
+}
+
+// workspace of w2a_hindsight_curve: the slot-27 flag, then the pool when the DP of max_budget does not fit in LDS
+// (big_envs envs per launch)
+static size_t hc_fixed_bytes() { return 256; }
+
+size_t w2a_hindsight_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget, int32_t big_envs) {
+  if (!env || n_steps <= 0 || big_envs <= 0 || max_budget < 0 || max_budget > HC_MAX_BUDGET) return 0;
+  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
+  const bool pool = hs_day_bytes(hb) + hc_dp_bytes((uint32_t)max_budget, hb) > HS_LDS_CAP;
+  return hc_fixed_bytes() + (pool ? (size_t)big_envs * align256(hc_dp_bytes((uint32_t)max_budget, hb)) : 0);
+}
+
+static int hindsight_curve(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                           float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words, void *workspace,
+                           size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words) {
+  // w2a_hindsight_optimum's refusals in its order (alert_masks may be NULL: mask_words is then not read), max_budget
+  // among what is checked without the handle
+  if (!start || !ret_out || !alerts_out || !workspace) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
+  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
+      !start->year_i || !start->coef_col || !start->sample || !start->finished)
+    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
+                             "year_i, coef_col, sample and finished are read)", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (alert_masks && mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
+  if (max_budget < 0 || max_budget > HC_MAX_BUDGET)
+    return fail(W2A_ERR_ARG, "%s: max_budget must lie in 0..1023", fn);
+  static_assert(HC_MAX_BUDGET == 1023, "the message above and include/w2a.h state the cap");
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if (alert_masks && (int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "%s: alert_masks needs ceil(T/32) words per env and budget", fn);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
+                             "depends on attempts and on the 14-day window)", fn);
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t n = env->n;
+  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T), B = (uint32_t)max_budget;
+  if (n > 0x7FFFFFFFll) return fail(W2A_ERR_ARG, "%s: num_envs too large", fn);
+  const size_t need = hs_day_bytes(hb) + hc_dp_bytes(B, hb), stride = align256(hc_dp_bytes(B, hb));
+  const bool in_lds = need <= HS_LDS_CAP;
+  if (workspace_bytes < hc_fixed_bytes() + (in_lds ? 0 : stride))
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_curve_workspace_bytes(env, n_steps, "
+                             "max_budget, 1)", fn);
+  char *ws = reinterpret_cast<char *>(workspace);
+  {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
+    int32_t *flag = reinterpret_cast<int32_t *>(ws);
+    const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
+    HIP_TRY(hipGetLastError());
+    int32_t used27 = 1;
+    HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (used27)
+      return fail(W2A_ERR_ARG, "%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
+                               "agent): the (remaining, streak) DP would not be exact", fn);
+  }
+  if (n == 0) return W2A_OK;
+  HcArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  HsArgs &a = ca.h;
+  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.n = n;
+  a.ret = ret_out; a.alerts = alerts_out; a.mask = alert_masks; a.mask_words = alert_masks ? mask_words : 0;
+  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
+  ca.B = max_budget;
+  if (in_lds) {
+    if (gated)
+      hipLaunchKernelGGL((k_hs_curve<false, true>), dim3((unsigned)n), dim3(HS_BLOCK), need, s, ca, 0u, nullptr, (size_t)0);
+    else
+      hipLaunchKernelGGL((k_hs_curve<false, false>), dim3((unsigned)n), dim3(HS_BLOCK), need, s, ca, 0u, nullptr, (size_t)0);
+    HIP_TRY(hipGetLastError());
+    return W2A_OK;
+  }
+  char *pool = ws + hc_fixed_bytes();
+  const size_t fit = (workspace_bytes - hc_fixed_bytes()) / stride;
+  const uint32_t per = fit < (size_t)n ? (uint32_t)fit : (uint32_t)n;
+  for (uint32_t i = 0; i < (uint32_t)n; i += per) {  // launches on one stream: each finds the pool free
+    const uint32_t cnt = min(per, (uint32_t)n - i);
+    if (gated)
+      hipLaunchKernelGGL((k_hs_curve<true, true>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, ca, i, pool, stride);
+    else
+      hipLaunchKernelGGL((k_hs_curve<true, false>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, ca, i, pool, stride);
+    HIP_TRY(hipGetLastError());
+  }
+  return W2A_OK;
+}
+
+int w2a_hindsight_curve(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget, float *ret_out,
+                        int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+  return hindsight_curve("w2a_hindsight_curve", env, start, n_steps, max_budget, ret_out, alerts_out, alert_masks,
+                         mask_words, workspace, workspace_bytes, stream, false, nullptr, 0);
+}
+
+int w2a_hindsight_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                              float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words,
+                              void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                              int32_t allowed_words) {
+  return hindsight_curve("w2a_hindsight_curve_gated", env, start, n_steps, max_budget, ret_out, alerts_out, alert_masks,
+                         mask_words, workspace, workspace_bytes, stream, true, allowed_days, allowed_words);
 }
 
 int w2a_alert_gate(w2a_env *env, int32_t obs_col, float threshold, const float *thresholds, int32_t n_steps,

@@ -2087,6 +2087,80 @@ class HeatAlertVecEnv(_VectorEnvBase):
             out["loss"] = los
         return out
 
+    def hindsight_budget_curve(self, max_budget: int, start_state: dict | None = None, n_steps: int | None = None,
+                               allowed_days=None, schedules: bool = False, packed: bool = False) -> dict:
+        """hindsight_optimum() for EVERY remaining budget 0 .. max_budget in one sweep: what one more alert would have
+        been worth to each env, and where alerts stop paying -- the return-versus-budget curves that splitting a fixed
+        number of alerts over counties needs (stats.budget_curve_by_group, stats.allocate_budget), and the regret of a
+        rollout under a sampled budget without a second DP. Column b of env e is the optimum over the env's stretch
+        (start_state, n_steps and allowed_days as hindsight_optimum()) from its start day, streak and draw HAD ITS
+        REMAINING BUDGET AT THE START BEEN b: hindsight_optimum() of the twin with budget = used + b, bit for bit
+        (return, alerts and schedule). The env's own budget is not read. Returns, with B = max_budget,
+            "return":     f32 [N, B + 1]  NOT monotone in b in general: the remaining budget enters the reward of
+                                          days without an alert too
+            "alerts":     i32 [N, B + 1]  alerts in budget b's schedule (<= b)
+            "own_budget": i32 [N]         budget - used of start_state: the env's own column where it is in 0 .. B
+            "alert_days": (schedules=True) bool [N, B + 1, T] by day of the episode, or with packed=True the kernel's
+                                          int32 [N, B + 1, ceil(T / 32)] words
+        Envs finished in start_state give rows of 0 and empty schedules; a start outside the tables gives a row of NaN.
+        One exact DP over (alerts remaining, streak) per env serves all budgets (w2a_hindsight_curve, include/w2a.h),
+        about twice the states of one hindsight_optimum() at budget B and no pruning by day. ValueError for a max_budget
+        that is not an int in 0 .. 1023, for schedules of more than 4 GiB (packed words plus, unless packed=True, the
+        bool array: ask for fewer envs or budgets per call), and for what hindsight_optimum() refuses. Reads
+        start_state and the tables only: the env's state, observation buffer and bookkeeping are untouched."""
+        who = "hindsight_budget_curve()"
+        self._check_hindsight(who)
+        if isinstance(max_budget, bool) or not isinstance(max_budget, (int, np.integer)) or \
+                not 0 <= max_budget <= _CURVE_MAX_BUDGET:
+            raise ValueError(f"{who}: max_budget must be an int in 0..{_CURVE_MAX_BUDGET}, got {max_budget!r}")
+        ct, n, dev = self.ct, self.num_envs, self.device
+        B = int(max_budget)
+        words = (ct.T + 31) // 32
+        if schedules:
+            need = n * (B + 1) * (4 * words + (0 if packed else ct.T))
+            if need > _CURVE_SCHEDULE_BYTES:
+                raise ValueError(f"{who}: the schedules of {n} envs x {B + 1} budgets need {need} bytes, more than "
+                                 f"{_CURVE_SCHEDULE_BYTES}; ask for fewer envs or budgets per call"
+                                 + ("" if packed else ", or packed=True"))
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        if start_state is None:
+            st = self._state_packed(_HS_FIELDS)[1]
+        else:
+            st = {}
+            for k in _HS_FIELDS:
+                if k not in start_state:
+                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
+                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
+                if st[k].shape != (n,):
+                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
+        if n_steps is not None and (isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer))):
+            raise ValueError(f"{who}: n_steps must be an int, got {n_steps!r}")
+        steps = int(n_steps) if n_steps is not None else ct.T
+        if steps <= 0:
+            raise ValueError(f"{who}: n_steps must be positive")
+        ret = torch.empty((n, B + 1), dtype=torch.float32, device=dev)
+        alerts = torch.empty((n, B + 1), dtype=torch.int32, device=dev)
+        masks = torch.empty((n, B + 1, words), dtype=torch.int32, device=dev) if schedules else None
+        with torch.cuda.device(dev):
+            ws_bytes = self._lib.w2a_hindsight_curve_workspace_bytes(self._h, steps, B, _HS_BIG_ENVS)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            v = _ffi.StateView()
+            for k in _HS_FIELDS:
+                setattr(v, k, st[k].data_ptr())
+            args = (self._h, C.byref(v), steps, B, ret.data_ptr(), alerts.data_ptr(),
+                    None if masks is None else masks.data_ptr(), words, ws.data_ptr(), ws_bytes, self._stream())
+            if gate is None:
+                _ffi.check(self._lib.w2a_hindsight_curve(*args), "w2a_hindsight_curve")
+            else:
+                _ffi.check(self._lib.w2a_hindsight_curve_gated(*args, gate.data_ptr(), int(gate.shape[1])),
+                           "w2a_hindsight_curve_gated")
+        self._keep_curve = (st, gate, ws)  # the launches are asynchronous
+        out = {"return": ret, "alerts": alerts, "own_budget": st["budget"] - st["used"]}
+        if schedules:
+            out["alert_days"] = masks if packed else \
+                _policy.unpack_alert_days(masks.view(n * (B + 1), words), ct.T).view(n, B + 1, ct.T)
+        return out
+
     def _check_hindsight(self, who: str):
         if self.fixes - {"budget"}:
             raise ValueError(f"{who} needs faithful semantics; fixes {sorted(self.fixes - {'budget'})} make the reward "
@@ -2261,6 +2335,9 @@ _PR_FIELDS = ("t", "used", "streak", "hist14", "budget", "n_days", "county_w", "
 # the start-state fields w2a_hindsight_optimum reads, and how many envs beyond the LDS budget one launch serves
 _HS_FIELDS = ("t", "used", "streak", "budget", "n_days", "county_w", "year_i", "coef_col", "sample", "finished")
 _HS_BIG_ENVS = 64
+# hindsight_budget_curve(): the largest max_budget w2a_hindsight_curve takes, and the bytes of schedules one call returns
+_CURVE_MAX_BUDGET = 1023
+_CURVE_SCHEDULE_BYTES = 4 << 30
 
 
 def __getattr__(name):  # weather2alert_amd.env.HeatAlertEnv: the drop-in lives in dropin.py (it builds on this module)

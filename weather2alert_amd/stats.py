@@ -182,3 +182,79 @@ def prob_better(Ra, Rb) -> torch.Tensor:
     if Ra.shape[-1] != Rb.shape[-1]:
         raise ValueError(f"draws differ: {Ra.shape[-1]} and {Rb.shape[-1]}")
     return ((Ra > Rb).to(torch.float64) + 0.5 * (Ra == Rb).to(torch.float64)).mean(-1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# return-versus-budget curves: HeatAlertVecEnv.hindsight_budget_curve
+# ----------------------------------------------------------------------------------------------------------------------
+def budget_curve_by_group(curve, group, n_groups: int) -> dict:
+    """The mean curve of every group (county, year, ...) in fp64: curve [N, B + 1] (hindsight_budget_curve()["return"]),
+    group int [N] in [0, n_groups). Rows that hold a NaN (a start outside the tables) are skipped and counted. Returns
+      "curve"   fp64 [n_groups, B + 1], NaN for a group with no row left
+      "count"   i64 [n_groups] rows averaged, "skipped" i64 [n_groups] rows left out
+    The groups' segments of the rows sorted by group, summed as differences of one fp64 prefix sum (policy.group_mean's
+    way): a fixed summation order, identical inputs give identical bits."""
+    curve = torch.as_tensor(curve)
+    group = torch.as_tensor(group, device=curve.device).to(torch.int64)
+    if curve.dim() != 2 or group.shape != (curve.shape[0],):
+        raise ValueError(f"budget_curve_by_group: curve [N, B + 1] and group [N], got {tuple(curve.shape)} and "
+                         f"{tuple(group.shape)}")
+    if group.numel() and (int(group.min()) < 0 or int(group.max()) >= n_groups):
+        raise ValueError(f"budget_curve_by_group: group ids must lie in [0, {n_groups})")
+    bad = torch.isnan(curve).any(1)
+    vals = torch.where(bad[:, None], torch.zeros_like(curve), curve).to(torch.float64)
+    sg, perm = torch.sort(group, stable=True)
+    zero = torch.zeros((1, curve.shape[1]), dtype=torch.float64, device=curve.device)
+    csum = torch.cat([zero, torch.cumsum(vals[perm], dim=0)])
+    cbad = torch.cat([torch.zeros(1, dtype=torch.int64, device=curve.device), torch.cumsum(bad[perm].to(torch.int64), 0)])
+    ids = torch.arange(n_groups, dtype=torch.int64, device=curve.device)
+    lo, hi = torch.searchsorted(sg, ids, right=False), torch.searchsorted(sg, ids, right=True)
+    skipped = cbad[hi] - cbad[lo]
+    count = hi - lo - skipped
+    mean = (csum[hi] - csum[lo]) / count.to(torch.float64)[:, None]  # 0 / 0 = NaN for an empty group
+    return {"curve": mean, "count": count, "skipped": skipped}
+
+
+def allocate_budget(group_curves, total: int, group_size=None) -> dict:
+    """Split `total` alerts over groups so that the summed curves are largest: the exact multiple-choice-knapsack DP.
+    group_curves [G, B + 1] (budget_curve_by_group()["curve"]): the value of giving group g the budget b. Without
+    group_size, budget b costs group g b alerts and is worth group_curves[g, b]; with group_size int [G] (envs per
+    group, every env of the group getting b) it costs group_size[g] * b and is worth group_size[g] * group_curves[g, b].
+    At most `total` alerts are spent, not exactly: the curves need not be monotone. Ties go to the smaller budget. A
+    group whose curve is all NaN (no envs) gets 0 and counts 0; a curve with some NaN is a ValueError. Returns
+      "budget" i64 [G], "value" float (fp64 sum), "spent" int
+    Host code, fp64, O(G * (B + 1) * total) time and G * (total + 1) bytes-per-choice of memory: meant for counties and
+    per-county totals, not for one group per env."""
+    V = torch.as_tensor(group_curves).detach().to("cpu", torch.float64)
+    if V.dim() != 2 or V.shape[1] < 1:
+        raise ValueError(f"allocate_budget: group_curves must be [G, B + 1], got {tuple(V.shape)}")
+    if isinstance(total, bool) or not isinstance(total, int) or total < 0:
+        raise ValueError(f"allocate_budget: total must be a non-negative int, got {total!r}")
+    G, nb = V.shape
+    size = torch.ones(G, dtype=torch.int64) if group_size is None else \
+        torch.as_tensor(group_size).detach().to("cpu", torch.int64)
+    if size.shape != (G,) or bool((size < 0).any()):
+        raise ValueError(f"allocate_budget: group_size must be {G} non-negative ints")
+    empty = torch.isnan(V).all(1)
+    if bool((torch.isnan(V).any(1) & ~empty).any()):
+        raise ValueError("allocate_budget: a group's curve holds NaN for some budgets only")
+    V = torch.where(empty[:, None], torch.zeros_like(V), V) * size.to(torch.float64)[:, None]
+    best = torch.zeros(total + 1, dtype=torch.float64)  # best[c]: the groups so far, at most c alerts spent
+    choice = torch.zeros((G, total + 1), dtype=torch.int16 if nb <= 32767 else torch.int32)
+    for g in range(G):
+        cur = torch.full((total + 1,), -float("inf"), dtype=torch.float64)
+        for b in range(1 if bool(empty[g]) else nb):
+            cost = int(size[g]) * b
+            if cost > total:
+                break
+            cand = best[: total + 1 - cost] + V[g, b]
+            win = cand > cur[cost:]  # strictly: a tie keeps the smaller budget
+            cur[cost:] = torch.where(win, cand, cur[cost:])
+            choice[g, cost:][win] = b
+        best = cur
+    budget = torch.zeros(G, dtype=torch.int64)
+    c = total
+    for g in range(G - 1, -1, -1):
+        budget[g] = int(choice[g, c])
+        c -= int(size[g]) * int(budget[g])
+    return {"budget": budget, "value": float(best[total]), "spent": total - c}
