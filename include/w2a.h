@@ -1289,6 +1289,44 @@ int w2a_hindsight_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t
                               void *workspace, size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
                               int32_t allowed_words);
 
+/* The hindsight optimum of the posterior mean (additions to ABI 18, nothing above changes): every env's best alert
+ * schedule for a stretch of days, knowing the whole stretch's weather and its remaining budget but NOT its posterior
+ * draw -- the schedule that maximises the return averaged over all n_samples draws of the env's coefficient column.
+ * No policy observes the draw, so this is the bound a policy can reach, an expert whose labels are functions of what a
+ * policy sees, and the yardstick of an env that pays the posterior mean.
+ * The states (j, s), the transitions, the day pruning and the strict comparison are w2a_hindsight_optimum's; only the
+ * reward a state weighs changes. With r_a^(i) the f32 reward an env holding draw i of the column (row coef_col *
+ * n_samples + i of W) pays in that state, bit for bit, the DP weighs
+ *     m_a = ( sum over i = 0 .. n_samples - 1 of (double) r_a^(i) ) / (double) n_samples,
+ * the sum in fp64, sequential in i from 0, by one lane per state (no cross-lane combination, no atomics: identical
+ * calls give identical bits). ret_out is the fp64 sum in day order of the chosen m_a along the backtracked path,
+ * rounded once to f32. With n_samples = 1, alert_mask and alerts_out are bit-identical to w2a_hindsight_optimum's and
+ * ret_out agrees to f32 rounding (that call adds in f32).
+ *   start, n_steps, ret_out, alert_mask, mask_words, alerts_out, stream   as w2a_hindsight_optimum; `sample` is only
+ *               range-checked (a start outside the tables gives NaN), the outputs do not depend on it
+ *   workspace   device memory of workspace_bytes >= w2a_hindsight_posterior_workspace_bytes(num_envs, T, n_samples,
+ *               n_steps, max_remaining, 1) bytes, 256-B aligned: w2a_hindsight_optimum's 8 B per env, and the pool
+ *               from the remaining budget at which 16 B per day + 96 B per draw + 16 B per state + 8 B per day and 64
+ *               states exceed 64 KiB of LDS. That function reads no handle (num_envs, T and n_samples are the
+ *               handle's), is non-decreasing in n_steps and max_remaining, and returns 0 for arguments the entry
+ *               refuses
+ *   allowed_days, allowed_words  (w2a_hindsight_posterior_gated) the gate of w2a_hindsight_optimum_gated
+ * Envs finished on entry, envs without a DP, the binning by U and the split between LDS and the pool are
+ * w2a_hindsight_optimum's (the same plan and scatter kernels). Synchronises `stream` and returns after the work is
+ * done. Reads the tables and the caller's arrays only: the handle's state and bookkeeping are untouched.
+ * Refuses where w2a_hindsight_optimum refuses, in its order and before any output is written, and W2A_ERR_ARG for
+ * tables whose n_samples is too large for the per-draw arrays (16 B per day + 96 B per draw above 64 KiB: more than
+ * 657 draws at 153 days). Sampled and posterior-mean handles alike: the reward mode is not read. */
+size_t w2a_hindsight_posterior_workspace_bytes(int64_t num_envs, int32_t T, int32_t n_samples, int32_t n_steps,
+                                               int32_t max_remaining, int32_t big_envs);
+int w2a_hindsight_posterior(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                            uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int w2a_hindsight_posterior_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                                  uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                                  size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                                  int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ SYMBOLS = [
     "w2a_lookahead_imitation_gradient_linear",
     "w2a_hindsight_along", "w2a_relabel_imitation_linear", "w2a_relabel_imitation_mlp",
     "w2a_hindsight_curve_workspace_bytes", "w2a_hindsight_curve", "w2a_hindsight_curve_gated",
+    "w2a_hindsight_posterior_workspace_bytes", "w2a_hindsight_posterior", "w2a_hindsight_posterior_gated",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -339,6 +340,14 @@ def load(build_if_missing: bool = True):
     lib.w2a_hindsight_curve.argtypes = [vp, C.POINTER(StateView), i32, i32, vp, vp, vp, i32, vp, C.c_size_t, vp]
     lib.w2a_hindsight_curve_gated.restype = C.c_int
     lib.w2a_hindsight_curve_gated.argtypes = lib.w2a_hindsight_curve.argtypes + gate
+    # the hindsight optimum of the posterior mean: w2a_hindsight_optimum's arguments; the workspace size reads no handle
+    # (num_envs, T, n_samples, n_steps, max_remaining, big_envs)
+    lib.w2a_hindsight_posterior_workspace_bytes.restype = C.c_size_t
+    lib.w2a_hindsight_posterior_workspace_bytes.argtypes = [i64, i32, i32, i32, i32, i32]
+    lib.w2a_hindsight_posterior.restype = C.c_int
+    lib.w2a_hindsight_posterior.argtypes = lib.w2a_hindsight_optimum.argtypes
+    lib.w2a_hindsight_posterior_gated.restype = C.c_int
+    lib.w2a_hindsight_posterior_gated.argtypes = lib.w2a_hindsight_optimum.argtypes + gate
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

@@ -66,6 +66,7 @@
 #include "w2a_actor_critic.hip.h"
 #include "w2a_hindsight.hip.h"
 #include "w2a_hindsight_curve.hip.h"
+#include "w2a_hindsight_posterior.hip.h"
 #include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1056,6 +1057,143 @@ int w2a_hindsight_along(w2a_env *env, const w2a_state_view *start, int32_t n_ste
   along.sched = alert_mask; along.gain = gain_out; along.value = value_out; along.loss = loss_out;
   return hindsight_optimum("w2a_hindsight_along", env, start, n_steps, regret_out, expert_mask, mask_words, nullptr, workspace,
                            workspace_bytes, stream, allowed_days != nullptr, allowed_days, allowed_words, &along);
+}
+
+// workspace of w2a_hindsight_posterior: w2a_hindsight_optimum's, the pool from the U at which the per-draw arrays, the
+// day tails and the DP together pass the LDS cap. No handle is read: the caller names num_envs, T and n_samples.
+size_t w2a_hindsight_posterior_workspace_bytes(int64_t num_envs, int32_t T, int32_t n_samples, int32_t n_steps,
+                                               int32_t max_remaining, int32_t big_envs) {
+  if (num_envs <= 0 || T <= 0 || T >= HS_BINS || n_samples <= 0 || n_steps <= 0 || big_envs <= 0) return 0;
+  const uint32_t hb = (uint32_t)min(n_steps, T);
+  const size_t fixed = hs_pm_fixed_bytes(hb, (uint32_t)n_samples);
+  if (fixed > HS_LDS_CAP) return 0;  // the entry refuses these tables
+  const uint32_t u = max_remaining <= 0 ? 0u : min((uint32_t)max_remaining, hb);
+  const bool pool = fixed + hs_dp_bytes(u, hb) > HS_LDS_CAP;
+  return hs_fixed_bytes(num_envs) + (pool ? (size_t)big_envs * align256(hs_dp_bytes(u, hb)) : 0);
+}
+
+static void launch_hs_pm(bool global, bool gated, uint32_t cnt, size_t lds, hipStream_t s, const HsArgs &a,
+                         const uint32_t *list, uint32_t u, char *pool, size_t stride) {
+  const dim3 g(cnt), b(HS_BLOCK);
+  if (global && gated) hipLaunchKernelGGL((k_hs_pm_dp<true, true>), g, b, lds, s, a, list, u, pool, stride);
+  else if (global) hipLaunchKernelGGL((k_hs_pm_dp<true, false>), g, b, lds, s, a, list, u, pool, stride);
+  else if (gated) hipLaunchKernelGGL((k_hs_pm_dp<false, true>), g, b, lds, s, a, list, u, pool, stride);
+  else hipLaunchKernelGGL((k_hs_pm_dp<false, false>), g, b, lds, s, a, list, u, pool, stride);
+}
+
+static int hindsight_posterior(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                               uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                               size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate,
+                               int32_t gate_words) {
+  // w2a_hindsight_optimum's refusals in its order, the LDS room of the per-draw arrays after the semantics flags
+  if (!start || !ret_out || !alert_mask || !alerts_out || !workspace) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
+  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
+      !start->year_i || !start->coef_col || !start->sample || !start->finished)
+    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
+                             "year_i, coef_col, sample and finished are read)", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if ((int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
+                             "depends on attempts and on the 14-day window)", fn);
+  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T), K = (uint32_t)env->tb.n_samples;
+  const size_t fixed = hs_pm_fixed_bytes(hb, K);
+  if (fixed > HS_LDS_CAP)
+    return fail(W2A_ERR_ARG, "%s: the tables' n_samples is too large: 96 bytes per draw and 16 per day of the "
+                             "stretch must fit in 64 KiB of LDS", fn);
+  static_assert(HS_LDS_CAP == 64 * 1024, "the message above and include/w2a.h state the cap");
+  if (gated) {
+    const int grc = check_gate(fn, env, gate, gate_words);
+    if (grc != W2A_OK) return grc;
+  }
+  if (stream_is_capturing((hipStream_t)stream))
+    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
+                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t n = env->n;
+  if (workspace_bytes < hs_fixed_bytes(n))
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_posterior_workspace_bytes(num_envs, T, "
+                             "n_samples, n_steps, 0, 1)", fn);
+  char *ws = reinterpret_cast<char *>(workspace);
+  {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
+    int32_t *flag = reinterpret_cast<int32_t *>(ws);
+    const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
+    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
+    HIP_TRY(hipGetLastError());
+    int32_t used27 = 1;
+    HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (used27)
+      return fail(W2A_ERR_ARG, "%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
+                               "agent): the (alerts, streak) DP would not be exact", fn);
+  }
+  HsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.mask_words = mask_words; a.n = n;
+  a.ret = ret_out; a.mask = alert_mask; a.alerts = alerts_out;
+  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
+  a.u_env = reinterpret_cast<uint32_t *>(ws);
+  a.order = reinterpret_cast<uint32_t *>(ws + align256(4 * (size_t)n));
+  a.hist = reinterpret_cast<uint32_t *>(ws + 2 * align256(4 * (size_t)n));
+  a.cursor = a.hist + HS_BINS;
+  char *pool = ws + hs_fixed_bytes(n);
+  const size_t pool_bytes = workspace_bytes - hs_fixed_bytes(n);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * HS_BINS, s));
+  hipLaunchKernelGGL(k_hs_plan, dim3(grid), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  uint32_t hist[HS_BINS], off[HS_BINS];
+  HIP_TRY(hipMemcpyAsync(hist, a.hist, 4 * (hb + 1), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  uint32_t acc = 0;
+  for (uint32_t u = 0; u <= hb; ++u) { off[u] = acc; acc += hist[u]; }
+  // bins that do not fit in LDS: the pool must hold one env of the largest of them (before any output is written)
+  for (uint32_t u = 0; u <= hb; ++u)
+    if (hist[u] && fixed + hs_dp_bytes(u, hb) > HS_LDS_CAP && pool_bytes < align256(hs_dp_bytes(u, hb)))
+      return fail(W2A_ERR_ARG, "%s: workspace too small for the largest budget in the batch "
+                               "(w2a_hindsight_posterior_workspace_bytes(num_envs, T, n_samples, n_steps, "
+                               "max(budget - used), 1) suffices)", fn);
+  HIP_TRY(hipMemcpyAsync(a.cursor, off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  for (uint32_t u = 0; u <= hb; ++u) {
+    if (!hist[u]) continue;
+    const size_t need = fixed + hs_dp_bytes(u, hb);
+    if (need <= HS_LDS_CAP) {
+      launch_hs_pm(false, gated, hist[u], need, s, a, a.order + off[u], u, nullptr, (size_t)0);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    const size_t stride = align256(hs_dp_bytes(u, hb));
+    const size_t fit = pool_bytes / stride;
+    const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
+    for (uint32_t i = 0; i < hist[u]; i += per) {  // launches on one stream: each finds the pool free
+      launch_hs_pm(true, gated, min(per, hist[u] - i), fixed, s, a, a.order + off[u] + i, u, pool, stride);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  // the cursor upload reads `off` from this frame: it must have left before the function returns
+  HIP_TRY(hipStreamSynchronize(s));
+  return W2A_OK;
+}
+
+int w2a_hindsight_posterior(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                            uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+  return hindsight_posterior("w2a_hindsight_posterior", env, start, n_steps, ret_out, alert_mask, mask_words, alerts_out,
+                             workspace, workspace_bytes, stream, false, nullptr, 0);
+}
+
+int w2a_hindsight_posterior_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                                  uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
+                                  size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
+                                  int32_t allowed_words) {
+  return hindsight_posterior("w2a_hindsight_posterior_gated", env, start, n_steps, ret_out, alert_mask, mask_words,
+                             alerts_out, workspace, workspace_bytes, stream, true, allowed_days, allowed_words);
 }
 
 // workspace of w2a_hindsight_curve: the slot-27 flag, then the pool when the DP of max_budget does not fit in LDS

@@ -2006,6 +2006,79 @@ class HeatAlertVecEnv(_VectorEnvBase):
         days = (((mask.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()
         return {"return": ret, "alert_days": days, "alerts": alerts}
 
+    def hindsight_posterior_optimum(self, start_state: dict | None = None, n_steps: int | None = None,
+                                    allowed_days=None, share: bool = True, posterior_returns: bool = False) -> dict:
+        """Every env's best alert schedule in hindsight WITH THE DRAW UNKNOWN: knowing the weather of the whole stretch
+        and the remaining budget, but not the env's posterior draw, the schedule of at most budget - used alerts with
+        the highest return AVERAGED OVER ALL n_samples DRAWS of the env's coefficient column. No policy observes the
+        draw, so this -- not hindsight_optimum() -- is the bound a policy can reach, an imitation expert whose labels
+        are functions of what a policy sees, and the yardstick of a reward_mode="posterior_mean" env (which pays that
+        average). start_state, n_steps and allowed_days as hindsight_optimum(). Returns
+            "return":     f32 [N]     the schedule's posterior-mean return: the fp64 sum over its days of the mean
+                                      over draws of the f32 rewards, rounded once (the draw-mean of
+                                      posterior_returns(start_state, alert_days) up to f32 rounding)
+            "alert_days": bool [N, T] the schedule (day of the episode; only the stretch's days can be set)
+            "alerts":     i32 [N]     alerts in it
+            "posterior_returns" (posterior_returns=True): f32 [N, n_samples], posterior_returns(start_state, alert_days)
+                                      on the schedule: column `sample` is what a sampled env pays for it, and the
+                                      rows feed stats.posterior_summary
+        Envs finished in start_state give 0 and an empty schedule, a start outside the tables NaN; ties do not alert.
+        hindsight_optimum()'s exact DP over (alerts issued, current streak) with the reward of every state averaged over
+        the draws in fp64, in draw order (w2a_hindsight_posterior, include/w2a.h); with n_samples = 1 the schedule is
+        hindsight_optimum()'s bit for bit. The result does not depend on `sample`: with share=True (the default) envs
+        that agree on t, used, streak, budget, n_days, county_w, year_i, coef_col and finished are found on the host
+        (torch.unique), one of each runs and the outputs are gathered back -- bit for bit what share=False, which runs
+        every env, returns. With allowed_days every env has its own gate row and nothing is shared.
+        Sampled and posterior_mean envs alike; faithful semantics only, and tables whose slot-27 coefficient is nonzero
+        or whose n_samples is beyond the kernel's per-draw arrays (657 draws at 153 days) are refused before anything
+        is written. Reads start_state and the tables only: the env's state, observation buffer and bookkeeping are
+        untouched."""
+        who = "hindsight_posterior_optimum()"
+        self._check_hindsight_fixes(who)
+        self._check_hindsight_slot27(who)
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _ffi.W2AError(f"{who}: the stream is recording a hipGraph; the call finds the distinct problems and "
+                                "sizes its launches on the host")
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        if start_state is None:
+            st = self._state_packed(_HS_FIELDS)[1]
+        else:
+            st = {}
+            for k in _HS_FIELDS:
+                if k not in start_state:
+                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
+                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
+                if st[k].shape != (n,):
+                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
+        steps = int(n_steps) if n_steps is not None else ct.T
+        if steps <= 0:
+            raise ValueError("n_steps must be positive")
+        with torch.cuda.device(dev):
+            if share and gate is None and n:
+                # one DP per distinct problem; a draw outside the tables keeps its own key (its answer is NaN)
+                key = torch.stack([st[k] for k in _HS_FIELDS if k != "sample"] +
+                                  [((st["sample"] < 0) | (st["sample"] >= ct.n_samples)).to(torch.int32)], dim=1)
+                uniq, inv = torch.unique(key, dim=0, return_inverse=True)
+                m = uniq.shape[0]
+                first = torch.full((m,), n, dtype=torch.int64, device=dev)
+                first.scatter_reduce_(0, inv, torch.arange(n, device=dev), reduce="amin")  # the lowest env id per key
+                # the library runs num_envs entries: the representatives first, the rest marked finished (no DP)
+                rep = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in _HS_FIELDS}
+                rep["finished"].fill_(1)
+                for k in _HS_FIELDS:
+                    rep[k][:m] = st[k][first]
+                ret, mask, alerts = (x[:m][inv] for x in self._hindsight_posterior_packed(rep, steps, None))
+                self.last_hindsight_posterior_keys = int(m)
+            else:
+                ret, mask, alerts = self._hindsight_posterior_packed(st, steps, gate)
+                self.last_hindsight_posterior_keys = n
+        out = {"return": ret, "alert_days": _policy.unpack_alert_days(mask, ct.T), "alerts": alerts}
+        if posterior_returns:
+            pr_state = dict(start_state) if start_state is not None else self.state()
+            out["posterior_returns"] = self.posterior_returns(pr_state, out["alert_days"], n_steps=n_steps)
+        return out
+
     def hindsight_values(self, alert_days, start_state: dict | None = None, n_steps: int | None = None,
                          allowed_days=None, value: bool = False, loss: bool = False) -> dict:
         """What hindsight_optimum()'s DP says in the states a GIVEN schedule reaches: the expert's action on every day
@@ -2162,12 +2235,18 @@ class HeatAlertVecEnv(_VectorEnvBase):
         return out
 
     def _check_hindsight(self, who: str):
-        if self.fixes - {"budget"}:
-            raise ValueError(f"{who} needs faithful semantics; fixes {sorted(self.fixes - {'budget'})} make the reward "
-                             "depend on attempts and on the 14-day window")
+        self._check_hindsight_fixes(who)
         if self._pm:
             raise ValueError(f"{who} needs reward_mode='sampled', not 'posterior_mean': that env pays the mean over "
                              "draws, so an optimum under the env's own draw is not its yardstick")
+        self._check_hindsight_slot27(who)
+
+    def _check_hindsight_fixes(self, who: str):
+        if self.fixes - {"budget"}:
+            raise ValueError(f"{who} needs faithful semantics; fixes {sorted(self.fixes - {'budget'})} make the reward "
+                             "depend on attempts and on the 14-day window")
+
+    def _check_hindsight_slot27(self, who: str):
         dt = self.dtables
         if getattr(dt, "_slot27_zero", None) is None:  # once per table
             dt._slot27_zero = not bool(np.any(np.asarray(self.ct.W).reshape(-1, 2, 32)[:, :, 27] != 0))
@@ -2201,6 +2280,31 @@ class HeatAlertVecEnv(_VectorEnvBase):
         else:
             _ffi.check(self._lib.w2a_hindsight_optimum_gated(*hs_args, gate.data_ptr(), int(gate.shape[1])),
                        "w2a_hindsight_optimum_gated")
+        return ret, mask, alerts
+
+    def _hindsight_posterior_packed(self, st0: dict, steps: int, gate=None):
+        """w2a_hindsight_posterior on device int32 state arrays: (return f32 [N], packed bitmap i32 [N, words],
+        alerts i32 [N]), as _hindsight_packed."""
+        n, dev, ct = self.num_envs, self.device, self.ct
+        words = (ct.T + 31) // 32
+        ret = torch.empty(n, dtype=torch.float32, device=dev)
+        mask = torch.empty((n, words), dtype=torch.int32, device=dev)
+        alerts = torch.empty(n, dtype=torch.int32, device=dev)
+        live = (st0["finished"] == 0) & (st0["t"] < st0["n_days"])
+        rem = int(torch.where(live, st0["budget"] - st0["used"], 0).max().item()) if n else 0
+        ws_bytes = self._lib.w2a_hindsight_posterior_workspace_bytes(n, ct.T, ct.n_samples, steps,
+                                                                    max(0, min(rem, 1 << 30)), _HS_BIG_ENVS)
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)  # (0: the entry refuses, with its message)
+        v = _ffi.StateView()
+        for k in _HS_FIELDS:
+            setattr(v, k, st0[k].data_ptr())
+        hs_args = (self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words, alerts.data_ptr(), ws.data_ptr(),
+                   ws_bytes, self._stream())
+        if gate is None:
+            _ffi.check(self._lib.w2a_hindsight_posterior(*hs_args), "w2a_hindsight_posterior")
+        else:
+            _ffi.check(self._lib.w2a_hindsight_posterior_gated(*hs_args, gate.data_ptr(), int(gate.shape[1])),
+                       "w2a_hindsight_posterior_gated")
         return ret, mask, alerts
 
     # ------------------------------------------------------------------ alert gate
