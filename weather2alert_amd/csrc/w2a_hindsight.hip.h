@@ -110,9 +110,10 @@ __global__ __launch_bounds__(256) void k_hs_plan(const HsArgs a) {
     if (cnt[b]) atomicAdd(&a.hist[b], cnt[b]);
 }
 
-// counting sort by U: a block reserves one range per bin, its envs take consecutive places in it; envs without a DP
-// get their outputs here (0 or NaN, an empty bitmap, no alerts)
-__global__ __launch_bounds__(256) void k_hs_scatter(const HsArgs a) {
+// counting sort by U: a block reserves one range per bin, its envs take consecutive places in it; an env without a DP
+// gets its outputs from fill(e, bad) (bad: a start outside the tables)
+template <class Fill>
+__device__ __forceinline__ void hs_scatter(const HsArgs &a, Fill fill) {
   __shared__ uint32_t cnt[HS_BINS];
   const uint32_t nb = (uint32_t)a.hb + 1u;
   for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
@@ -120,11 +121,7 @@ __global__ __launch_bounds__(256) void k_hs_scatter(const HsArgs a) {
   const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   uint32_t U = e < (uint64_t)a.n ? a.u_env[e] : HS_NONE;
   if (U == HS_NONE || U == HS_BAD) {
-    if (e < (uint64_t)a.n) {
-      a.ret[e] = U == HS_BAD ? __builtin_nanf("") : 0.0f;
-      a.alerts[e] = 0;
-      for (int w = 0; w < a.mask_words; ++w) a.mask[e * (uint32_t)a.mask_words + w] = 0u;
-    }
+    if (e < (uint64_t)a.n) fill(e, U == HS_BAD);
     U = HS_NONE;
   }
   const uint32_t rank = U != HS_NONE ? atomicAdd(&cnt[U], 1u) : 0u;
@@ -133,6 +130,15 @@ __global__ __launch_bounds__(256) void k_hs_scatter(const HsArgs a) {
     if (cnt[b]) cnt[b] = atomicAdd(&a.cursor[b], cnt[b]);
   __syncthreads();
   if (U != HS_NONE) a.order[cnt[U] + rank] = (uint32_t)e;
+}
+
+// hs_scatter for w2a_hindsight_optimum and w2a_hindsight_posterior: 0 or NaN, an empty bitmap, no alerts
+__global__ __launch_bounds__(256) void k_hs_scatter(const HsArgs a) {
+  hs_scatter(a, [&](uint64_t e, bool bad) {
+    a.ret[e] = bad ? __builtin_nanf("") : 0.0f;
+    a.alerts[e] = 0;
+    for (int w = 0; w < a.mask_words; ++w) a.mask[e * (uint32_t)a.mask_words + w] = 0u;
+  });
 }
 
 struct HsCoef {  // the coefficients of the run-time part of both chains (slots 24, 25, 26, 28, 29), fp64
@@ -167,6 +173,81 @@ __device__ __forceinline__ uint32_t hs_row(uint32_t idx) {  // j of state idx: j
   return j;
 }
 
+// ---- the statements every kernel of the family shares (k_hs_dp, k_hs_along, k_hs_curve, k_hs_pm_dp): written once, so
+// that "the same statements, the same bits" holds by construction
+
+// the two fp64 prefixes (b, e) over slots 0..23 of one day (row xp) under one coefficient row pair (wq)
+__device__ __forceinline__ double2 hs_prefix(const float4 *xp, const float4 *wq) {
+  double zb = 0.0, ze = 0.0;
+#pragma unroll
+  for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
+    const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
+    zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
+    zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
+    zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
+    zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
+  }
+  return make_double2(zb, ze);
+}
+
+// a day's tail from quad 7 of its row: x28, x29, the heat gate, -
+__device__ __forceinline__ float4 hs_day_tail(const float4 x7) {
+  return make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
+}
+
+// day statics under the coefficient rows wq, lanes over days: pz[d] and tl[d] for d = lane .. H
+__device__ __forceinline__ void hs_day_statics(const HsArgs &a, const HsEnv &h, const float4 *wq, uint32_t lane,
+                                               double2 *pz, float4 *tl) {
+  const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
+  for (uint32_t d = lane; d < h.H; d += HS_BLOCK) {
+    const float4 *xp = a.tb.X + (size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4);
+    const double2 p = hs_prefix(xp, wq);
+    const float4 x7 = xp[GATE_QUAD];
+    pz[d] = p;
+    tl[d] = hs_day_tail(x7);
+  }
+}
+
+__device__ __forceinline__ HsCoef hs_load_coef(const float4 *wq) {
+  const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
+  HsCoef c;
+  c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
+  c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
+  return c;
+}
+
+// env e's bitmap row: lane l holds word l (every lane walked the same path); words past the 64th are empty
+__device__ __forceinline__ void hs_store_mask_row(const HsArgs &a, uint32_t e, uint32_t lane, uint32_t word) {
+  for (uint32_t w = lane; w < (uint32_t)a.mask_words; w += HS_BLOCK)
+    a.mask[(size_t)e * (uint32_t)a.mask_words + w] = w < HS_BLOCK && w == lane ? word : 0u;
+}
+
+// state idx = (j, k) of the (alerts, streak) DP on a day with prefixes p and tail tq, V_{d+1} in vn: both Q values, the
+// strict comparison and V_d. k_hs_dp keeps `best` and `alert`; k_hs_along also q0, q1 and `allowed` in the path's state.
+struct HsState {
+  bool allowed, alert;  // the alert transition exists (budget left, day open); the DP takes it
+  double q0, q1, best;  // q1 = q0 where no alert is allowed
+};
+__device__ __forceinline__ HsState hs_state(const HsCoef &c, const HsEnv &h, int32_t rem0, bool open, double2 p, float4 tq,
+                                            bool gate, bool day0, const double *vn, uint32_t idx) {
+  const uint32_t j = hs_row(idx), k = idx - j * (j + 3u) / 2u;
+  const float s = (float)(k == j + 1u ? h.s0 + j : k);
+  const int32_t rem = h.budget - (int32_t)(h.used + j);
+  HsState r;
+  r.allowed = (int32_t)j < rem0 && open;
+  const float r0 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem, 0u);
+  r.q0 = (double)r0 + vn[j * (j + 3u) / 2u];
+  r.best = r.q0; r.q1 = r.q0;
+  r.alert = false;
+  if (r.allowed) {
+    const float r1 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem - 1, 1u);
+    r.q1 = (double)r1 + vn[(j + 1u) * (j + 4u) / 2u + k + 1u];
+    r.alert = r.q1 > r.q0;
+    r.best = r.alert ? r.q1 : r.q0;
+  }
+  return r;
+}
+
 // one env per 64-lane workgroup; envs list[0 .. gridDim.x) all have this U. GLOBAL: V and the decision words live in
 // `pool` (pool_stride bytes per workgroup) instead of LDS.
 // GATE: the alert transition exists only on the days a.gate allows (the best schedule UNDER the restriction); the word
@@ -189,29 +270,8 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
 
   // the env's own coefficient rows (wave-uniform), f32 as stored
   const float4 *wq = a.tb.W + (size_t)h.wrow * (2 * ROWF / 4);
-  // ---- day statics: lanes over days
-  const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
-  for (uint32_t d = lane; d < H; d += HS_BLOCK) {
-    const float4 *xp = a.tb.X + (size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4);
-    double zb = 0.0, ze = 0.0;
-#pragma unroll
-    for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
-      const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
-      zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
-      zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
-      zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
-      zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
-    }
-    const float4 x7 = xp[GATE_QUAD];
-    pz[d] = make_double2(zb, ze);
-    tl[d] = make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
-  }
-  HsCoef c;
-  {
-    const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
-    c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
-    c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
-  }
+  hs_day_statics(a, h, wq, lane, pz, tl);
+  const HsCoef c = hs_load_coef(wq);
   const int32_t rem0 = h.budget - (int32_t)h.used;  // remaining budget at the start; an alert needs j < rem0
   for (uint32_t i = lane; i < hs_ns(U); i += HS_BLOCK) V1[i] = 0.0;  // V_H = 0
   __syncthreads();
@@ -228,23 +288,11 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
     const bool day0 = (h.t0 + (uint32_t)d) == 0u, gate = tq.z != 0.0f;
     for (uint32_t c0 = 0; c0 < nsd; c0 += HS_BLOCK) {
       const uint32_t idx = c0 + lane;
-      const bool valid = idx < nsd;
       bool alert = false;
-      if (valid) {
-        const uint32_t j = hs_row(idx), k = idx - j * (j + 3u) / 2u;
-        const float s = (float)(k == j + 1u ? h.s0 + j : k);
-        const int32_t rem = h.budget - (int32_t)(h.used + j);
-        const bool allowed = (int32_t)j < rem0 && open;
-        const float r0 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem, 0u);
-        const double q0 = (double)r0 + vn[j * (j + 3u) / 2u];
-        double best = q0;
-        if (allowed) {
-          const float r1 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem - 1, 1u);
-          const double q1 = (double)r1 + vn[(j + 1u) * (j + 4u) / 2u + k + 1u];
-          alert = q1 > q0;
-          best = alert ? q1 : q0;
-        }
-        vc[idx] = best;
+      if (idx < nsd) {
+        const HsState st = hs_state(c, h, rem0, open, p, tq, gate, day0, vn, idx);
+        alert = st.alert;
+        vc[idx] = st.best;
       }
       const uint64_t bits = __ballot(alert);
       if (lane == 0) dec[(size_t)d * NCU + c0 / HS_BLOCK] = bits;
@@ -272,8 +320,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
     j += act;
     k = act ? k + 1u : 0u;
   }
-  for (uint32_t w = lane; w < (uint32_t)a.mask_words; w += HS_BLOCK)
-    a.mask[(size_t)e * (uint32_t)a.mask_words + w] = w < HS_BLOCK && w == lane ? word : 0u;
+  hs_store_mask_row(a, e, lane, word);
   if (lane == 0) {
     a.ret[e] = ret;
     a.alerts[e] = (int32_t)n_alerts;
@@ -284,9 +331,9 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_dp(const HsArgs a, const uint32
 // hindsight values along a GIVEN schedule (w2a_hindsight_along)
 // ----------------------------------------------------------------------------------------
 // The backward sweep above forms Q_d(state, no alert) and Q_d(state, alert) of every reachable state and keeps only
-// what the optimum's own path needs. k_hs_along runs the same sweep (the same statements: the same rewards, the same
-// fp64 values, the same strict comparison) and keeps, per day, the values of the ONE state a caller's schedule
-// reaches: the labels DAgger fits to and the per-day share of the regret.
+// what the optimum's own path needs. k_hs_along runs the same sweep (hs_state: the same rewards, the same fp64 values,
+// the same strict comparison) and keeps, per day, the values of the ONE state a caller's schedule reaches: the labels
+// DAgger fits to and the per-day share of the regret.
 //   Forward first: every lane walks the schedule (attempts; closed days and attempts without budget are no-ops) and
 //   lane 0 leaves the day's state index and the alert issued in the fourth float of tl[d] (bit 31 the alert, bits
 //   0..29 the index), so LDS and workspace are those of k_hs_dp (the decision words' room is simply not used).
@@ -302,36 +349,21 @@ struct HsAlongArgs {
   float *loss;            // [hb][n], nullable
 };
 
-// k_hs_scatter for w2a_hindsight_along: the same counting sort; envs without a DP get 0 (NaN: a start outside the
-// tables) in every float output, NaN in every gain and an empty bitmap
+// hs_scatter for w2a_hindsight_along: envs without a DP get 0 (NaN: a start outside the tables) in every float output,
+// NaN in every gain and an empty bitmap
 __global__ __launch_bounds__(256) void k_hs_along_scatter(const HsAlongArgs aa) {
   const HsArgs &a = aa.h;
-  __shared__ uint32_t cnt[HS_BINS];
-  const uint32_t nb = (uint32_t)a.hb + 1u;
-  for (uint32_t b = threadIdx.x; b < nb; b += 256) cnt[b] = 0;
-  __syncthreads();
-  const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  uint32_t U = e < (uint64_t)a.n ? a.u_env[e] : HS_NONE;
-  if (U == HS_NONE || U == HS_BAD) {
-    if (e < (uint64_t)a.n) {
-      const float nan = __builtin_nanf(""), fill = U == HS_BAD ? nan : 0.0f;
-      a.ret[e] = fill;
-      for (int w = 0; w < a.mask_words; ++w) a.mask[e * (uint32_t)a.mask_words + w] = 0u;
-      for (uint32_t s = 0; s < (uint32_t)a.hb; ++s) {
-        const size_t o = (size_t)s * (size_t)a.n + e;
-        aa.gain[o] = nan;
-        if (aa.value) aa.value[o] = fill;
-        if (aa.loss) aa.loss[o] = fill;
-      }
+  hs_scatter(a, [&](uint64_t e, bool bad) {
+    const float nan = __builtin_nanf(""), fill = bad ? nan : 0.0f;
+    a.ret[e] = fill;
+    for (int w = 0; w < a.mask_words; ++w) a.mask[e * (uint32_t)a.mask_words + w] = 0u;
+    for (uint32_t s = 0; s < (uint32_t)a.hb; ++s) {
+      const size_t o = (size_t)s * (size_t)a.n + e;
+      aa.gain[o] = nan;
+      if (aa.value) aa.value[o] = fill;
+      if (aa.loss) aa.loss[o] = fill;
     }
-    U = HS_NONE;
-  }
-  const uint32_t rank = U != HS_NONE ? atomicAdd(&cnt[U], 1u) : 0u;
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < nb; b += 256)
-    if (cnt[b]) cnt[b] = atomicAdd(&a.cursor[b], cnt[b]);
-  __syncthreads();
-  if (U != HS_NONE) a.order[cnt[U] + rank] = (uint32_t)e;
+  });
 }
 
 #define HS_PATH_ALERT 0x80000000u   // the alert the schedule issues that day
@@ -356,29 +388,8 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_along(const HsAlongArgs aa, con
 
   // the env's own coefficient rows (wave-uniform), f32 as stored
   const float4 *wq = a.tb.W + (size_t)h.wrow * (2 * ROWF / 4);
-  // ---- day statics: lanes over days
-  const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
-  for (uint32_t d = lane; d < H; d += HS_BLOCK) {
-    const float4 *xp = a.tb.X + (size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4);
-    double zb = 0.0, ze = 0.0;
-#pragma unroll
-    for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
-      const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
-      zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
-      zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
-      zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
-      zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
-    }
-    const float4 x7 = xp[GATE_QUAD];
-    pz[d] = make_double2(zb, ze);
-    tl[d] = make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
-  }
-  HsCoef c;
-  {
-    const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
-    c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
-    c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
-  }
+  hs_day_statics(a, h, wq, lane, pz, tl);
+  const HsCoef c = hs_load_coef(wq);
   const int32_t rem0 = h.budget - (int32_t)h.used;  // remaining budget at the start; an alert needs j < rem0
   for (uint32_t i = lane; i < hs_ns(U); i += HS_BLOCK) V1[i] = 0.0;  // V_H = 0
   __syncthreads();
@@ -399,7 +410,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_along(const HsAlongArgs aa, con
   }
   __syncthreads();
 
-  // ---- backward DP (k_hs_dp's, statement for statement): V_{d+1} in vn, V_d into vc
+  // ---- backward DP (k_hs_dp's: hs_state): V_{d+1} in vn, V_d into vc
   double *vn = V1, *vc = V0;
   uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   const size_t n = (size_t)a.n;
@@ -415,30 +426,16 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_along(const HsAlongArgs aa, con
     double mine_loss = 0.0;
     for (uint32_t c0 = 0; c0 < nsd; c0 += HS_BLOCK) {
       const uint32_t idx = c0 + lane;
-      const bool valid = idx < nsd;
-      if (valid) {
-        const uint32_t j = hs_row(idx), k = idx - j * (j + 3u) / 2u;
-        const float s = (float)(k == j + 1u ? h.s0 + j : k);
-        const int32_t rem = h.budget - (int32_t)(h.used + j);
-        const bool allowed = (int32_t)j < rem0 && open;
-        const float r0 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem, 0u);
-        const double q0 = (double)r0 + vn[j * (j + 3u) / 2u];
-        double best = q0, q1 = q0;
-        bool alert = false;
-        if (allowed) {
-          const float r1 = hs_reward(c, p.x, p.y, tq.x, tq.y, gate, day0, s, rem - 1, 1u);
-          q1 = (double)r1 + vn[(j + 1u) * (j + 4u) / 2u + k + 1u];
-          alert = q1 > q0;
-          best = alert ? q1 : q0;
-        }
-        vc[idx] = best;
+      if (idx < nsd) {
+        const HsState st = hs_state(c, h, rem0, open, p, tq, gate, day0, vn, idx);
+        vc[idx] = st.best;
         if (idx == (path & HS_PATH_IDX)) {
           const size_t o = (size_t)d * n + e;
           mine = true;
-          mine_alert = alert;
-          mine_loss = best - ((path & HS_PATH_ALERT) ? q1 : q0);  // an issued alert was allowed: q1 is its value
-          aa.gain[o] = allowed ? (float)(q1 - q0) : __builtin_nanf("");
-          if (aa.value) aa.value[o] = (float)best;
+          mine_alert = st.alert;
+          mine_loss = st.best - ((path & HS_PATH_ALERT) ? st.q1 : st.q0);  // an issued alert was allowed: q1 is its value
+          aa.gain[o] = st.allowed ? (float)(st.q1 - st.q0) : __builtin_nanf("");
+          if (aa.value) aa.value[o] = (float)st.best;
           if (aa.loss) aa.loss[o] = (float)mine_loss;
         }
       }
@@ -458,8 +455,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_along(const HsAlongArgs aa, con
     const uint32_t path = reinterpret_cast<const uint32_t *>(tl + d)[3];
     if ((path & HS_PATH_EXPERT) && lane == (tt >> 5)) word |= 1u << (tt & 31u);
   }
-  for (uint32_t w = lane; w < (uint32_t)a.mask_words; w += HS_BLOCK)
-    a.mask[(size_t)e * (uint32_t)a.mask_words + w] = w < HS_BLOCK && w == lane ? word : 0u;
+  hs_store_mask_row(a, e, lane, word);
   if (lane == 0) {
     double regret = 0.0;
     for (uint32_t d = 0; d < H; ++d) regret += pz[d].x;

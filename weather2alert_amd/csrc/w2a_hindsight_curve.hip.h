@@ -89,29 +89,8 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_curve(const HcArgs ca, uint32_t
 
   // the env's own coefficient rows (wave-uniform), f32 as stored
   const float4 *wq = a.tb.W + (size_t)h.wrow * (2 * ROWF / 4);
-  // ---- day statics: lanes over days
-  const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
-  for (uint32_t d = lane; d < H; d += HS_BLOCK) {
-    const float4 *xp = a.tb.X + (size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4);
-    double zb = 0.0, ze = 0.0;
-#pragma unroll
-    for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
-      const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
-      zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
-      zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
-      zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
-      zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
-    }
-    const float4 x7 = xp[GATE_QUAD];
-    pz[d] = make_double2(zb, ze);
-    tl[d] = make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
-  }
-  HsCoef c;
-  {
-    const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
-    c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
-    c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
-  }
+  hs_day_statics(a, h, wq, lane, pz, tl);
+  const HsCoef c = hs_load_coef(wq);
   for (uint32_t i = lane; i < NS; i += HS_BLOCK) V1[i] = 0.0;  // V_H = 0
   __syncthreads();
 

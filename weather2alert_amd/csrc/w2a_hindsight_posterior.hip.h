@@ -22,7 +22,7 @@
 //   draw), per draw the run-time coefficients (HsCoef, 80 B, filled once) and ONE day's two fp64 prefixes over slots
 //   0..23 (16 B), then V and the decision words as in k_hs_dp (GLOBAL: in the caller's pool).
 //   Per day of the backward sweep, lanes over draws (lane, lane + 64, ...) form that day's prefixes of every draw with
-//   the FMA chain of k_hs_dp's statics loop; one barrier; then k_hs_dp's state loop with the two hs_reward calls inside
+//   hs_prefix, the FMA chain of k_hs_dp's statics; one barrier; then k_hs_dp's state loop with the two hs_reward calls inside
 //   a loop over draws whose prefixes and coefficients are wave-uniform LDS reads. The coefficient rows of slots 0..23
 //   (192 B per draw) are re-read from L2 every day rather than kept in registers: draws per lane are a run-time number,
 //   two draws would take 96 VGPRs, and the reads (19 KB per env-day at K = 100) are two orders below the state loop's
@@ -31,20 +31,6 @@
 //   chosen reward, leaves (double) r^(i) in LDS, and after a barrier every lane adds them in draw order -- the same sum
 //   and the same bits as the sweep's m_a.
 __host__ __device__ __forceinline__ size_t hs_pm_fixed_bytes(uint32_t hb, uint32_t K) { return 16ull * hb + 96ull * K; }
-
-// the two fp64 prefixes over slots 0..23 of one day (row xp) under one draw (rows wq): k_hs_dp's chain
-__device__ __forceinline__ double2 hs_pm_prefix(const float4 *xp, const float4 *wq) {
-  double zb = 0.0, ze = 0.0;
-#pragma unroll
-  for (int q = 0; q < RT_QUAD; ++q) {  // slots 0..23 in slot order
-    const float4 x = xp[q], b = wq[q], f = wq[ROWF / 4 + q];
-    zb = fma((double)x.x, (double)b.x, zb); ze = fma((double)x.x, (double)f.x, ze);
-    zb = fma((double)x.y, (double)b.y, zb); ze = fma((double)x.y, (double)f.y, ze);
-    zb = fma((double)x.z, (double)b.z, zb); ze = fma((double)x.z, (double)f.z, ze);
-    zb = fma((double)x.w, (double)b.w, zb); ze = fma((double)x.w, (double)f.w, ze);
-  }
-  return make_double2(zb, ze);
-}
 
 // one env per 64-lane workgroup; list, U, GLOBAL, GATE, pool as k_hs_dp
 template <bool GLOBAL, bool GATE>
@@ -69,18 +55,9 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_pm_dp(const HsArgs a, const uin
   const float4 *w0 = a.tb.W + (size_t)((uint32_t)a.st.coef_col[e] * K) * (2 * ROWF / 4);
   const uint32_t rows_per_day = (uint32_t)(a.tb.S_w * a.tb.Y);
   // ---- day tails: lanes over days; run-time coefficients: lanes over draws
-  for (uint32_t d = lane; d < H; d += HS_BLOCK) {
-    const float4 x7 = a.tb.X[(size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4) + GATE_QUAD];
-    tl[d] = make_float4(x7.x, x7.y, x7.z > 0.5f ? 1.0f : 0.0f, 0.0f);
-  }
-  for (uint32_t i = lane; i < K; i += HS_BLOCK) {
-    const float4 *wq = w0 + (size_t)i * (2 * ROWF / 4);
-    const float4 b6 = wq[RT_QUAD], b7 = wq[GATE_QUAD], f6 = wq[ROWF / 4 + RT_QUAD], f7 = wq[ROWF / 4 + GATE_QUAD];
-    HsCoef c;
-    c.b24 = b6.x; c.b25 = b6.y; c.b26 = b6.z; c.b28 = b7.x; c.b29 = b7.y;
-    c.e24 = f6.x; c.e25 = f6.y; c.e26 = f6.z; c.e28 = f7.x; c.e29 = f7.y;
-    cf[i] = c;
-  }
+  for (uint32_t d = lane; d < H; d += HS_BLOCK)
+    tl[d] = hs_day_tail(a.tb.X[(size_t)((h.t0 + d) * rows_per_day + h.ep_row) * (ROWF / 4) + GATE_QUAD]);
+  for (uint32_t i = lane; i < K; i += HS_BLOCK) cf[i] = hs_load_coef(w0 + (size_t)i * (2 * ROWF / 4));
   const int32_t rem0 = h.budget - (int32_t)h.used;  // remaining budget at the start; an alert needs j < rem0
   const double dK = (double)K;
   for (uint32_t i = lane; i < hs_ns(U); i += HS_BLOCK) V1[i] = 0.0;  // V_H = 0
@@ -91,7 +68,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_pm_dp(const HsArgs a, const uin
   uint32_t gate_word = 0, gate_idx = 0xFFFFFFFFu;
   for (int32_t d = (int32_t)H - 1; d >= 0; --d) {
     const float4 *xp = a.tb.X + (size_t)((h.t0 + (uint32_t)d) * rows_per_day + h.ep_row) * (ROWF / 4);
-    for (uint32_t i = lane; i < K; i += HS_BLOCK) pp[i] = hs_pm_prefix(xp, w0 + (size_t)i * (2 * ROWF / 4));
+    for (uint32_t i = lane; i < K; i += HS_BLOCK) pp[i] = hs_prefix(xp, w0 + (size_t)i * (2 * ROWF / 4));
     __syncthreads();
     const bool open = !GATE || gate_allows(a.gate, a.gate_words, e, h.t0 + (uint32_t)d, gate_word, gate_idx);
     const uint32_t J = min((uint32_t)d, U);
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_pm_dp(const HsArgs a, const uin
     const int32_t rem = h.budget - (int32_t)(h.used + j + act);
     const float4 *xp = a.tb.X + (size_t)(tt * rows_per_day + h.ep_row) * (ROWF / 4);
     for (uint32_t i = lane; i < K; i += HS_BLOCK) {
-      const double2 p = hs_pm_prefix(xp, w0 + (size_t)i * (2 * ROWF / 4));
+      const double2 p = hs_prefix(xp, w0 + (size_t)i * (2 * ROWF / 4));
       rr[i] = (double)hs_reward(cf[i], p.x, p.y, tq.x, tq.y, tq.z != 0.0f, tt == 0u, s, rem, act);
     }
     __syncthreads();
@@ -156,8 +133,7 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_pm_dp(const HsArgs a, const uin
     j += act;
     k = act ? k + 1u : 0u;
   }
-  for (uint32_t w = lane; w < (uint32_t)a.mask_words; w += HS_BLOCK)
-    a.mask[(size_t)e * (uint32_t)a.mask_words + w] = w < HS_BLOCK && w == lane ? word : 0u;
+  hs_store_mask_row(a, e, lane, word);
   if (lane == 0) {
     a.ret[e] = (float)ret;
     a.alerts[e] = (int32_t)n_alerts;

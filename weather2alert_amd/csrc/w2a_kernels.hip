@@ -882,17 +882,168 @@ int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint3
   return W2A_OK;
 }
 
-// workspace of w2a_hindsight_optimum: U per env, histogram + cursors of U, env ids by U, then the pool of the bins whose
-// DP does not fit in LDS (big_envs envs of the largest U a horizon of hb days can have)
+// ----------------------------------------------------------------------------------------
+// hindsight family: w2a_hindsight_optimum / _along, w2a_hindsight_posterior, w2a_hindsight_curve
+// ----------------------------------------------------------------------------------------
+// What the three bodies share is written once, in the manner of w2a_policy_dispatch.hip.h: check_hs_* (the refusals, in
+// the order every entry reports them), hs_refuse_slot27, fill_hs_args, hs_bin (plan -> histogram -> prefix sum -> pool
+// check -> cursor), hs_launch_bins (LDS or pool, bin by bin) and HS_LAUNCH (the <GLOBAL, GATE> instantiation, chosen at
+// run time). Each body keeps the ORDER of the calls, its own NULL test, what only it refuses and its own messages.
+// Every refusal comes before the first kernel that writes a caller's array.
+
+#define HS_CHECK(expr)             \
+  do {                             \
+    const int rc_ = (expr);        \
+    if (rc_ != W2A_OK) return rc_; \
+  } while (0)
+
+// fail() with the entry's name and one more string
+static int hs_fail(const char *fmt, const char *fn, const char *what) {
+  snprintf(g_err, sizeof(g_err), fmt, fn, what);
+  return W2A_ERR_ARG;
+}
+
+// what can be checked without the handle (so that it is checked on any machine), after the entry's own NULL test.
+// has_mask: the curve's alert_masks may be NULL, mask_words is then not read
+static int check_hs_start(const char *fn, const w2a_state_view *start, int32_t n_steps, bool has_mask, int32_t mask_words) {
+  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
+      !start->year_i || !start->coef_col || !start->sample || !start->finished)
+    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
+                             "year_i, coef_col, sample and finished are read)", fn);
+  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
+  if (has_mask && mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
+  return W2A_OK;
+}
+
+// the handle, the bitmap's width (mask_rule: the entry's sentence about its array) and the semantics flags
+static int check_hs_handle(const char *fn, const w2a_env *env, bool has_mask, int32_t mask_words, const char *mask_rule) {
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if (has_mask && (int64_t)mask_words * 32 < env->tb.T) return hs_fail("%s: %s", fn, mask_rule);
+  if (env->tb.fixes)
+    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
+                             "depends on attempts and on the 14-day window)", fn);
+  return W2A_OK;
+}
+
+// the gate of a _gated entry, then the capture: the last refusals that read no workspace
+static int check_hs_gate_capture(const char *fn, const w2a_env *env, bool gated, const uint32_t *gate, int32_t gate_words,
+                                 void *stream) {
+  if (gated) HS_CHECK(check_gate(fn, env, gate, gate_words));
+  return refuse_while_capturing(fn, stream);
+}
+
+// is the slot-27 coefficient zero in every row? (checked before any output is written; the flag is the workspace's
+// first word). dp_state: what the entry's DP state holds beside the streak
+static int hs_refuse_slot27(const char *fn, const w2a_env *env, void *workspace, hipStream_t s, const char *dp_state) {
+  int32_t *flag = reinterpret_cast<int32_t *>(workspace);
+  const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
+  HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
+  HIP_TRY(hipGetLastError());
+  int32_t used27 = 1;
+  HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (used27)
+    return hs_fail("%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
+                   "agent): the (%s, streak) DP would not be exact", fn, dp_state);
+  return W2A_OK;
+}
+
+// the caller's side of HsArgs (gate NULL: an entry without _gated)
+static void fill_hs_args(HsArgs &a, const w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
+                         uint32_t *mask, int32_t mask_words, int32_t *alerts_out, const uint32_t *gate, int32_t gate_words) {
+  memset(&a, 0, sizeof(a));
+  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = min(n_steps, env->tb.T); a.mask_words = mask_words; a.n = env->n;
+  a.ret = ret_out; a.mask = mask; a.alerts = alerts_out;
+  a.gate = gate; a.gate_words = gate ? gate_words : 0;
+}
+
+// the <GLOBAL, GATE> instantiation of kernel template K on cnt workgroups of HS_BLOCK lanes
+#define HS_LAUNCH(K, global, gated, cnt, lds, s, ...)                                             \
+  do {                                                                                            \
+    const dim3 g_(cnt), b_(HS_BLOCK);                                                             \
+    if (global && gated) hipLaunchKernelGGL((K<true, true>), g_, b_, lds, s, __VA_ARGS__);        \
+    else if (global) hipLaunchKernelGGL((K<true, false>), g_, b_, lds, s, __VA_ARGS__);           \
+    else if (gated) hipLaunchKernelGGL((K<false, true>), g_, b_, lds, s, __VA_ARGS__);            \
+    else hipLaunchKernelGGL((K<false, false>), g_, b_, lds, s, __VA_ARGS__);                      \
+  } while (0)
+
+// workspace of the binned entries: U per env, histogram + cursors of U, env ids by U, then the pool of the bins whose
+// DP does not fit in LDS beside `fixed` bytes (big_envs envs of the largest U a horizon of hb days can have)
 static size_t hs_fixed_bytes(int64_t n) { return 2 * align256(4 * (size_t)n) + 2 * align256(4 * HS_BINS); }
+
+static size_t hs_workspace_bytes(int64_t n, size_t fixed, uint32_t hb, int32_t max_remaining, int32_t big_envs) {
+  const uint32_t u = max_remaining <= 0 ? 0u : min((uint32_t)max_remaining, hb);
+  // the pool only for a U whose DP does not fit in LDS (a larger U than the batch's never occurs)
+  const bool pool = fixed + hs_dp_bytes(u, hb) > HS_LDS_CAP;
+  return hs_fixed_bytes(n) + (pool ? (size_t)big_envs * align256(hs_dp_bytes(u, hb)) : 0);
+}
+
+struct HsBins {  // the batch by U, on the host: envs per bin, every bin's first place in a.order; the pool
+  uint32_t hist[HS_BINS], off[HS_BINS];
+  char *pool;
+  size_t pool_bytes;
+};
+
+// binds the workspace to `a`, runs k_hs_plan and forms the bins. Bins that do not fit in LDS beside `fixed` bytes: the
+// pool must hold one env of the largest of them (pool_fmt: the entry's refusal; checked before any output is written:
+// k_hs_plan writes none). Then the cursor leaves for the entry's scatter.
+static int hs_bin(const char *fn, const char *pool_fmt, HsArgs &a, void *workspace, size_t workspace_bytes, size_t fixed,
+                  hipStream_t s, HsBins &b) {
+  char *ws = reinterpret_cast<char *>(workspace);
+  const int64_t n = a.n;
+  const uint32_t hb = (uint32_t)a.hb;
+  a.u_env = reinterpret_cast<uint32_t *>(ws);
+  a.order = reinterpret_cast<uint32_t *>(ws + align256(4 * (size_t)n));
+  a.hist = reinterpret_cast<uint32_t *>(ws + 2 * align256(4 * (size_t)n));
+  a.cursor = a.hist + HS_BINS;
+  b.pool = ws + hs_fixed_bytes(n);
+  b.pool_bytes = workspace_bytes - hs_fixed_bytes(n);
+  HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * HS_BINS, s));
+  hipLaunchKernelGGL(k_hs_plan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(b.hist, a.hist, 4 * (hb + 1), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  uint32_t acc = 0;
+  for (uint32_t u = 0; u <= hb; ++u) { b.off[u] = acc; acc += b.hist[u]; }
+  for (uint32_t u = 0; u <= hb; ++u)
+    if (b.hist[u] && fixed + hs_dp_bytes(u, hb) > HS_LDS_CAP && b.pool_bytes < align256(hs_dp_bytes(u, hb)))
+      return fail(W2A_ERR_ARG, pool_fmt, fn);
+  HIP_TRY(hipMemcpyAsync(a.cursor, b.off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
+  return W2A_OK;
+}
+
+// one launch per occupied bin: in LDS where `fixed` bytes and the bin's DP fit, else V and the decision words in the
+// pool, as many envs per launch as it holds. launch(global, cnt, lds, list, u, pool, stride) starts the entry's kernel.
+// (extern "C++": a template cannot have the C linkage of the block this file's host side sits in)
+extern "C++" template <class Launch>
+static int hs_launch_bins(const HsArgs &a, const HsBins &b, size_t fixed, hipStream_t s, Launch launch) {
+  const uint32_t hb = (uint32_t)a.hb;
+  for (uint32_t u = 0; u <= hb; ++u) {
+    if (!b.hist[u]) continue;
+    const size_t need = fixed + hs_dp_bytes(u, hb);
+    if (need <= HS_LDS_CAP) {
+      launch(false, b.hist[u], need, a.order + b.off[u], u, nullptr, (size_t)0);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    const size_t stride = align256(hs_dp_bytes(u, hb));
+    const size_t fit = b.pool_bytes / stride;
+    const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
+    for (uint32_t i = 0; i < b.hist[u]; i += per) {  // launches on one stream: each finds the pool free
+      launch(true, min(per, b.hist[u] - i), fixed, a.order + b.off[u] + i, u, b.pool, stride);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  // the cursor upload reads `off` from the entry's frame: it must have left before the entry returns
+  HIP_TRY(hipStreamSynchronize(s));
+  return W2A_OK;
+}
 
 size_t w2a_hindsight_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_remaining, int32_t big_envs) {
   if (!env || n_steps <= 0 || big_envs <= 0) return 0;
   const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
-  const uint32_t u = max_remaining <= 0 ? 0u : min((uint32_t)max_remaining, hb);
-  // the pool only for a U whose DP does not fit in LDS (a larger U than the batch's never occurs)
-  const bool pool = hs_day_bytes(hb) + hs_dp_bytes(u, hb) > HS_LDS_CAP;
-  return hs_fixed_bytes(env->n) + (pool ? (size_t)big_envs * align256(hs_dp_bytes(u, hb)) : 0);
+  return hs_workspace_bytes(env->n, hs_day_bytes(hb), hb, max_remaining, big_envs);
 }
 
 static int hindsight_optimum(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
@@ -901,136 +1052,40 @@ static int hindsight_optimum(const char *fn, w2a_env *env, const w2a_state_view 
                              const HsAlongArgs *along = nullptr) {
   // `along` (w2a_hindsight_along): the schedule to walk and the per-day outputs; ret_out is then the regret, alert_mask
   // the expert's bitmap, and alerts_out is not written
-  // what can be checked without the handle first (so that it is checked on any machine)
   if (!start || !ret_out || !alert_mask || (!alerts_out && !along) || !workspace || (along && (!along->sched || !along->gain)))
     return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
-  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
-      !start->year_i || !start->coef_col || !start->sample || !start->finished)
-    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
-                             "year_i, coef_col, sample and finished are read)", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
-                             "depends on attempts and on the 14-day window)", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  HS_CHECK(check_hs_start(fn, start, n_steps, true, mask_words));
+  HS_CHECK(check_hs_handle(fn, env, true, mask_words, "alert_mask needs ceil(T/32) words per env"));
+  HS_CHECK(check_hs_gate_capture(fn, env, gated, gate, gate_words, stream));
   const hipStream_t s = (hipStream_t)stream;
-  const int64_t n = env->n;
-  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
-  if (workspace_bytes < hs_fixed_bytes(n))
+  if (workspace_bytes < hs_fixed_bytes(env->n))
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_workspace_bytes(env, n_steps, "
                              "0, 1)", fn);
-  char *ws = reinterpret_cast<char *>(workspace);
-  {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
-    int32_t *flag = reinterpret_cast<int32_t *>(ws);
-    const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
-    HIP_TRY(hipGetLastError());
-    int32_t used27 = 1;
-    HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (used27)
-      return fail(W2A_ERR_ARG, "%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
-                               "agent): the (alerts, streak) DP would not be exact", fn);
-  }
+  HS_CHECK(hs_refuse_slot27(fn, env, workspace, s, "alerts"));
   HsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.mask_words = mask_words; a.n = n;
-  a.ret = ret_out; a.mask = alert_mask; a.alerts = alerts_out;
-  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
-  a.u_env = reinterpret_cast<uint32_t *>(ws);
-  a.order = reinterpret_cast<uint32_t *>(ws + align256(4 * (size_t)n));
-  a.hist = reinterpret_cast<uint32_t *>(ws + 2 * align256(4 * (size_t)n));
-  a.cursor = a.hist + HS_BINS;
-  char *pool = ws + hs_fixed_bytes(n);
-  const size_t pool_bytes = workspace_bytes - hs_fixed_bytes(n);
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * HS_BINS, s));
-  hipLaunchKernelGGL(k_hs_plan, dim3(grid), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  uint32_t hist[HS_BINS], off[HS_BINS];
-  HIP_TRY(hipMemcpyAsync(hist, a.hist, 4 * (hb + 1), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  uint32_t acc = 0;
-  for (uint32_t u = 0; u <= hb; ++u) { off[u] = acc; acc += hist[u]; }
-  // bins that do not fit in LDS: the pool must hold one env of the largest of them (checked before any output is
-  // written: k_hs_plan writes none)
-  for (uint32_t u = 0; u <= hb; ++u)
-    if (hist[u] && hs_day_bytes(hb) + hs_dp_bytes(u, hb) > HS_LDS_CAP && pool_bytes < align256(hs_dp_bytes(u, hb)))
-      return fail(W2A_ERR_ARG, "%s: workspace too small for the largest budget in the batch "
-                               "(w2a_hindsight_workspace_bytes(env, n_steps, max(budget - used), 1) suffices)", fn);
-  HIP_TRY(hipMemcpyAsync(a.cursor, off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
-  HsAlongArgs aa;
-  if (along) {
-    aa = *along;
-    aa.h = a;
-    hipLaunchKernelGGL(k_hs_along_scatter, dim3(grid), dim3(256), 0, s, aa);
-  } else {
+  HsBins b;
+  fill_hs_args(a, env, start, n_steps, ret_out, alert_mask, mask_words, alerts_out, gated ? gate : nullptr, gate_words);
+  const size_t fixed = hs_day_bytes((uint32_t)a.hb);
+  HS_CHECK(hs_bin(fn, "%s: workspace too small for the largest budget in the batch "
+                       "(w2a_hindsight_workspace_bytes(env, n_steps, max(budget - used), 1) suffices)",
+                   a, workspace, workspace_bytes, fixed, s, b));
+  const unsigned grid = (unsigned)((a.n + 255) / 256);
+  if (!along) {
     hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return hs_launch_bins(a, b, fixed, s, [&](bool global, uint32_t cnt, size_t lds, const uint32_t *list, uint32_t u,
+                                              char *pool, size_t stride) {
+      HS_LAUNCH(k_hs_dp, global, gated, cnt, lds, s, a, list, u, pool, stride);
+    });
   }
+  HsAlongArgs aa = *along;
+  aa.h = a;
+  hipLaunchKernelGGL(k_hs_along_scatter, dim3(grid), dim3(256), 0, s, aa);
   HIP_TRY(hipGetLastError());
-  for (uint32_t u = 0; u <= hb; ++u) {
-    if (!hist[u]) continue;
-    const size_t need = hs_day_bytes(hb) + hs_dp_bytes(u, hb);
-    if (along) {  // the same split between LDS and the pool, the same launches
-      if (need <= HS_LDS_CAP) {
-        if (gated)
-          hipLaunchKernelGGL((k_hs_along<false, true>), dim3(hist[u]), dim3(HS_BLOCK), need, s, aa, a.order + off[u], u, nullptr, (size_t)0);
-        else
-          hipLaunchKernelGGL((k_hs_along<false, false>), dim3(hist[u]), dim3(HS_BLOCK), need, s, aa, a.order + off[u], u, nullptr, (size_t)0);
-        HIP_TRY(hipGetLastError());
-        continue;
-      }
-      const size_t stride = align256(hs_dp_bytes(u, hb));
-      const size_t fit = pool_bytes / stride;
-      const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
-      for (uint32_t i = 0; i < hist[u]; i += per) {
-        const uint32_t cnt = min(per, hist[u] - i);
-        if (gated)
-          hipLaunchKernelGGL((k_hs_along<true, true>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, aa, a.order + off[u] + i, u,
-                             pool, stride);
-        else
-          hipLaunchKernelGGL((k_hs_along<true, false>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, aa, a.order + off[u] + i, u,
-                             pool, stride);
-        HIP_TRY(hipGetLastError());
-      }
-      continue;
-    }
-    if (need <= HS_LDS_CAP) {
-      if (gated)
-        hipLaunchKernelGGL((k_hs_dp<false, true>), dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
-      else
-        hipLaunchKernelGGL((k_hs_dp<false, false>), dim3(hist[u]), dim3(HS_BLOCK), need, s, a, a.order + off[u], u, nullptr, (size_t)0);
-      HIP_TRY(hipGetLastError());
-    } else {
-      const size_t stride = align256(hs_dp_bytes(u, hb));
-      const size_t fit = pool_bytes / stride;
-      const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
-      for (uint32_t i = 0; i < hist[u]; i += per) {
-        const uint32_t cnt = min(per, hist[u] - i);
-        if (gated)
-          hipLaunchKernelGGL((k_hs_dp<true, true>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, a, a.order + off[u] + i, u,
-                             pool, stride);
-        else
-          hipLaunchKernelGGL((k_hs_dp<true, false>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, a, a.order + off[u] + i, u,
-                             pool, stride);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-  }
-  // the cursor upload reads `off` from this frame: it must have left before the function returns
-  HIP_TRY(hipStreamSynchronize(s));
-  return W2A_OK;
+  return hs_launch_bins(a, b, fixed, s, [&](bool global, uint32_t cnt, size_t lds, const uint32_t *list, uint32_t u,
+                                            char *pool, size_t stride) {
+    HS_LAUNCH(k_hs_along, global, gated, cnt, lds, s, aa, list, u, pool, stride);
+  });
 }
 
 int w2a_hindsight_optimum(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
@@ -1067,18 +1122,7 @@ size_t w2a_hindsight_posterior_workspace_bytes(int64_t num_envs, int32_t T, int3
   const uint32_t hb = (uint32_t)min(n_steps, T);
   const size_t fixed = hs_pm_fixed_bytes(hb, (uint32_t)n_samples);
   if (fixed > HS_LDS_CAP) return 0;  // the entry refuses these tables
-  const uint32_t u = max_remaining <= 0 ? 0u : min((uint32_t)max_remaining, hb);
-  const bool pool = fixed + hs_dp_bytes(u, hb) > HS_LDS_CAP;
-  return hs_fixed_bytes(num_envs) + (pool ? (size_t)big_envs * align256(hs_dp_bytes(u, hb)) : 0);
-}
-
-static void launch_hs_pm(bool global, bool gated, uint32_t cnt, size_t lds, hipStream_t s, const HsArgs &a,
-                         const uint32_t *list, uint32_t u, char *pool, size_t stride) {
-  const dim3 g(cnt), b(HS_BLOCK);
-  if (global && gated) hipLaunchKernelGGL((k_hs_pm_dp<true, true>), g, b, lds, s, a, list, u, pool, stride);
-  else if (global) hipLaunchKernelGGL((k_hs_pm_dp<true, false>), g, b, lds, s, a, list, u, pool, stride);
-  else if (gated) hipLaunchKernelGGL((k_hs_pm_dp<false, true>), g, b, lds, s, a, list, u, pool, stride);
-  else hipLaunchKernelGGL((k_hs_pm_dp<false, false>), g, b, lds, s, a, list, u, pool, stride);
+  return hs_workspace_bytes(num_envs, fixed, hb, max_remaining, big_envs);
 }
 
 static int hindsight_posterior(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
@@ -1087,98 +1131,32 @@ static int hindsight_posterior(const char *fn, w2a_env *env, const w2a_state_vie
                                int32_t gate_words) {
   // w2a_hindsight_optimum's refusals in its order, the LDS room of the per-draw arrays after the semantics flags
   if (!start || !ret_out || !alert_mask || !alerts_out || !workspace) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
-  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
-      !start->year_i || !start->coef_col || !start->sample || !start->finished)
-    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
-                             "year_i, coef_col, sample and finished are read)", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if ((int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_mask needs ceil(T/32) words per env", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
-                             "depends on attempts and on the 14-day window)", fn);
-  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T), K = (uint32_t)env->tb.n_samples;
-  const size_t fixed = hs_pm_fixed_bytes(hb, K);
+  HS_CHECK(check_hs_start(fn, start, n_steps, true, mask_words));
+  HS_CHECK(check_hs_handle(fn, env, true, mask_words, "alert_mask needs ceil(T/32) words per env"));
+  const size_t fixed = hs_pm_fixed_bytes((uint32_t)min(n_steps, env->tb.T), (uint32_t)env->tb.n_samples);
   if (fixed > HS_LDS_CAP)
     return fail(W2A_ERR_ARG, "%s: the tables' n_samples is too large: 96 bytes per draw and 16 per day of the "
                              "stretch must fit in 64 KiB of LDS", fn);
   static_assert(HS_LDS_CAP == 64 * 1024, "the message above and include/w2a.h state the cap");
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  HS_CHECK(check_hs_gate_capture(fn, env, gated, gate, gate_words, stream));
   const hipStream_t s = (hipStream_t)stream;
-  const int64_t n = env->n;
-  if (workspace_bytes < hs_fixed_bytes(n))
+  if (workspace_bytes < hs_fixed_bytes(env->n))
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_posterior_workspace_bytes(num_envs, T, "
                              "n_samples, n_steps, 0, 1)", fn);
-  char *ws = reinterpret_cast<char *>(workspace);
-  {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
-    int32_t *flag = reinterpret_cast<int32_t *>(ws);
-    const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
-    HIP_TRY(hipGetLastError());
-    int32_t used27 = 1;
-    HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (used27)
-      return fail(W2A_ERR_ARG, "%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
-                               "agent): the (alerts, streak) DP would not be exact", fn);
-  }
+  HS_CHECK(hs_refuse_slot27(fn, env, workspace, s, "alerts"));
   HsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.mask_words = mask_words; a.n = n;
-  a.ret = ret_out; a.mask = alert_mask; a.alerts = alerts_out;
-  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
-  a.u_env = reinterpret_cast<uint32_t *>(ws);
-  a.order = reinterpret_cast<uint32_t *>(ws + align256(4 * (size_t)n));
-  a.hist = reinterpret_cast<uint32_t *>(ws + 2 * align256(4 * (size_t)n));
-  a.cursor = a.hist + HS_BINS;
-  char *pool = ws + hs_fixed_bytes(n);
-  const size_t pool_bytes = workspace_bytes - hs_fixed_bytes(n);
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * HS_BINS, s));
-  hipLaunchKernelGGL(k_hs_plan, dim3(grid), dim3(256), 0, s, a);
+  HsBins b;
+  fill_hs_args(a, env, start, n_steps, ret_out, alert_mask, mask_words, alerts_out, gated ? gate : nullptr, gate_words);
+  HS_CHECK(hs_bin(fn, "%s: workspace too small for the largest budget in the batch "
+                       "(w2a_hindsight_posterior_workspace_bytes(num_envs, T, n_samples, n_steps, "
+                       "max(budget - used), 1) suffices)",
+                   a, workspace, workspace_bytes, fixed, s, b));
+  hipLaunchKernelGGL(k_hs_scatter, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
   HIP_TRY(hipGetLastError());
-  uint32_t hist[HS_BINS], off[HS_BINS];
-  HIP_TRY(hipMemcpyAsync(hist, a.hist, 4 * (hb + 1), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  uint32_t acc = 0;
-  for (uint32_t u = 0; u <= hb; ++u) { off[u] = acc; acc += hist[u]; }
-  // bins that do not fit in LDS: the pool must hold one env of the largest of them (before any output is written)
-  for (uint32_t u = 0; u <= hb; ++u)
-    if (hist[u] && fixed + hs_dp_bytes(u, hb) > HS_LDS_CAP && pool_bytes < align256(hs_dp_bytes(u, hb)))
-      return fail(W2A_ERR_ARG, "%s: workspace too small for the largest budget in the batch "
-                               "(w2a_hindsight_posterior_workspace_bytes(num_envs, T, n_samples, n_steps, "
-                               "max(budget - used), 1) suffices)", fn);
-  HIP_TRY(hipMemcpyAsync(a.cursor, off, 4 * (hb + 1), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  for (uint32_t u = 0; u <= hb; ++u) {
-    if (!hist[u]) continue;
-    const size_t need = fixed + hs_dp_bytes(u, hb);
-    if (need <= HS_LDS_CAP) {
-      launch_hs_pm(false, gated, hist[u], need, s, a, a.order + off[u], u, nullptr, (size_t)0);
-      HIP_TRY(hipGetLastError());
-      continue;
-    }
-    const size_t stride = align256(hs_dp_bytes(u, hb));
-    const size_t fit = pool_bytes / stride;
-    const uint32_t per = fit < 0x7FFFFFFFu ? (uint32_t)fit : 0x7FFFFFFFu;
-    for (uint32_t i = 0; i < hist[u]; i += per) {  // launches on one stream: each finds the pool free
-      launch_hs_pm(true, gated, min(per, hist[u] - i), fixed, s, a, a.order + off[u] + i, u, pool, stride);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  // the cursor upload reads `off` from this frame: it must have left before the function returns
-  HIP_TRY(hipStreamSynchronize(s));
-  return W2A_OK;
+  return hs_launch_bins(a, b, fixed, s, [&](bool global, uint32_t cnt, size_t lds, const uint32_t *list, uint32_t u,
+                                            char *pool, size_t stride) {
+    HS_LAUNCH(k_hs_pm_dp, global, gated, cnt, lds, s, a, list, u, pool, stride);
+  });
 }
 
 int w2a_hindsight_posterior(w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
@@ -1213,28 +1191,13 @@ static int hindsight_curve(const char *fn, w2a_env *env, const w2a_state_view *s
   // w2a_hindsight_optimum's refusals in its order (alert_masks may be NULL: mask_words is then not read), max_budget
   // among what is checked without the handle
   if (!start || !ret_out || !alerts_out || !workspace) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
-  if (!start->t || !start->used || !start->streak || !start->budget || !start->n_days || !start->county_w ||
-      !start->year_i || !start->coef_col || !start->sample || !start->finished)
-    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, used, streak, budget, n_days, county_w, "
-                             "year_i, coef_col, sample and finished are read)", fn);
-  if (n_steps <= 0) return fail(W2A_ERR_ARG, "%s: n_steps must be positive", fn);
-  if (alert_masks && mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
+  HS_CHECK(check_hs_start(fn, start, n_steps, alert_masks != nullptr, mask_words));
   if (max_budget < 0 || max_budget > HC_MAX_BUDGET)
     return fail(W2A_ERR_ARG, "%s: max_budget must lie in 0..1023", fn);
   static_assert(HC_MAX_BUDGET == 1023, "the message above and include/w2a.h state the cap");
-  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
-  if (alert_masks && (int64_t)mask_words * 32 < env->tb.T)
-    return fail(W2A_ERR_ARG, "%s: alert_masks needs ceil(T/32) words per env and budget", fn);
-  if (env->tb.fixes)
-    return fail(W2A_ERR_ARG, "%s: not available with corrected-semantics flags (the reward then "
-                             "depends on attempts and on the 14-day window)", fn);
-  if (gated) {
-    const int grc = check_gate(fn, env, gate, gate_words);
-    if (grc != W2A_OK) return grc;
-  }
-  if (stream_is_capturing((hipStream_t)stream))
-    return fail(W2A_ERR_STATE, "%s: the stream is recording a hipGraph; only w2a_step can be recorded (episode "
-                               "boundaries inside a graph: W2A_STEP_AUTORESET)", fn);
+  HS_CHECK(check_hs_handle(fn, env, alert_masks != nullptr, mask_words,
+                            "alert_masks needs ceil(T/32) words per env and budget"));
+  HS_CHECK(check_hs_gate_capture(fn, env, gated, gate, gate_words, stream));
   const hipStream_t s = (hipStream_t)stream;
   const int64_t n = env->n;
   const uint32_t hb = (uint32_t)min(n_steps, env->tb.T), B = (uint32_t)max_budget;
@@ -1244,45 +1207,22 @@ static int hindsight_curve(const char *fn, w2a_env *env, const w2a_state_view *s
   if (workspace_bytes < hc_fixed_bytes() + (in_lds ? 0 : stride))
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_curve_workspace_bytes(env, n_steps, "
                              "max_budget, 1)", fn);
-  char *ws = reinterpret_cast<char *>(workspace);
-  {  // is the slot-27 coefficient zero in every row? (checked before any output is written)
-    int32_t *flag = reinterpret_cast<int32_t *>(ws);
-    const int64_t w_rows = (int64_t)env->tb.S * env->tb.n_samples * 2;
-    HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_hs_scan_slot27, dim3((unsigned)((w_rows + 255) / 256)), dim3(256), 0, s, env->tb.W, w_rows, flag);
-    HIP_TRY(hipGetLastError());
-    int32_t used27 = 1;
-    HIP_TRY(hipMemcpyAsync(&used27, flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (used27)
-      return fail(W2A_ERR_ARG, "%s: a coefficient row has a nonzero slot-27 term (alert_2wks of the "
-                               "agent): the (remaining, streak) DP would not be exact", fn);
-  }
+  HS_CHECK(hs_refuse_slot27(fn, env, workspace, s, "remaining"));
   if (n == 0) return W2A_OK;
   HcArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  HsArgs &a = ca.h;
-  a.tb = env->tb; a.st = *start; a.n_steps = n_steps; a.hb = (int32_t)hb; a.n = n;
-  a.ret = ret_out; a.alerts = alerts_out; a.mask = alert_masks; a.mask_words = alert_masks ? mask_words : 0;
-  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
+  fill_hs_args(ca.h, env, start, n_steps, ret_out, alert_masks, alert_masks ? mask_words : 0, alerts_out,
+               gated ? gate : nullptr, gate_words);
   ca.B = max_budget;
   if (in_lds) {
-    if (gated)
-      hipLaunchKernelGGL((k_hs_curve<false, true>), dim3((unsigned)n), dim3(HS_BLOCK), need, s, ca, 0u, nullptr, (size_t)0);
-    else
-      hipLaunchKernelGGL((k_hs_curve<false, false>), dim3((unsigned)n), dim3(HS_BLOCK), need, s, ca, 0u, nullptr, (size_t)0);
+    HS_LAUNCH(k_hs_curve, false, gated, (unsigned)n, need, s, ca, 0u, nullptr, (size_t)0);
     HIP_TRY(hipGetLastError());
     return W2A_OK;
   }
-  char *pool = ws + hc_fixed_bytes();
+  char *pool = reinterpret_cast<char *>(workspace) + hc_fixed_bytes();
   const size_t fit = (workspace_bytes - hc_fixed_bytes()) / stride;
   const uint32_t per = fit < (size_t)n ? (uint32_t)fit : (uint32_t)n;
   for (uint32_t i = 0; i < (uint32_t)n; i += per) {  // launches on one stream: each finds the pool free
-    const uint32_t cnt = min(per, (uint32_t)n - i);
-    if (gated)
-      hipLaunchKernelGGL((k_hs_curve<true, true>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, ca, i, pool, stride);
-    else
-      hipLaunchKernelGGL((k_hs_curve<true, false>), dim3(cnt), dim3(HS_BLOCK), hs_day_bytes(hb), s, ca, i, pool, stride);
+    HS_LAUNCH(k_hs_curve, true, gated, min(per, (uint32_t)n - i), hs_day_bytes(hb), s, ca, i, pool, stride);
     HIP_TRY(hipGetLastError());
   }
   return W2A_OK;
@@ -1302,6 +1242,8 @@ int w2a_hindsight_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t
   return hindsight_curve("w2a_hindsight_curve_gated", env, start, n_steps, max_budget, ret_out, alerts_out, alert_masks,
                          mask_words, workspace, workspace_bytes, stream, true, allowed_days, allowed_words);
 }
+#undef HS_LAUNCH
+#undef HS_CHECK
 
 int w2a_alert_gate(w2a_env *env, int32_t obs_col, float threshold, const float *thresholds, int32_t n_steps,
                    uint32_t *allowed_days, int32_t allowed_words, void *stream) {

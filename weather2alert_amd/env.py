@@ -1982,29 +1982,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
         another dtype or shape): the DP may alert only on allowed days, so the result is the best schedule UNDER the
         restriction -- the regret yardstick and the imitation expert of a policy with the same "allowed_days". Its
         return is still bit for bit what the env pays for that schedule."""
-        self._check_hindsight("hindsight_optimum()")
+        who = "hindsight_optimum()"
+        self._check_hindsight(who)
         ct, n, dev = self.ct, self.num_envs, self.device
-        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev,
-                                          "hindsight_optimum()")
-        if start_state is None:
-            st = self._state_packed(_HS_FIELDS)[1]
-        else:
-            st = {}
-            for k in _HS_FIELDS:
-                if k not in start_state:
-                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
-                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
-                if st[k].shape != (n,):
-                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
-        steps = int(n_steps) if n_steps is not None else ct.T
-        if steps <= 0:
-            raise ValueError("n_steps must be positive")
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=False)
         with torch.cuda.device(dev):
             ret, mask, alerts = self._hindsight_packed(st, steps, gate)
-        words = mask.shape[1]
-        bits = torch.arange(32, device=dev, dtype=torch.int32)
-        days = (((mask.unsqueeze(-1) >> bits) & 1).reshape(n, words * 32)[:, : ct.T]).bool()
-        return {"return": ret, "alert_days": days, "alerts": alerts}
+        return {"return": ret, "alert_days": _policy.unpack_alert_days(mask, ct.T), "alerts": alerts}
 
     def hindsight_posterior_optimum(self, start_state: dict | None = None, n_steps: int | None = None,
                                     allowed_days=None, share: bool = True, posterior_returns: bool = False) -> dict:
@@ -2041,19 +2027,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
             raise _ffi.W2AError(f"{who}: the stream is recording a hipGraph; the call finds the distinct problems and "
                                 "sizes its launches on the host")
         gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
-        if start_state is None:
-            st = self._state_packed(_HS_FIELDS)[1]
-        else:
-            st = {}
-            for k in _HS_FIELDS:
-                if k not in start_state:
-                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
-                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
-                if st[k].shape != (n,):
-                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
-        steps = int(n_steps) if n_steps is not None else ct.T
-        if steps <= 0:
-            raise ValueError("n_steps must be positive")
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=False)
         with torch.cuda.device(dev):
             if share and gate is None and n:
                 # one DP per distinct problem; a draw outside the tables keeps its own key (its answer is NaN)
@@ -2068,10 +2043,10 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 rep["finished"].fill_(1)
                 for k in _HS_FIELDS:
                     rep[k][:m] = st[k][first]
-                ret, mask, alerts = (x[:m][inv] for x in self._hindsight_posterior_packed(rep, steps, None))
+                ret, mask, alerts = (x[:m][inv] for x in self._hindsight_packed(rep, steps, None, posterior=True))
                 self.last_hindsight_posterior_keys = int(m)
             else:
-                ret, mask, alerts = self._hindsight_posterior_packed(st, steps, gate)
+                ret, mask, alerts = self._hindsight_packed(st, steps, gate, posterior=True)
                 self.last_hindsight_posterior_keys = n
         out = {"return": ret, "alert_days": _policy.unpack_alert_days(mask, ct.T), "alerts": alerts}
         if posterior_returns:
@@ -2111,21 +2086,8 @@ class HeatAlertVecEnv(_VectorEnvBase):
         ct, n, dev = self.ct, self.num_envs, self.device
         mask = _policy.check_schedule(alert_days, "alert_days", n, ct.T, dev, who)
         gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
-        if start_state is None:
-            st = self._state_packed(_HS_FIELDS)[1]
-        else:
-            st = {}
-            for k in _HS_FIELDS:
-                if k not in start_state:
-                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
-                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
-                if st[k].shape != (n,):
-                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
-        if n_steps is not None and (isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer))):
-            raise ValueError(f"{who}: n_steps must be an int, got {n_steps!r}")
-        steps = int(n_steps) if n_steps is not None else ct.T
-        if steps <= 0:
-            raise ValueError(f"{who}: n_steps must be positive")
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=True)
         words = mask.shape[1]
 
         def rows(fill):  # the library writes the first min(steps, T) call-days
@@ -2139,15 +2101,9 @@ class HeatAlertVecEnv(_VectorEnvBase):
         expert = torch.empty((n, words), dtype=torch.int32, device=dev)
         regret = torch.empty(n, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            live = (st["finished"] == 0) & (st["t"] < st["n_days"])
-            rem = 0
-            if n and not torch.cuda.is_current_stream_capturing():  # (a capture is refused by the library itself)
-                rem = int(torch.where(live, st["budget"] - st["used"], 0).max().item())
-            ws_bytes = self._lib.w2a_hindsight_workspace_bytes(self._h, steps, max(0, min(rem, 1 << 30)), _HS_BIG_ENVS)
+            ws_bytes = self._lib.w2a_hindsight_workspace_bytes(self._h, steps, self._hs_max_remaining(st), _HS_BIG_ENVS)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            v = _ffi.StateView()
-            for k in _HS_FIELDS:
-                setattr(v, k, st[k].data_ptr())
+            v = self._hs_state_view(st)
             _ffi.check(self._lib.w2a_hindsight_along(
                 self._h, C.byref(v), steps, mask.data_ptr(), words, None if gate is None else gate.data_ptr(),
                 0 if gate is None else int(gate.shape[1]), gain.data_ptr(), expert.data_ptr(), regret.data_ptr(),
@@ -2196,30 +2152,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
                                  f"{_CURVE_SCHEDULE_BYTES}; ask for fewer envs or budgets per call"
                                  + ("" if packed else ", or packed=True"))
         gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
-        if start_state is None:
-            st = self._state_packed(_HS_FIELDS)[1]
-        else:
-            st = {}
-            for k in _HS_FIELDS:
-                if k not in start_state:
-                    raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
-                st[k] = torch.as_tensor(start_state[k], device=dev).to(torch.int32).contiguous()
-                if st[k].shape != (n,):
-                    raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
-        if n_steps is not None and (isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer))):
-            raise ValueError(f"{who}: n_steps must be an int, got {n_steps!r}")
-        steps = int(n_steps) if n_steps is not None else ct.T
-        if steps <= 0:
-            raise ValueError(f"{who}: n_steps must be positive")
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=True)
         ret = torch.empty((n, B + 1), dtype=torch.float32, device=dev)
         alerts = torch.empty((n, B + 1), dtype=torch.int32, device=dev)
         masks = torch.empty((n, B + 1, words), dtype=torch.int32, device=dev) if schedules else None
         with torch.cuda.device(dev):
             ws_bytes = self._lib.w2a_hindsight_curve_workspace_bytes(self._h, steps, B, _HS_BIG_ENVS)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            v = _ffi.StateView()
-            for k in _HS_FIELDS:
-                setattr(v, k, st[k].data_ptr())
+            v = self._hs_state_view(st)
             args = (self._h, C.byref(v), steps, B, ret.data_ptr(), alerts.data_ptr(),
                     None if masks is None else masks.data_ptr(), words, ws.data_ptr(), ws_bytes, self._stream())
             if gate is None:
@@ -2254,57 +2195,65 @@ class HeatAlertVecEnv(_VectorEnvBase):
             raise ValueError(f"{who}: some coefficient row has a nonzero slot-27 (alert_2wks of the agent) term; the "
                              "(alerts, streak) DP is exact only without it")
 
-    def _hindsight_packed(self, st0: dict, steps: int, gate=None):
-        """w2a_hindsight_optimum on device int32 state arrays: (return f32 [N], packed bitmap i32 [N, words],
-        alerts i32 [N]). gate: packed allowed days, int32 [N, words] (w2a_hindsight_optimum_gated)."""
-        n, dev = self.num_envs, self.device
-        words = (self.ct.T + 31) // 32
-        ret = torch.empty(n, dtype=torch.float32, device=dev)
-        mask = torch.empty((n, words), dtype=torch.int32, device=dev)
-        alerts = torch.empty(n, dtype=torch.int32, device=dev)
-        # one host reduction: the pool for DPs beyond LDS is sized for the batch's largest remaining budget (none at
-        # the tables' default budgets)
-        live = (st0["finished"] == 0) & (st0["t"] < st0["n_days"])
-        rem = 0
-        if n and not torch.cuda.is_current_stream_capturing():  # (a capture is refused by the library itself)
-            rem = int(torch.where(live, st0["budget"] - st0["used"], 0).max().item())
-        ws_bytes = self._lib.w2a_hindsight_workspace_bytes(self._h, steps, max(0, min(rem, 1 << 30)), _HS_BIG_ENVS)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    def _hs_start_state(self, start_state: dict | None) -> dict:
+        """start_state (a state() dict; None: the current state) as the int32 [N] device arrays of _HS_FIELDS"""
+        if start_state is None:
+            return self._state_packed(_HS_FIELDS)[1]
+        n, st = self.num_envs, {}
+        for k in _HS_FIELDS:
+            if k not in start_state:
+                raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
+            st[k] = torch.as_tensor(start_state[k], device=self.device).to(torch.int32).contiguous()
+            if st[k].shape != (n,):
+                raise ValueError(f"start_state[{k!r}] must have shape ({n},)")
+        return st
+
+    def _hs_steps(self, n_steps, who: str, strict: bool) -> int:
+        """n_steps (None: to the end of every episode) as a positive int; strict refuses what is not an integer
+        (hindsight_optimum() and hindsight_posterior_optimum() take what int() takes)"""
+        if strict and n_steps is not None and (isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer))):
+            raise ValueError(f"{who}: n_steps must be an int, got {n_steps!r}")
+        steps = int(n_steps) if n_steps is not None else self.ct.T
+        if steps <= 0:
+            raise ValueError(f"{who}: n_steps must be positive")
+        return steps
+
+    def _hs_max_remaining(self, st: dict) -> int:
+        """the largest remaining budget of a live env, as the *_workspace_bytes functions take it: one host reduction
+        that sizes the pool of the DPs beyond LDS (none at the tables' default budgets). 0 under a stream capture, which
+        the library itself refuses (hindsight_posterior_optimum() has refused it before it gets here)"""
+        if not self.num_envs or torch.cuda.is_current_stream_capturing():
+            return 0
+        live = (st["finished"] == 0) & (st["t"] < st["n_days"])
+        return max(0, min(int(torch.where(live, st["budget"] - st["used"], 0).max().item()), 1 << 30))
+
+    @staticmethod
+    def _hs_state_view(st: dict):
         v = _ffi.StateView()
         for k in _HS_FIELDS:
-            setattr(v, k, st0[k].data_ptr())
-        hs_args = (self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words, alerts.data_ptr(), ws.data_ptr(),
-                   ws_bytes, self._stream())
-        if gate is None:
-            _ffi.check(self._lib.w2a_hindsight_optimum(*hs_args), "w2a_hindsight_optimum")
-        else:
-            _ffi.check(self._lib.w2a_hindsight_optimum_gated(*hs_args, gate.data_ptr(), int(gate.shape[1])),
-                       "w2a_hindsight_optimum_gated")
-        return ret, mask, alerts
+            setattr(v, k, st[k].data_ptr())
+        return v
 
-    def _hindsight_posterior_packed(self, st0: dict, steps: int, gate=None):
-        """w2a_hindsight_posterior on device int32 state arrays: (return f32 [N], packed bitmap i32 [N, words],
-        alerts i32 [N]), as _hindsight_packed."""
+    def _hindsight_packed(self, st0: dict, steps: int, gate=None, posterior: bool = False):
+        """w2a_hindsight_optimum (posterior: w2a_hindsight_posterior) on device int32 state arrays: (return f32 [N],
+        packed bitmap i32 [N, words], alerts i32 [N]). gate: packed allowed days, int32 [N, words] (the _gated entry)."""
         n, dev, ct = self.num_envs, self.device, self.ct
         words = (ct.T + 31) // 32
         ret = torch.empty(n, dtype=torch.float32, device=dev)
         mask = torch.empty((n, words), dtype=torch.int32, device=dev)
         alerts = torch.empty(n, dtype=torch.int32, device=dev)
-        live = (st0["finished"] == 0) & (st0["t"] < st0["n_days"])
-        rem = int(torch.where(live, st0["budget"] - st0["used"], 0).max().item()) if n else 0
-        ws_bytes = self._lib.w2a_hindsight_posterior_workspace_bytes(n, ct.T, ct.n_samples, steps,
-                                                                    max(0, min(rem, 1 << 30)), _HS_BIG_ENVS)
-        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)  # (0: the entry refuses, with its message)
-        v = _ffi.StateView()
-        for k in _HS_FIELDS:
-            setattr(v, k, st0[k].data_ptr())
-        hs_args = (self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words, alerts.data_ptr(), ws.data_ptr(),
-                   ws_bytes, self._stream())
-        if gate is None:
-            _ffi.check(self._lib.w2a_hindsight_posterior(*hs_args), "w2a_hindsight_posterior")
+        rem = self._hs_max_remaining(st0)
+        if posterior:
+            ws_bytes = self._lib.w2a_hindsight_posterior_workspace_bytes(n, ct.T, ct.n_samples, steps, rem, _HS_BIG_ENVS)
         else:
-            _ffi.check(self._lib.w2a_hindsight_posterior_gated(*hs_args, gate.data_ptr(), int(gate.shape[1])),
-                       "w2a_hindsight_posterior_gated")
+            ws_bytes = self._lib.w2a_hindsight_workspace_bytes(self._h, steps, rem, _HS_BIG_ENVS)
+        # (0 bytes, the posterior's answer for tables it cannot take: the entry refuses, with its message)
+        ws = torch.empty(max(ws_bytes, 256) if posterior else ws_bytes, dtype=torch.uint8, device=dev)
+        v = self._hs_state_view(st0)
+        name = ("w2a_hindsight_posterior" if posterior else "w2a_hindsight_optimum") + ("" if gate is None else "_gated")
+        tail = () if gate is None else (gate.data_ptr(), int(gate.shape[1]))
+        _ffi.check(getattr(self._lib, name)(self._h, C.byref(v), steps, ret.data_ptr(), mask.data_ptr(), words,
+                                            alerts.data_ptr(), ws.data_ptr(), ws_bytes, self._stream(), *tail), name)
         return ret, mask, alerts
 
     # ------------------------------------------------------------------ alert gate
