@@ -1327,6 +1327,45 @@ int w2a_hindsight_posterior_gated(w2a_env *env, const w2a_state_view *start, int
                                   size_t workspace_bytes, void *stream, const uint32_t *allowed_days,
                                   int32_t allowed_words);
 
+/* Draw-blind hindsight values along a GIVEN schedule (additions to ABI 18, nothing above changes): what the DP of
+ * w2a_hindsight_posterior says in the states a caller's schedule reaches, not only on its own optimal path -- DAgger
+ * labels that are functions of what a policy sees, and every day's share of the regret against the bound a policy can
+ * reach. w2a_hindsight_along's job on w2a_hindsight_posterior's reward: the walk, the attempts (an attempt on a closed
+ * day is 0 before the budget test; an attempt with used + j == budget issues nothing), the outputs, their shapes and
+ * their fills are w2a_hindsight_along's, with
+ *     Q0 = m_0 + V_{d+1}(j, 0),    Q1 = m_1 + V_{d+1}(j + 1, streak + 1)   (Q1 only while used + j < budget on an allowed day)
+ * and m_a the draw-mean of w2a_hindsight_posterior: the fp64 sum of the f32 rewards over the draws in draw order,
+ * divided by (double) n_samples.
+ *   start, n_steps, alert_mask, mask_words, allowed_days, allowed_words   as w2a_hindsight_along; `sample` is only
+ *                range-checked, the outputs do not depend on it
+ *   gain_out     device f32 [min(n_steps, T)][num_envs] by call-day and ENV ID: (float)(Q1 - Q0); NaN where no alert is
+ *                possible that day and on call-days s >= H
+ *   expert_mask  device u32 [num_envs][mask_words]: bit t + s is set iff Q1 > Q0 in fp64
+ *   regret_out   device f32 [num_envs]: the fp64 sum, in day order, of V_d(state) - Q_{a_s}, a_s the alert ISSUED on
+ *                call-day s, rounded once: w2a_hindsight_posterior's optimum from `start` less the schedule's
+ *                posterior-mean return
+ *   value_out    nullable f32 [min(n_steps, T)][num_envs]: (float)V_d(state) = max(Q0, Q1); 0 for s >= H
+ *   loss_out     nullable f32 [min(n_steps, T)][num_envs]: (float)(V_d(state) - Q_{a_s}) >= 0, exactly +0 where the
+ *                alert issued is the expert's bit; 0 for s >= H
+ *   workspace    as w2a_hindsight_posterior: w2a_hindsight_posterior_workspace_bytes(num_envs, T, n_samples, n_steps,
+ *                max_remaining, 1) bytes. The day's fp64 loss takes the room of the day's slots 28 and 29 once they
+ *                have been read, so LDS, the split between LDS and the pool and the largest n_samples are that call's
+ * Envs finished on entry (or with t >= n_days) get 0, NaN gains and an empty bitmap; a start state outside the tables
+ * gives NaN in every float output and an empty bitmap.
+ * Numerics contract: the backward sweep is w2a_hindsight_posterior's, statement for statement (one device function),
+ * so along that call's own schedule expert_mask is the schedule, every loss is +0 and the regret is +0; with
+ * n_samples = 1 every output is w2a_hindsight_along's bit for bit (0.0 + (double) r and x / 1.0 are exact); the
+ * values of a state do not depend on the start the DP was run from, so rows s >= k equal the rows of a call from the
+ * state reached after k days, bit for bit. One lane writes each output, the regret is added by one lane in day order,
+ * and there are no atomics: identical calls give identical bits.
+ * Synchronises `stream` and refuses as w2a_hindsight_posterior, in its order (NULL alert_mask, gain_out, expert_mask or
+ * regret_out among the NULL arguments; every refusal before any output is written); reads the tables and the caller's
+ * arrays only. Sampled and posterior-mean handles alike. */
+int w2a_hindsight_posterior_along(w2a_env *env, const w2a_state_view *start, int32_t n_steps, const uint32_t *alert_mask,
+                                  int32_t mask_words, const uint32_t *allowed_days, int32_t allowed_words,
+                                  float *gain_out, uint32_t *expert_mask, float *regret_out, float *value_out,
+                                  float *loss_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,7 @@ SYMBOLS = [
     "w2a_hindsight_along", "w2a_relabel_imitation_linear", "w2a_relabel_imitation_mlp",
     "w2a_hindsight_curve_workspace_bytes", "w2a_hindsight_curve", "w2a_hindsight_curve_gated",
     "w2a_hindsight_posterior_workspace_bytes", "w2a_hindsight_posterior", "w2a_hindsight_posterior_gated",
+    "w2a_hindsight_posterior_along",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -348,6 +349,9 @@ def load(build_if_missing: bool = True):
     lib.w2a_hindsight_posterior.argtypes = lib.w2a_hindsight_optimum.argtypes
     lib.w2a_hindsight_posterior_gated.restype = C.c_int
     lib.w2a_hindsight_posterior_gated.argtypes = lib.w2a_hindsight_optimum.argtypes + gate
+    # its values along a schedule: w2a_hindsight_along's arguments, w2a_hindsight_posterior's workspace
+    lib.w2a_hindsight_posterior_along.restype = C.c_int
+    lib.w2a_hindsight_posterior_along.argtypes = lib.w2a_hindsight_along.argtypes
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

@@ -883,7 +883,7 @@ int w2a_posterior_returns(w2a_env *env, const w2a_state_view *start, const uint3
 }
 
 // ----------------------------------------------------------------------------------------
-// hindsight family: w2a_hindsight_optimum / _along, w2a_hindsight_posterior, w2a_hindsight_curve
+// hindsight family: w2a_hindsight_optimum / _along, w2a_hindsight_posterior / _along, w2a_hindsight_curve
 // ----------------------------------------------------------------------------------------
 // What the three bodies share is written once, in the manner of w2a_policy_dispatch.hip.h: check_hs_* (the refusals, in
 // the order every entry reports them), hs_refuse_slot27, fill_hs_args, hs_bin (plan -> histogram -> prefix sum -> pool
@@ -1128,9 +1128,11 @@ size_t w2a_hindsight_posterior_workspace_bytes(int64_t num_envs, int32_t T, int3
 static int hindsight_posterior(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, float *ret_out,
                                uint32_t *alert_mask, int32_t mask_words, int32_t *alerts_out, void *workspace,
                                size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate,
-                               int32_t gate_words) {
-  // w2a_hindsight_optimum's refusals in its order, the LDS room of the per-draw arrays after the semantics flags
-  if (!start || !ret_out || !alert_mask || !alerts_out || !workspace) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
+                               int32_t gate_words, const HsAlongArgs *along = nullptr) {
+  // w2a_hindsight_optimum's refusals in its order, the LDS room of the per-draw arrays after the semantics flags.
+  // `along` (w2a_hindsight_posterior_along): as in hindsight_optimum()
+  if (!start || !ret_out || !alert_mask || (!alerts_out && !along) || !workspace || (along && (!along->sched || !along->gain)))
+    return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
   HS_CHECK(check_hs_start(fn, start, n_steps, true, mask_words));
   HS_CHECK(check_hs_handle(fn, env, true, mask_words, "alert_mask needs ceil(T/32) words per env"));
   const size_t fixed = hs_pm_fixed_bytes((uint32_t)min(n_steps, env->tb.T), (uint32_t)env->tb.n_samples);
@@ -1151,11 +1153,22 @@ static int hindsight_posterior(const char *fn, w2a_env *env, const w2a_state_vie
                        "(w2a_hindsight_posterior_workspace_bytes(num_envs, T, n_samples, n_steps, "
                        "max(budget - used), 1) suffices)",
                    a, workspace, workspace_bytes, fixed, s, b));
-  hipLaunchKernelGGL(k_hs_scatter, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+  const unsigned grid = (unsigned)((a.n + 255) / 256);
+  if (!along) {
+    hipLaunchKernelGGL(k_hs_scatter, dim3(grid), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return hs_launch_bins(a, b, fixed, s, [&](bool global, uint32_t cnt, size_t lds, const uint32_t *list, uint32_t u,
+                                              char *pool, size_t stride) {
+      HS_LAUNCH(k_hs_pm_dp, global, gated, cnt, lds, s, a, list, u, pool, stride);
+    });
+  }
+  HsAlongArgs aa = *along;
+  aa.h = a;
+  hipLaunchKernelGGL(k_hs_along_scatter, dim3(grid), dim3(256), 0, s, aa);
   HIP_TRY(hipGetLastError());
   return hs_launch_bins(a, b, fixed, s, [&](bool global, uint32_t cnt, size_t lds, const uint32_t *list, uint32_t u,
                                             char *pool, size_t stride) {
-    HS_LAUNCH(k_hs_pm_dp, global, gated, cnt, lds, s, a, list, u, pool, stride);
+    HS_LAUNCH(k_hs_pm_along, global, gated, cnt, lds, s, aa, list, u, pool, stride);
   });
 }
 
@@ -1172,6 +1185,18 @@ int w2a_hindsight_posterior_gated(w2a_env *env, const w2a_state_view *start, int
                                   int32_t allowed_words) {
   return hindsight_posterior("w2a_hindsight_posterior_gated", env, start, n_steps, ret_out, alert_mask, mask_words,
                              alerts_out, workspace, workspace_bytes, stream, true, allowed_days, allowed_words);
+}
+
+int w2a_hindsight_posterior_along(w2a_env *env, const w2a_state_view *start, int32_t n_steps, const uint32_t *alert_mask,
+                                  int32_t mask_words, const uint32_t *allowed_days, int32_t allowed_words,
+                                  float *gain_out, uint32_t *expert_mask, float *regret_out, float *value_out,
+                                  float *loss_out, void *workspace, size_t workspace_bytes, void *stream) {
+  HsAlongArgs along;
+  memset(&along, 0, sizeof(along));
+  along.sched = alert_mask; along.gain = gain_out; along.value = value_out; along.loss = loss_out;
+  return hindsight_posterior("w2a_hindsight_posterior_along", env, start, n_steps, regret_out, expert_mask, mask_words,
+                             nullptr, workspace, workspace_bytes, stream, allowed_days != nullptr, allowed_days,
+                             allowed_words, &along);
 }
 
 // workspace of w2a_hindsight_curve: the slot-27 flag, then the pool when the DP of max_budget does not fit in LDS

@@ -2031,18 +2031,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         steps = self._hs_steps(n_steps, who, strict=False)
         with torch.cuda.device(dev):
             if share and gate is None and n:
-                # one DP per distinct problem; a draw outside the tables keeps its own key (its answer is NaN)
-                key = torch.stack([st[k] for k in _HS_FIELDS if k != "sample"] +
-                                  [((st["sample"] < 0) | (st["sample"] >= ct.n_samples)).to(torch.int32)], dim=1)
-                uniq, inv = torch.unique(key, dim=0, return_inverse=True)
-                m = uniq.shape[0]
-                first = torch.full((m,), n, dtype=torch.int64, device=dev)
-                first.scatter_reduce_(0, inv, torch.arange(n, device=dev), reduce="amin")  # the lowest env id per key
-                # the library runs num_envs entries: the representatives first, the rest marked finished (no DP)
-                rep = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in _HS_FIELDS}
-                rep["finished"].fill_(1)
-                for k in _HS_FIELDS:
-                    rep[k][:m] = st[k][first]
+                rep, inv, _, m = self._hs_posterior_share(st)
                 ret, mask, alerts = (x[:m][inv] for x in self._hindsight_packed(rep, steps, None, posterior=True))
                 self.last_hindsight_posterior_keys = int(m)
             else:
@@ -2115,6 +2104,111 @@ class HeatAlertVecEnv(_VectorEnvBase):
         if loss:
             out["loss"] = los
         return out
+
+    def hindsight_posterior_values(self, alert_days, start_state: dict | None = None, n_steps: int | None = None,
+                                   allowed_days=None, value: bool = False, loss: bool = False,
+                                   share: bool = True) -> dict:
+        """hindsight_values() with THE DRAW UNKNOWN: what hindsight_posterior_optimum()'s DP says in the states a GIVEN
+        schedule reaches. The draw-blind expert's action on every day of a learner's own rollout -- DAgger labels that
+        are functions of what a policy sees (imitation_gradient(labels=...), examples/dagger_draw_blind.py) -- and each
+        day's share of the regret against the bound a policy can reach. alert_days, start_state, n_steps (an int),
+        allowed_days, value and loss as hindsight_values(); the keys, the [S, N] shapes by call-day and the fills (NaN
+        gains and 0 for s >= H_e and beyond T, 0 / NaN gains / no bits for finished envs, NaN for a start outside the
+        tables) are that call's too, with Q0 = m0 + V(no alert), Q1 = m1 + V(alert) and m the reward averaged over all
+        n_samples draws of the env's coefficient column in fp64, in draw order:
+            "alert_gain"         f32 [S, N]  Q1 - Q0; NaN where no alert is possible
+            "expert_alert_days"  bool [N, T] day t0 + s is set iff Q1 > Q0
+            "regret"             f32 [N]     the fp64 sum over the env's days of V(state) - Q(issued alert):
+                                             hindsight_posterior_optimum()'s return from start_state less the
+                                             schedule's posterior-mean return
+            "value"  (value=True) f32 [S, N] V(state) = max(Q0, Q1)
+            "loss"   (loss=True)  f32 [S, N] V(state) - Q(issued alert) >= 0, exactly 0 where the alert issued is the
+                                             expert's
+        Along hindsight_posterior_optimum()'s own schedule the expert bits are the schedule and every loss and the
+        regret are 0; with n_samples = 1 every output is hindsight_values()'s bit for bit. The result does not depend on
+        `sample`. share=True (the default) runs one env of each set that agrees on the problem (the fields
+        hindsight_posterior_optimum() shares on) AND on the packed schedule words, and gathers the columns back -- bit
+        for bit what share=False returns; last_hindsight_posterior_keys is the number run. A sampled learner's
+        schedules differ from env to env, so it shares next to nothing; a deterministic learner's schedule is a function
+        of the problem and shares as the optimum does. With allowed_days nothing is shared.
+        Sampled and posterior_mean envs alike; refuses what hindsight_posterior_optimum() refuses (corrected-semantics
+        fixes, slot-27 tables, a stream capture, an n_samples beyond the kernel's per-draw arrays) before anything is
+        written. Reads start_state, the tables and the schedule only: the env's state, observation buffer and
+        bookkeeping are untouched. w2a_hindsight_posterior_along (include/w2a.h)."""
+        who = "hindsight_posterior_values()"
+        self._check_hindsight_fixes(who)
+        self._check_hindsight_slot27(who)
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _ffi.W2AError(f"{who}: the stream is recording a hipGraph; the call finds the distinct problems and "
+                                "sizes its launches on the host")
+        mask = _policy.check_schedule(alert_days, "alert_days", n, ct.T, dev, who)
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=True)
+        words = mask.shape[1]
+        inv = None
+        if share and gate is None and n:
+            # the representatives first with their own schedules, the rest marked finished (no DP)
+            st, inv, first, m = self._hs_posterior_share(st, mask)
+            sched = torch.zeros_like(mask)
+            sched[:m] = mask[first]
+            mask = sched
+
+        def rows(fill):  # the library writes the first min(steps, T) call-days
+            if steps > ct.T:
+                return torch.full((steps, n), fill, dtype=torch.float32, device=dev)
+            return torch.empty((steps, n), dtype=torch.float32, device=dev)
+
+        gain = rows(float("nan"))
+        val = rows(0.0) if value else None
+        los = rows(0.0) if loss else None
+        expert = torch.empty((n, words), dtype=torch.int32, device=dev)
+        regret = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws_bytes = self._lib.w2a_hindsight_posterior_workspace_bytes(n, ct.T, ct.n_samples, steps,
+                                                                         self._hs_max_remaining(st), _HS_BIG_ENVS)
+            # (0 bytes: tables the entry refuses, with its message)
+            ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+            v = self._hs_state_view(st)
+            _ffi.check(self._lib.w2a_hindsight_posterior_along(
+                self._h, C.byref(v), steps, mask.data_ptr(), words, None if gate is None else gate.data_ptr(),
+                0 if gate is None else int(gate.shape[1]), gain.data_ptr(), expert.data_ptr(), regret.data_ptr(),
+                None if val is None else val.data_ptr(), None if los is None else los.data_ptr(), ws.data_ptr(),
+                ws_bytes, self._stream()), "w2a_hindsight_posterior_along")
+        self.last_hindsight_posterior_keys = n if inv is None else int(m)
+        if inv is not None:  # rows beyond T keep their fill in every column
+            gain, expert, regret = gain[:, :m][:, inv], expert[:m][inv], regret[:m][inv]
+            val = None if val is None else val[:, :m][:, inv]
+            los = None if los is None else los[:, :m][:, inv]
+        out = {"alert_gain": gain, "expert_alert_days": _policy.unpack_alert_days(expert, ct.T), "regret": regret}
+        if value:
+            out["value"] = val
+        if loss:
+            out["loss"] = los
+        return out
+
+    def _hs_posterior_share(self, st: dict, sched=None):
+        """The distinct problems of the draw-blind DP, found on the host: envs that agree on every _HS_FIELDS array
+        but `sample` (a draw outside the tables keeps its own key: its answer is NaN) and, with sched (int32
+        [N, words]), on their packed schedule words. Returns (rep, inv, first, m): rep the state arrays the library
+        runs -- num_envs entries, the m representatives (the lowest env id of each key, `first`) in front and the rest
+        marked finished (no DP) -- and inv the key of every env, so that x[:m][inv] gathers a per-env output back."""
+        n, dev = st["t"].shape[0], st["t"].device
+        cols = [st[k] for k in _HS_FIELDS if k != "sample"] + \
+               [((st["sample"] < 0) | (st["sample"] >= self.ct.n_samples)).to(torch.int32)]
+        key = torch.stack(cols, dim=1)
+        if sched is not None:
+            key = torch.cat([key, sched.to(torch.int32)], dim=1)
+        uniq, inv = torch.unique(key, dim=0, return_inverse=True)
+        m = uniq.shape[0]
+        first = torch.full((m,), n, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(0, inv, torch.arange(n, device=dev), reduce="amin")  # the lowest env id per key
+        rep = {k: torch.zeros(n, dtype=torch.int32, device=dev) for k in _HS_FIELDS}
+        rep["finished"].fill_(1)
+        for k in _HS_FIELDS:
+            rep[k][:m] = st[k][first]
+        return rep, inv, first, m
 
     def hindsight_budget_curve(self, max_budget: int, start_state: dict | None = None, n_steps: int | None = None,
                                allowed_days=None, schedules: bool = False, packed: bool = False) -> dict:
