@@ -5,8 +5,13 @@ batch's own total number of alerts over counties that maximises the summed curve
 tables' default budgets: first the hindsight value of both, then the regret of the same threshold policy rolled out
 under each.
 
-    python examples/budget_allocation.py            # needs one ROCm GPU
+--draw-blind: the split is decided before anyone knows which posterior draw a county's episode gets, so it also
+allocates from the draw-blind curves (hindsight_posterior_budget_curve: the optimum of the reward averaged over all
+draws) and prints both allocations and their values under the draw-mean, read off the draw-blind curves.
+
+    python examples/budget_allocation.py [--draw-blind]           # needs one ROCm GPU
 """
+import argparse
 import os
 import sys
 
@@ -15,6 +20,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from weather2alert_amd import HeatAlertVecEnv, compile_from_synth, stats, synth
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--draw-blind", action="store_true")
+args = ap.parse_args()
 
 data = synth.make_synth("linear", n_fips=64, years=[2006, 2007, 2008], n_samples=100, seed=0, extra_confounder_fips=6)
 tables = compile_from_synth(data)
@@ -51,6 +60,26 @@ v_new = curve["return"][rows, new.long()].double().mean().item()
 assert abs(v_new * n - alloc["value"]) <= 1e-6 * abs(alloc["value"]) and alloc["spent"] <= total
 print(f"hindsight value per episode: default budgets {v_def:.3f}, allocated {v_new:.3f} "
       f"({alloc['spent']} of {total} alerts spent)")
+
+# 4b. the same split from the draw-blind curves, and all three splits scored under the draw-mean
+if args.draw_blind:
+    blind = env.hindsight_posterior_budget_curve(B, start_state=st0)
+    assert torch.equal(blind["own_budget"], own)
+    by_b = stats.budget_curve_by_group(blind["return"], county, tables.S_w)
+    alloc_b = stats.allocate_budget(by_b["curve"], total, group_size=by_b["count"])
+    new_b = alloc_b["budget"].to(env.device)[county].to(torch.int32)
+    print(f"draw-blind curves: {env.last_hindsight_posterior_keys} distinct problems among {n} episodes")
+    print("county budgets, own-draw allocation -> draw-blind allocation:")
+    print("  " + "  ".join(f"{int(alloc['budget'][g])}->{int(alloc_b['budget'][g])}" for g in range(tables.S_w)
+                          if int(by["count"][g])))
+    moved = int((alloc["budget"] != alloc_b["budget"])[(by["count"] > 0).cpu()].sum())
+    print(f"{moved} of {int((by['count'] > 0).sum())} counties get another budget")
+    for name, bud in (("default", own), ("own-draw allocation", new), ("draw-blind allocation", new_b)):
+        v = blind["return"][rows, bud.long()].double().mean().item()
+        print(f"draw-mean value per episode, {name:22s}: {v:9.3f} ({int(bud.sum())} alerts)")
+    v_b = blind["return"][rows, new_b.long()].double().mean().item()
+    assert abs(v_b * n - alloc_b["value"]) <= 1e-6 * abs(alloc_b["value"]) and alloc_b["spent"] <= total
+    assert v_b >= blind["return"][rows, new.long()].double().mean().item() - 1e-9  # the optimum of these curves
 
 # 5. the same threshold policy under each split: its return, and its regret against the curve's column
 policy = {"kind": "threshold", "feature": "heat_qi", "threshold": 0.9, "require_budget": True}

@@ -1366,6 +1366,49 @@ int w2a_hindsight_posterior_along(w2a_env *env, const w2a_state_view *start, int
                                   float *gain_out, uint32_t *expert_mask, float *regret_out, float *value_out,
                                   float *loss_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The draw-blind hindsight budget curve (additions to ABI 18, nothing above changes): w2a_hindsight_posterior for EVERY
+ * remaining budget b = 0 .. max_budget at once -- the return-versus-budget curves of a decision that is taken before
+ * anyone knows which posterior draw an episode will get. w2a_hindsight_curve's job on w2a_hindsight_posterior's
+ * reward: the states (r = alerts remaining, s = the streak), the recurrence
+ *     V_d(r, s) = max( m_0 + V_{d+1}(r, 0),  m_1 + V_{d+1}(r - 1, s + 1) ),  V_H = 0,  the alert only while r > 0,
+ * the (max_budget + 1)(max_budget + 2) states per day and the strict comparison are w2a_hindsight_curve's, and m_a is
+ * the draw-mean of w2a_hindsight_posterior: the fp64 sum over the draws i = 0 .. n_samples - 1, in draw order, of the
+ * f32 reward an env holding draw i of the column pays in that state (rem = r without an alert, r - 1 with one),
+ * divided by (double) n_samples, by one lane per state.
+ *   start, n_steps, max_budget, ret_out, alerts_out, alert_masks, mask_words, stream   as w2a_hindsight_curve; `sample`
+ *                   is only range-checked (a start outside the tables gives a row of NaN), the outputs do not depend
+ *                   on it, and the env's own budget and used are not read
+ *   workspace       device memory of workspace_bytes >= w2a_hindsight_posterior_curve_workspace_bytes(env, n_steps,
+ *                   max_budget, 1) bytes, 256-B aligned: 256 B, and a pool only if 16 B per day + 96 B per draw + 16 B
+ *                   per state + 8 B per day and 64 states exceed 64 KiB of LDS (always from max_budget 63);
+ *                   `big_envs` sizes the pool for that many envs per launch (speed only)
+ *   allowed_days, allowed_words  (w2a_hindsight_posterior_curve_gated) the gate of w2a_hindsight_optimum_gated: every
+ *                   column is the best schedule UNDER the restriction
+ * Envs finished on entry (or with t >= n_days) get rows of 0, 0 alerts and empty bitmaps; a start state outside the
+ * tables gives a row of NaN, 0 alerts and empty bitmaps.
+ * Numerics contract: the backward sweep weighs w2a_hindsight_posterior's sums statement for statement, and each
+ * budget's schedule is backtracked by one lane that adds its path's rewards in draw order and the days' means in fp64
+ * in day order, rounded once to f32: ret_out[e][b], alerts_out[e][b] and alert_masks[e][b] are BIT-IDENTICAL to
+ * w2a_hindsight_posterior's outputs for the twin with budget = used + b (under the same gate). With n_samples = 1 the
+ * alerts and the schedules are w2a_hindsight_curve's bit for bit and ret_out agrees to f32 rounding. No atomics:
+ * identical calls give identical bits.
+ * Synchronises `stream` once (the slot-27 flag comes to the host before anything is written), then queues its launches
+ * and returns without waiting for them. Reads the tables and the caller's arrays only: the handle's state and
+ * bookkeeping are untouched. Sampled and posterior-mean handles alike: the reward mode is not read.
+ * Refuses where w2a_hindsight_curve refuses, in its order and before any output is written, and after the handle's
+ * checks W2A_ERR_ARG for tables whose n_samples is too large for the per-draw arrays (16 B per day + 96 B per draw above
+ * 64 KiB: more than 657 draws at 153 days). w2a_hindsight_posterior_curve_workspace_bytes returns 0 for a NULL handle
+ * and for arguments or tables the entry refuses. */
+size_t w2a_hindsight_posterior_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget,
+                                                     int32_t big_envs);
+int w2a_hindsight_posterior_curve(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                                  float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int w2a_hindsight_posterior_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                                        float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words,
+                                        void *workspace, size_t workspace_bytes, void *stream,
+                                        const uint32_t *allowed_days, int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

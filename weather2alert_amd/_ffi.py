@@ -49,6 +49,8 @@ SYMBOLS = [
     "w2a_hindsight_curve_workspace_bytes", "w2a_hindsight_curve", "w2a_hindsight_curve_gated",
     "w2a_hindsight_posterior_workspace_bytes", "w2a_hindsight_posterior", "w2a_hindsight_posterior_gated",
     "w2a_hindsight_posterior_along",
+    "w2a_hindsight_posterior_curve_workspace_bytes", "w2a_hindsight_posterior_curve",
+    "w2a_hindsight_posterior_curve_gated",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -352,6 +354,13 @@ def load(build_if_missing: bool = True):
     # its values along a schedule: w2a_hindsight_along's arguments, w2a_hindsight_posterior's workspace
     lib.w2a_hindsight_posterior_along.restype = C.c_int
     lib.w2a_hindsight_posterior_along.argtypes = lib.w2a_hindsight_along.argtypes
+    # the draw-blind budget curve: w2a_hindsight_curve's arguments throughout
+    lib.w2a_hindsight_posterior_curve_workspace_bytes.restype = C.c_size_t
+    lib.w2a_hindsight_posterior_curve_workspace_bytes.argtypes = lib.w2a_hindsight_curve_workspace_bytes.argtypes
+    lib.w2a_hindsight_posterior_curve.restype = C.c_int
+    lib.w2a_hindsight_posterior_curve.argtypes = lib.w2a_hindsight_curve.argtypes
+    lib.w2a_hindsight_posterior_curve_gated.restype = C.c_int
+    lib.w2a_hindsight_posterior_curve_gated.argtypes = lib.w2a_hindsight_curve_gated.argtypes
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

@@ -67,6 +67,7 @@
 #include "w2a_hindsight.hip.h"
 #include "w2a_hindsight_curve.hip.h"
 #include "w2a_hindsight_posterior.hip.h"
+#include "w2a_hindsight_posterior_curve.hip.h"
 #include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1203,18 +1204,37 @@ int w2a_hindsight_posterior_along(w2a_env *env, const w2a_state_view *start, int
 // (big_envs envs per launch)
 static size_t hc_fixed_bytes() { return 256; }
 
-size_t w2a_hindsight_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget, int32_t big_envs) {
+// the LDS a curve kernel keeps beside V and the decision words: k_hs_curve's day statics, or (posterior) k_hs_pm_dp's
+// day tails and per-draw arrays
+static size_t hc_lds_fixed(const w2a_env *env, uint32_t hb, bool posterior) {
+  return posterior ? hs_pm_fixed_bytes(hb, (uint32_t)env->tb.n_samples) : hs_day_bytes(hb);
+}
+
+static size_t hc_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget, int32_t big_envs, bool posterior) {
   if (!env || n_steps <= 0 || big_envs <= 0 || max_budget < 0 || max_budget > HC_MAX_BUDGET) return 0;
   const uint32_t hb = (uint32_t)min(n_steps, env->tb.T);
-  const bool pool = hs_day_bytes(hb) + hc_dp_bytes((uint32_t)max_budget, hb) > HS_LDS_CAP;
+  const size_t fixed = hc_lds_fixed(env, hb, posterior);
+  if (fixed > HS_LDS_CAP) return 0;  // (posterior) the entry refuses these tables
+  const bool pool = fixed + hc_dp_bytes((uint32_t)max_budget, hb) > HS_LDS_CAP;
   return hc_fixed_bytes() + (pool ? (size_t)big_envs * align256(hc_dp_bytes((uint32_t)max_budget, hb)) : 0);
+}
+
+size_t w2a_hindsight_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget, int32_t big_envs) {
+  return hc_workspace_bytes(env, n_steps, max_budget, big_envs, false);
+}
+
+size_t w2a_hindsight_posterior_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget,
+                                                     int32_t big_envs) {
+  return hc_workspace_bytes(env, n_steps, max_budget, big_envs, true);
 }
 
 static int hindsight_curve(const char *fn, w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
                            float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words, void *workspace,
-                           size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words) {
+                           size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words,
+                           bool posterior = false) {
   // w2a_hindsight_optimum's refusals in its order (alert_masks may be NULL: mask_words is then not read), max_budget
-  // among what is checked without the handle
+  // among what is checked without the handle. posterior (w2a_hindsight_posterior_curve): k_hs_pm_curve on
+  // w2a_hindsight_posterior's LDS, with that entry's refusal of an n_samples beyond the per-draw arrays in its place
   if (!start || !ret_out || !alerts_out || !workspace) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
   HS_CHECK(check_hs_start(fn, start, n_steps, alert_masks != nullptr, mask_words));
   if (max_budget < 0 || max_budget > HC_MAX_BUDGET)
@@ -1222,24 +1242,33 @@ static int hindsight_curve(const char *fn, w2a_env *env, const w2a_state_view *s
   static_assert(HC_MAX_BUDGET == 1023, "the message above and include/w2a.h state the cap");
   HS_CHECK(check_hs_handle(fn, env, alert_masks != nullptr, mask_words,
                             "alert_masks needs ceil(T/32) words per env and budget"));
+  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T), B = (uint32_t)max_budget;
+  const size_t fixed = hc_lds_fixed(env, hb, posterior);
+  if (fixed > HS_LDS_CAP)
+    return fail(W2A_ERR_ARG, "%s: the tables' n_samples is too large: 96 bytes per draw and 16 per day of the "
+                             "stretch must fit in 64 KiB of LDS", fn);
   HS_CHECK(check_hs_gate_capture(fn, env, gated, gate, gate_words, stream));
   const hipStream_t s = (hipStream_t)stream;
   const int64_t n = env->n;
-  const uint32_t hb = (uint32_t)min(n_steps, env->tb.T), B = (uint32_t)max_budget;
   if (n > 0x7FFFFFFFll) return fail(W2A_ERR_ARG, "%s: num_envs too large", fn);
-  const size_t need = hs_day_bytes(hb) + hc_dp_bytes(B, hb), stride = align256(hc_dp_bytes(B, hb));
+  const size_t need = fixed + hc_dp_bytes(B, hb), stride = align256(hc_dp_bytes(B, hb));
   const bool in_lds = need <= HS_LDS_CAP;
   if (workspace_bytes < hc_fixed_bytes() + (in_lds ? 0 : stride))
-    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_hindsight_curve_workspace_bytes(env, n_steps, "
-                             "max_budget, 1)", fn);
+    return hs_fail("%s: workspace smaller than %s(env, n_steps, max_budget, 1)", fn,
+                   posterior ? "w2a_hindsight_posterior_curve_workspace_bytes" : "w2a_hindsight_curve_workspace_bytes");
   HS_CHECK(hs_refuse_slot27(fn, env, workspace, s, "remaining"));
   if (n == 0) return W2A_OK;
   HcArgs ca;
   fill_hs_args(ca.h, env, start, n_steps, ret_out, alert_masks, alert_masks ? mask_words : 0, alerts_out,
                gated ? gate : nullptr, gate_words);
   ca.B = max_budget;
+  // cnt envs from env i on: V and the decision words in LDS beside `fixed` bytes, or (global) in the pool
+  auto launch = [&](bool global, uint32_t cnt, size_t lds, uint32_t i, char *pool, size_t pool_stride) {
+    if (posterior) HS_LAUNCH(k_hs_pm_curve, global, gated, cnt, lds, s, ca, i, pool, pool_stride);
+    else HS_LAUNCH(k_hs_curve, global, gated, cnt, lds, s, ca, i, pool, pool_stride);
+  };
   if (in_lds) {
-    HS_LAUNCH(k_hs_curve, false, gated, (unsigned)n, need, s, ca, 0u, nullptr, (size_t)0);
+    launch(false, (uint32_t)n, need, 0u, nullptr, (size_t)0);
     HIP_TRY(hipGetLastError());
     return W2A_OK;
   }
@@ -1247,7 +1276,7 @@ static int hindsight_curve(const char *fn, w2a_env *env, const w2a_state_view *s
   const size_t fit = (workspace_bytes - hc_fixed_bytes()) / stride;
   const uint32_t per = fit < (size_t)n ? (uint32_t)fit : (uint32_t)n;
   for (uint32_t i = 0; i < (uint32_t)n; i += per) {  // launches on one stream: each finds the pool free
-    HS_LAUNCH(k_hs_curve, true, gated, min(per, (uint32_t)n - i), hs_day_bytes(hb), s, ca, i, pool, stride);
+    launch(true, min(per, (uint32_t)n - i), fixed, i, pool, stride);
     HIP_TRY(hipGetLastError());
   }
   return W2A_OK;
@@ -1266,6 +1295,22 @@ int w2a_hindsight_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t
                               int32_t allowed_words) {
   return hindsight_curve("w2a_hindsight_curve_gated", env, start, n_steps, max_budget, ret_out, alerts_out, alert_masks,
                          mask_words, workspace, workspace_bytes, stream, true, allowed_days, allowed_words);
+}
+
+int w2a_hindsight_posterior_curve(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                                  float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+  return hindsight_curve("w2a_hindsight_posterior_curve", env, start, n_steps, max_budget, ret_out, alerts_out,
+                         alert_masks, mask_words, workspace, workspace_bytes, stream, false, nullptr, 0, true);
+}
+
+int w2a_hindsight_posterior_curve_gated(w2a_env *env, const w2a_state_view *start, int32_t n_steps, int32_t max_budget,
+                                        float *ret_out, int32_t *alerts_out, uint32_t *alert_masks, int32_t mask_words,
+                                        void *workspace, size_t workspace_bytes, void *stream,
+                                        const uint32_t *allowed_days, int32_t allowed_words) {
+  return hindsight_curve("w2a_hindsight_posterior_curve_gated", env, start, n_steps, max_budget, ret_out, alerts_out,
+                         alert_masks, mask_words, workspace, workspace_bytes, stream, true, allowed_days, allowed_words,
+                         true);
 }
 #undef HS_LAUNCH
 #undef HS_CHECK

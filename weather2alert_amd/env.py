@@ -2188,14 +2188,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
             out["loss"] = los
         return out
 
-    def _hs_posterior_share(self, st: dict, sched=None):
+    def _hs_posterior_share(self, st: dict, sched=None, unread=()):
         """The distinct problems of the draw-blind DP, found on the host: envs that agree on every _HS_FIELDS array
         but `sample` (a draw outside the tables keeps its own key: its answer is NaN) and, with sched (int32
-        [N, words]), on their packed schedule words. Returns (rep, inv, first, m): rep the state arrays the library
+        [N, words]), on their packed schedule words. unread: further fields the caller's kernel does not read (the
+        budget curve's `budget` and `used`). Returns (rep, inv, first, m): rep the state arrays the library
         runs -- num_envs entries, the m representatives (the lowest env id of each key, `first`) in front and the rest
         marked finished (no DP) -- and inv the key of every env, so that x[:m][inv] gathers a per-env output back."""
         n, dev = st["t"].shape[0], st["t"].device
-        cols = [st[k] for k in _HS_FIELDS if k != "sample"] + \
+        cols = [st[k] for k in _HS_FIELDS if k != "sample" and k not in unread] + \
                [((st["sample"] < 0) | (st["sample"] >= self.ct.n_samples)).to(torch.int32)]
         key = torch.stack(cols, dim=1)
         if sched is not None:
@@ -2233,10 +2234,74 @@ class HeatAlertVecEnv(_VectorEnvBase):
         start_state and the tables only: the env's state, observation buffer and bookkeeping are untouched."""
         who = "hindsight_budget_curve()"
         self._check_hindsight(who)
+        B = self._curve_check(who, max_budget, schedules, packed)
+        ct, n, dev = self.ct, self.num_envs, self.device
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=True)
+        with torch.cuda.device(dev):
+            ret, alerts, masks = self._curve_packed(st, steps, B, gate, schedules)
+        return self._curve_out(ret, alerts, masks, st, schedules, packed)
+
+    def hindsight_posterior_budget_curve(self, max_budget: int, start_state: dict | None = None,
+                                         n_steps: int | None = None, allowed_days=None, schedules: bool = False,
+                                         packed: bool = False, share: bool = True) -> dict:
+        """hindsight_budget_curve() WITH THE DRAW UNKNOWN: hindsight_posterior_optimum() for EVERY remaining budget
+        0 .. max_budget in one sweep. Splitting a fixed number of alerts over counties (stats.budget_curve_by_group,
+        stats.allocate_budget) is decided before anyone knows which posterior draw a county's episode will get; curves
+        under each env's own draw make the allocation chase draw noise and report regret against a bound no policy can
+        reach. Column b of env e is hindsight_posterior_optimum() of the twin with budget = used + b, bit for bit
+        (return, alerts and schedule), also under allowed_days and a truncated n_steps. The env's own budget is not
+        read. Keys, shapes, dtypes and fills are hindsight_budget_curve()'s, with B = max_budget:
+            "return":     f32 [N, B + 1]  the posterior-mean return of budget b's schedule (the fp64 sum over its days
+                                          of the mean over draws of the f32 rewards, rounded once)
+            "alerts":     i32 [N, B + 1]  alerts in budget b's schedule (<= b)
+            "own_budget": i32 [N]         budget - used of start_state: the env's own column where it is in 0 .. B
+            "alert_days": (schedules=True) bool [N, B + 1, T] by day of the episode, or with packed=True the kernel's
+                                          int32 [N, B + 1, ceil(T / 32)] words
+        Envs finished in start_state give rows of 0 and empty schedules; a start outside the tables gives a row of NaN.
+        hindsight_budget_curve()'s DP over (alerts remaining, streak) with the reward of every state averaged over the
+        n_samples draws of the env's coefficient column in fp64, in draw order (w2a_hindsight_posterior_curve,
+        include/w2a.h); with n_samples = 1 alerts and schedules are hindsight_budget_curve()'s bit for bit. The result
+        depends on neither `sample` nor the env's budget and used: with share=True (the default) envs that agree on t,
+        streak, n_days, county_w, year_i, coef_col and finished are found on the host (torch.unique), one of each runs
+        and the rows are gathered back -- bit for bit what share=False returns; last_hindsight_posterior_keys is the
+        number run. With allowed_days every env has its own gate row and nothing is shared.
+        Sampled and posterior_mean envs alike. max_budget, n_steps (an int) and the 4 GiB schedule cap as
+        hindsight_budget_curve(); refuses what hindsight_posterior_optimum() refuses (corrected-semantics fixes,
+        slot-27 tables, a stream capture, an n_samples beyond the kernel's per-draw arrays: 657 draws at 153 days)
+        before anything is written. Reads start_state and the tables only: the env's state, observation buffer and
+        bookkeeping are untouched."""
+        who = "hindsight_posterior_budget_curve()"
+        self._check_hindsight_fixes(who)
+        self._check_hindsight_slot27(who)
+        B = self._curve_check(who, max_budget, schedules, packed)
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _ffi.W2AError(f"{who}: the stream is recording a hipGraph; the call finds the distinct problems and "
+                                "sizes its launches on the host")
+        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
+        st = self._hs_start_state(start_state)
+        steps = self._hs_steps(n_steps, who, strict=True)
+        with torch.cuda.device(dev):
+            if share and gate is None and n:
+                # k_hs_pm_curve reads neither budget nor used (rem is B - m - i), so they are not part of the problem
+                rep, inv, _, m = self._hs_posterior_share(st, unread=("budget", "used"))
+                ret, alerts, masks = self._curve_packed(rep, steps, B, None, schedules, posterior=True)
+                ret, alerts = ret[:m][inv], alerts[:m][inv]
+                masks = None if masks is None else masks[:m][inv]
+                self.last_hindsight_posterior_keys = int(m)
+            else:
+                ret, alerts, masks = self._curve_packed(st, steps, B, gate, schedules, posterior=True)
+                self.last_hindsight_posterior_keys = n
+        return self._curve_out(ret, alerts, masks, st, schedules, packed)
+
+    def _curve_check(self, who: str, max_budget, schedules: bool, packed: bool) -> int:
+        """max_budget as an int in 0 .. 1023 and the byte cap of the schedules"""
         if isinstance(max_budget, bool) or not isinstance(max_budget, (int, np.integer)) or \
                 not 0 <= max_budget <= _CURVE_MAX_BUDGET:
             raise ValueError(f"{who}: max_budget must be an int in 0..{_CURVE_MAX_BUDGET}, got {max_budget!r}")
-        ct, n, dev = self.ct, self.num_envs, self.device
+        ct, n = self.ct, self.num_envs
         B = int(max_budget)
         words = (ct.T + 31) // 32
         if schedules:
@@ -2245,28 +2310,39 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 raise ValueError(f"{who}: the schedules of {n} envs x {B + 1} budgets need {need} bytes, more than "
                                  f"{_CURVE_SCHEDULE_BYTES}; ask for fewer envs or budgets per call"
                                  + ("" if packed else ", or packed=True"))
-        gate = _policy.check_allowed_days({"kind": "linear", "allowed_days": allowed_days}, n, ct.T, dev, who)
-        st = self._hs_start_state(start_state)
-        steps = self._hs_steps(n_steps, who, strict=True)
+        return B
+
+    def _curve_packed(self, st: dict, steps: int, B: int, gate, schedules: bool, posterior: bool = False):
+        """w2a_hindsight_curve (posterior: w2a_hindsight_posterior_curve) on device int32 state arrays: (return f32
+        [N, B + 1], alerts i32 [N, B + 1], packed schedules i32 [N, B + 1, words] or None). gate: packed allowed days
+        (the _gated entry)."""
+        ct, n, dev = self.ct, self.num_envs, self.device
+        words = (ct.T + 31) // 32
         ret = torch.empty((n, B + 1), dtype=torch.float32, device=dev)
         alerts = torch.empty((n, B + 1), dtype=torch.int32, device=dev)
         masks = torch.empty((n, B + 1, words), dtype=torch.int32, device=dev) if schedules else None
-        with torch.cuda.device(dev):
-            ws_bytes = self._lib.w2a_hindsight_curve_workspace_bytes(self._h, steps, B, _HS_BIG_ENVS)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            v = self._hs_state_view(st)
-            args = (self._h, C.byref(v), steps, B, ret.data_ptr(), alerts.data_ptr(),
-                    None if masks is None else masks.data_ptr(), words, ws.data_ptr(), ws_bytes, self._stream())
-            if gate is None:
-                _ffi.check(self._lib.w2a_hindsight_curve(*args), "w2a_hindsight_curve")
-            else:
-                _ffi.check(self._lib.w2a_hindsight_curve_gated(*args, gate.data_ptr(), int(gate.shape[1])),
-                           "w2a_hindsight_curve_gated")
+        name = "w2a_hindsight_posterior_curve" if posterior else "w2a_hindsight_curve"
+        ws_bytes = getattr(self._lib, name + "_workspace_bytes")(self._h, steps, B, _HS_BIG_ENVS)
+        # (0 bytes, the posterior's answer for tables it cannot take: the entry refuses, with its message)
+        ws = torch.empty(max(ws_bytes, 256) if posterior else ws_bytes, dtype=torch.uint8, device=dev)
+        v = self._hs_state_view(st)
+        args = (self._h, C.byref(v), steps, B, ret.data_ptr(), alerts.data_ptr(),
+                None if masks is None else masks.data_ptr(), words, ws.data_ptr(), ws_bytes, self._stream())
+        if gate is None:
+            _ffi.check(getattr(self._lib, name)(*args), name)
+        else:
+            _ffi.check(getattr(self._lib, name + "_gated")(*args, gate.data_ptr(), int(gate.shape[1])), name + "_gated")
         self._keep_curve = (st, gate, ws)  # the launches are asynchronous
+        return ret, alerts, masks
+
+    def _curve_out(self, ret, alerts, masks, st: dict, schedules: bool, packed: bool) -> dict:
+        """the curve calls' dict; own_budget from the caller's (unshared) start state"""
+        ct, n = self.ct, self.num_envs
+        B, words = ret.shape[1] - 1, (ct.T + 31) // 32
         out = {"return": ret, "alerts": alerts, "own_budget": st["budget"] - st["used"]}
         if schedules:
             out["alert_days"] = masks if packed else \
-                _policy.unpack_alert_days(masks.view(n * (B + 1), words), ct.T).view(n, B + 1, ct.T)
+                _policy.unpack_alert_days(masks.reshape(n * (B + 1), words), ct.T).view(n, B + 1, ct.T)
         return out
 
     def _check_hindsight(self, who: str):
