@@ -9,7 +9,12 @@ under each.
 allocates from the draw-blind curves (hindsight_posterior_budget_curve: the optimum of the reward averaged over all
 draws) and prints both allocations and their values under the draw-mean, read off the draw-blind curves.
 
-    python examples/budget_allocation.py [--draw-blind]           # needs one ROCm GPU
+--policy: the split should maximise what the policy that will actually run earns, so it also allocates from that
+policy's own curves (policy_budget_curve: rollout(linear) for every budget in one sweep -- here the linear form of the
+threshold policy below) and prints them next to the hindsight and draw-blind ones, with the policy's share of the
+hindsight optimum per budget.
+
+    python examples/budget_allocation.py [--draw-blind] [--policy]           # needs one ROCm GPU
 """
 import argparse
 import os
@@ -23,6 +28,7 @@ from weather2alert_amd import HeatAlertVecEnv, compile_from_synth, stats, synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--draw-blind", action="store_true")
+ap.add_argument("--policy", action="store_true")
 args = ap.parse_args()
 
 data = synth.make_synth("linear", n_fips=64, years=[2006, 2007, 2008], n_samples=100, seed=0, extra_confounder_fips=6)
@@ -80,6 +86,32 @@ if args.draw_blind:
     v_b = blind["return"][rows, new_b.long()].double().mean().item()
     assert abs(v_b * n - alloc_b["value"]) <= 1e-6 * abs(alloc_b["value"]) and alloc_b["spent"] <= total
     assert v_b >= blind["return"][rows, new.long()].double().mean().item() - 1e-9  # the optimum of these curves
+
+# 4c. the split on the curves of the policy that will run: heat_qi > 0.9 with budget left, as a linear policy
+if args.policy:
+    w = torch.zeros((1, tables.n_obs), dtype=torch.float32)
+    w[0, tables.feature_names.index("heat_qi")] = 1.0
+    lin = {"kind": "linear", "weight": w, "bias": [-torch.tensor(0.9, dtype=torch.float32).item()], "require_budget": True}
+    pcv = env.policy_budget_curve(lin, B)  # the env is as reset() left it: its own state, its own observation rows
+    assert torch.equal(pcv["own_budget"], own) and not bool(pcv["attempts_over_budget"].any())
+    by_p = stats.budget_curve_by_group(pcv["return"], county, tables.S_w)
+    alloc_p = stats.allocate_budget(by_p["curve"], total, group_size=by_p["count"])
+    new_p = alloc_p["budget"].to(env.device)[county].to(torch.int32)
+    blind_p = env.hindsight_posterior_budget_curve(B, start_state=st0)["return"].double().mean(0)
+    hs_p, po_p = curve["return"].double().mean(0), pcv["return"].double().mean(0)
+    print("budget: mean return of the hindsight optimum / the draw-blind optimum / the policy (policy / hindsight)")
+    for b in range(B + 1):
+        print(f"  {b:3d}: {hs_p[b].item():9.3f} {blind_p[b].item():9.3f} {po_p[b].item():9.3f}   "
+              f"({(po_p[b] / hs_p[b]).item():.4f})")
+    print("county budgets, hindsight allocation -> policy allocation:")
+    print("  " + "  ".join(f"{int(alloc['budget'][g])}->{int(alloc_p['budget'][g])}" for g in range(tables.S_w)
+                          if int(by["count"][g])))
+    for name, bud in (("default", own), ("hindsight allocation", new), ("policy allocation", new_p)):
+        v = pcv["return"][rows, bud.long()].double().mean().item()
+        print(f"policy's return per episode, {name:22s}: {v:9.3f} ({int(bud.sum())} alerts)")
+    v_p = pcv["return"][rows, new_p.long()].double().mean().item()
+    assert abs(v_p * n - alloc_p["value"]) <= 1e-6 * abs(alloc_p["value"]) and alloc_p["spent"] <= total
+    assert v_p >= pcv["return"][rows, new.long()].double().mean().item() - 1e-9  # the optimum of these curves
 
 # 5. the same threshold policy under each split: its return, and its regret against the curve's column
 policy = {"kind": "threshold", "feature": "heat_qi", "threshold": 0.9, "require_budget": True}

@@ -1409,6 +1409,60 @@ int w2a_hindsight_posterior_curve_gated(w2a_env *env, const w2a_state_view *star
                                         void *workspace, size_t workspace_bytes, void *stream,
                                         const uint32_t *allowed_days, int32_t allowed_words);
 
+/* The policy budget curve (additions to ABI 18, nothing above changes): w2a_rollout_linear for EVERY remaining budget
+ * b = 0 .. max_budget at once -- what the policy that will actually run earns with b alerts, the row of the
+ * budget-curve table whose upper bounds are w2a_hindsight_curve and w2a_hindsight_posterior_curve. Column b of env e is
+ * w2a_rollout_linear of the twin whose budget is used + b: the same weather, draw, counters and Bernoulli uniforms
+ * (keyed by seed, env id, episode and day), require_budget and the gate as there.
+ * The reward and the policy read the budget through the run-time slots 24..27 only, and the fp64 chains run in slot
+ * order: per env-day the row is gathered once and the three chains run once over slots 0..23; per budget only slots
+ * 24..27 from that budget's counters, then 28 and 29, the decision, the reward and the counter update.
+ *   policy          as w2a_rollout_linear (weight, bias, group, n_groups, sample, require_budget, seed)
+ *   start           the start state; t, streak, hist14, n_days, county_w, year_i, coef_col, sample, episode_no and
+ *                   finished are read. budget and used are NOT read: the remaining budget of column b is b
+ *   n_steps         days to run from every env's start day (an env stops at its episode's end)
+ *   max_budget      0 .. 1023, the same for every env of the call
+ *   obs             device f32 [num_envs][n_obs]: the row every env's agent holds in `start` (the first decision's
+ *                   input; column b reads (float) b in place of its remaining_budget column, at that column's place in
+ *                   the chain). Read only. NULL: the rows are rebuilt as a reset writes them -- day 0's table row with
+ *                   lag, streak and 14-day count 0 -- which is the held row only where every live env of `start` is at
+ *                   t = 0 with nothing used
+ *   ret_out         device f32 [num_envs][max_budget + 1]: the rewards summed over the days run
+ *   alerts_out      device i32 [num_envs][max_budget + 1]: alerts issued
+ *   attempts_over_budget  device i32 [num_envs][max_budget + 1]: attempts made with no budget left
+ *   alert_masks     NULL (mask_words is then not read), or device u32 [num_envs][max_budget + 1][mask_words]: the
+ *                   alerts issued by day of the episode, in w2a_rollout_linear's alert_mask format; every word is
+ *                   written; mask_words * 32 >= T
+ *   workspace       device memory of workspace_bytes >= w2a_policy_curve_workspace_bytes(env, n_steps, max_budget)
+ *                   bytes, 256-B aligned: 256 reserved bytes (the per-budget state lives in registers, the day
+ *                   prefixes in LDS)
+ *   allowed_days, allowed_words  (w2a_policy_curve_linear_gated) the gate of w2a_rollout_linear_gated
+ * Envs finished on entry (or with t >= n_days) get rows of 0 and empty bitmaps; a start state outside the tables gives
+ * a row of NaN, zero counts and empty bitmaps.
+ * Numerics contract: the statements of w2a_rollout_linear in its order -- logit with the bias first and slots in slot
+ * order, require_budget, the gate, the budget test, the gate flag of slot 30, the f32 sigmoids, the f32 sum of the
+ * rewards in day order: ret_out[e][b], alerts_out[e][b], attempts_over_budget[e][b] and alert_masks[e][b] are
+ * BIT-IDENTICAL to that call's outputs on the twin. No atomics: identical calls give identical bits.
+ * Queues one launch and returns without waiting. Reads the tables and the caller's arrays only: the handle's state,
+ * observation buffer and bookkeeping are untouched.
+ * Refuses before anything is written: W2A_ERR_ARG for what w2a_rollout_linear refuses of the policy struct and n_steps,
+ * NULL start, outputs or start-state arrays, mask_words <= 0 with alert_masks, max_budget outside 0..1023, a NULL or
+ * misaligned workspace (all checked before the handle), a NULL handle, mask_words * 32 < T with alert_masks, a handle
+ * with corrected-semantics flags, num_envs * n_obs >= 2^31, a workspace smaller than
+ * w2a_policy_curve_workspace_bytes(env, n_steps, max_budget), a bad gate; W2A_ERR_STATE while `stream` is recording a
+ * hipGraph; W2A_ERR_SCHEMA as w2a_rollout_linear. w2a_policy_curve_workspace_bytes returns 0 for a NULL handle and for
+ * arguments the entry refuses. */
+size_t w2a_policy_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget);
+int w2a_policy_curve_linear(w2a_env *env, const w2a_linear_policy *policy, const w2a_state_view *start, int32_t n_steps,
+                            int32_t max_budget, const float *obs, float *ret_out, int32_t *alerts_out,
+                            int32_t *attempts_over_budget, uint32_t *alert_masks, int32_t mask_words, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int w2a_policy_curve_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const w2a_state_view *start,
+                                  int32_t n_steps, int32_t max_budget, const float *obs, float *ret_out,
+                                  int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_masks,
+                                  int32_t mask_words, void *workspace, size_t workspace_bytes, void *stream,
+                                  const uint32_t *allowed_days, int32_t allowed_words);
+
 #ifdef __cplusplus
 }
 #endif

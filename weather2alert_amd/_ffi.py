@@ -51,6 +51,7 @@ SYMBOLS = [
     "w2a_hindsight_posterior_along",
     "w2a_hindsight_posterior_curve_workspace_bytes", "w2a_hindsight_posterior_curve",
     "w2a_hindsight_posterior_curve_gated",
+    "w2a_policy_curve_workspace_bytes", "w2a_policy_curve_linear", "w2a_policy_curve_linear_gated",
 ]
 Q_LOCKSTEP_DAY, Q_PACKED_ELIGIBLE, Q_PACKED_CURRENT, Q_CANONICAL_CURRENT, Q_LAST_ROLLOUT_KERNEL, Q_LAST_STEP_KERNEL, Q_LOCKSTEP = 0, 1, 2, 3, 4, 5, 6
 Q_EPISODE_WORD_BYTES = 7
@@ -361,6 +362,15 @@ def load(build_if_missing: bool = True):
     lib.w2a_hindsight_posterior_curve.argtypes = lib.w2a_hindsight_curve.argtypes
     lib.w2a_hindsight_posterior_curve_gated.restype = C.c_int
     lib.w2a_hindsight_posterior_curve_gated.argtypes = lib.w2a_hindsight_curve_gated.argtypes
+    # the policy budget curve: the policy, start, n_steps, max_budget, the held rows (nullable), returns, alerts,
+    # attempts over budget, the nullable schedules and their words, the workspace and the stream
+    lib.w2a_policy_curve_workspace_bytes.restype = C.c_size_t
+    lib.w2a_policy_curve_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.w2a_policy_curve_linear.restype = C.c_int
+    lib.w2a_policy_curve_linear.argtypes = [vp, C.POINTER(LinearPolicy), C.POINTER(StateView), i32, i32, vp, vp, vp, vp,
+                                            vp, i32, vp, C.c_size_t, vp]
+    lib.w2a_policy_curve_linear_gated.restype = C.c_int
+    lib.w2a_policy_curve_linear_gated.argtypes = lib.w2a_policy_curve_linear.argtypes + gate
     if lib.w2a_abi_version() != ABI_VERSION:
         raise W2AError(f"libw2a.so ABI {lib.w2a_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib

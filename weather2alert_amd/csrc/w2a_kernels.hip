@@ -68,6 +68,7 @@
 #include "w2a_hindsight_curve.hip.h"
 #include "w2a_hindsight_posterior.hip.h"
 #include "w2a_hindsight_posterior_curve.hip.h"
+#include "w2a_policy_curve.hip.h"
 #include "w2a_gate.hip.h"
 #include "w2a_sort.hip.h"
 
@@ -1312,6 +1313,101 @@ int w2a_hindsight_posterior_curve_gated(w2a_env *env, const w2a_state_view *star
                          alert_masks, mask_words, workspace, workspace_bytes, stream, true, allowed_days, allowed_words,
                          true);
 }
+// ----------------------------------------------------------------------------------------
+// policy budget curve: w2a_policy_curve_linear / _gated (k_policy_curve_linear, w2a_policy_curve.hip.h)
+// ----------------------------------------------------------------------------------------
+// The policy struct's checks and the slot map are w2a_rollout_linear's (w2a_policy_dispatch.hip.h), the start state's
+// and max_budget's are w2a_hindsight_curve's; every refusal comes before the launch, which is the only thing that writes.
+// The kernel keeps its per-budget state in registers and the day prefixes in LDS: the workspace is 256 reserved bytes.
+static size_t pc_workspace_bytes() { return 256; }
+
+size_t w2a_policy_curve_workspace_bytes(const w2a_env *env, int32_t n_steps, int32_t max_budget) {
+  if (!env || n_steps <= 0 || max_budget < 0 || max_budget > PC_MAX_BUDGET) return 0;
+  return pc_workspace_bytes();
+}
+
+static int policy_curve_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, const w2a_state_view *start,
+                               int32_t n_steps, int32_t max_budget, const float *obs, float *ret_out, int32_t *alerts_out,
+                               int32_t *attempts_over_budget, uint32_t *alert_masks, int32_t mask_words, void *workspace,
+                               size_t workspace_bytes, void *stream, bool gated, const uint32_t *gate, int32_t gate_words) {
+  // what needs no handle first (so that it is checked on any machine): the policy, the arrays, the two integers
+  HS_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
+  if (!start || !ret_out || !alerts_out || !attempts_over_budget) return fail(W2A_ERR_ARG, "%s: NULL argument", fn);
+  if (!start->t || !start->streak || !start->hist14 || !start->n_days || !start->county_w || !start->year_i ||
+      !start->coef_col || !start->sample || !start->episode_no || !start->finished)
+    return fail(W2A_ERR_ARG, "%s: NULL start-state array (t, streak, hist14, n_days, county_w, year_i, coef_col, "
+                             "sample, episode_no and finished are read)", fn);
+  if (alert_masks && mask_words <= 0) return fail(W2A_ERR_ARG, "%s: mask_words must be positive", fn);
+  if (max_budget < 0 || max_budget > PC_MAX_BUDGET) return fail(W2A_ERR_ARG, "%s: max_budget must lie in 0..1023", fn);
+  static_assert(PC_MAX_BUDGET == 1023, "the message above and include/w2a.h state the cap");
+  HS_CHECK(check_workspace_pointer(fn, workspace));
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if (alert_masks && (int64_t)mask_words * 32 < env->tb.T)
+    return fail(W2A_ERR_ARG, "%s: alert_masks needs ceil(T/32) words per env and budget", fn);
+  HS_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_NONE, 0));
+  if (workspace_bytes < pc_workspace_bytes())
+    return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_curve_workspace_bytes(env, n_steps, max_budget)", fn);
+  if (gated) HS_CHECK(check_gate(fn, env, gate, gate_words));
+  HS_CHECK(refuse_while_capturing(fn, stream));
+  PcArgs a;
+  memset(&a, 0, sizeof(a));
+  {
+    RolloutArgs r;  // the slot map of the rollouts (and their refusal of a schema with a column on slot 30 or 31)
+    memset(&r, 0, sizeof(r));
+    HS_CHECK(fill_rollout_common(fn, env, n_steps, r, a.slot_obs, a.obs_mask));
+  }
+  a.tb = env->tb; a.st = *start; a.n = env->n; a.gid0 = env->gid0; a.n_steps = n_steps; a.B = max_budget;
+  const uint32_t nb = (uint32_t)max_budget + 1u;
+  a.n_chunks = (int32_t)((nb + PC_BLOCK - 1) / PC_BLOCK);
+  a.C = (int32_t)((nb + (uint32_t)a.n_chunks - 1) / (uint32_t)a.n_chunks);
+  a.E = PC_BLOCK / a.C;
+  a.D = PC_BLOCK / a.E;
+  a.weight = reinterpret_cast<const float4 *>(policy->weight); a.bias = policy->bias; a.group = policy->group;
+  a.n_groups = policy->n_groups; a.n_obs = env->tb.n_obs; a.obs = obs;
+  a.require_budget = policy->require_budget; a.seed = policy->seed;
+  a.gate = gated ? gate : nullptr; a.gate_words = gated ? gate_words : 0;
+  a.ret = ret_out; a.alerts = alerts_out; a.over = attempts_over_budget;
+  a.mask = alert_masks; a.mask_words = alert_masks ? mask_words : 0;
+  if (env->n == 0) return W2A_OK;
+  const int64_t blocks = (env->n + a.E - 1) / a.E * a.n_chunks;
+  if (blocks > 0x7FFFFFFFll) return fail(W2A_ERR_ARG, "%s: num_envs x budget chunks exceed one launch (2^31 - 1 workgroups)", fn);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 g((unsigned)blocks), blk(PC_BLOCK);
+  const bool smp = policy->sample != 0, sch = alert_masks != nullptr;
+#define PC_LAUNCH(S, G, M) hipLaunchKernelGGL((k_policy_curve_linear<S, G, M>), g, blk, 0, s, a)
+  if (smp && gated && sch) PC_LAUNCH(true, true, true);
+  else if (smp && gated) PC_LAUNCH(true, true, false);
+  else if (smp && sch) PC_LAUNCH(true, false, true);
+  else if (smp) PC_LAUNCH(true, false, false);
+  else if (gated && sch) PC_LAUNCH(false, true, true);
+  else if (gated) PC_LAUNCH(false, true, false);
+  else if (sch) PC_LAUNCH(false, false, true);
+  else PC_LAUNCH(false, false, false);
+#undef PC_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return W2A_OK;
+}
+
+int w2a_policy_curve_linear(w2a_env *env, const w2a_linear_policy *policy, const w2a_state_view *start, int32_t n_steps,
+                            int32_t max_budget, const float *obs, float *ret_out, int32_t *alerts_out,
+                            int32_t *attempts_over_budget, uint32_t *alert_masks, int32_t mask_words, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+  return policy_curve_linear("w2a_policy_curve_linear", env, policy, start, n_steps, max_budget, obs, ret_out, alerts_out,
+                             attempts_over_budget, alert_masks, mask_words, workspace, workspace_bytes, stream, false,
+                             nullptr, 0);
+}
+
+int w2a_policy_curve_linear_gated(w2a_env *env, const w2a_linear_policy *policy, const w2a_state_view *start,
+                                  int32_t n_steps, int32_t max_budget, const float *obs, float *ret_out,
+                                  int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_masks,
+                                  int32_t mask_words, void *workspace, size_t workspace_bytes, void *stream,
+                                  const uint32_t *allowed_days, int32_t allowed_words) {
+  return policy_curve_linear("w2a_policy_curve_linear_gated", env, policy, start, n_steps, max_budget, obs, ret_out,
+                             alerts_out, attempts_over_budget, alert_masks, mask_words, workspace, workspace_bytes, stream,
+                             true, allowed_days, allowed_words);
+}
+
+
 #undef HS_LAUNCH
 #undef HS_CHECK
 

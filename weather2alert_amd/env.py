@@ -2296,6 +2296,111 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 self.last_hindsight_posterior_keys = n
         return self._curve_out(ret, alerts, masks, st, schedules, packed)
 
+    def policy_budget_curve(self, policy: dict, max_budget: int, start_state: dict | None = None,
+                            n_steps: int | None = None, schedules: bool = False, packed: bool = False) -> dict:
+        """rollout(linear) for EVERY remaining budget 0 .. max_budget in one sweep: what the policy that will actually
+        run earns with b alerts -- the policy's row of the budget-curve table whose upper bounds are
+        hindsight_budget_curve() (weather and draw known) and hindsight_posterior_budget_curve() (weather known), so
+        that stats.budget_curve_by_group / stats.allocate_budget split alerts over counties on what is attainable and
+        ``curve_policy / curve_hindsight`` is the regret per budget. Column b of env e is rollout() of the twin env whose
+        budget is used + b, bit for bit in return, counts and schedule: the same weather, draw and counters, the same
+        Bernoulli uniforms (keyed by seed, env id, episode and day: all budgets share them), require_budget and the gate.
+        policy: a ``"kind": "linear"`` dict as rollout() takes it -- weight, bias, group, sample, seed, require_budget
+        and "allowed_days" (bool [N, T] or packed words). Returns, with B = max_budget, the keys of
+        hindsight_budget_curve() (same names, shapes, dtypes and fills) and one more:
+            "return":     f32 [N, B + 1]  rewards summed over the days run
+            "alerts":     i32 [N, B + 1]  alerts issued (<= b)
+            "attempts_over_budget": i32 [N, B + 1]  attempts with no budget left, as rollout() counts them
+            "own_budget": i32 [N]         budget - used of the start state: the env's own column where it is in 0 .. B
+            "alert_days": (schedules=True) bool [N, B + 1, T] by day of the episode, or with packed=True the kernel's
+                                          int32 [N, B + 1, ceil(T / 32)] words (the 4 GiB cap of hindsight_budget_curve())
+        Envs finished in the start state give rows of 0 and empty schedules.
+        The reward and the policy read the budget through four run-time slots only, and the fp64 chains run in slot
+        order: per env-day the table row is gathered once and the three chains run once over slots 0..23; per budget
+        only the tail runs (w2a_policy_curve_linear, include/w2a.h) -- against B + 1 reset(budget=b) + rollout() calls.
+        start_state (default: the env's own state) is taken with the checks of hindsight_budget_curve() and goes to
+        the kernel the same way, as decoded int32 arrays: the env's packed state is not read. The first decision needs
+        the row the agent holds. For the env's own state (start_state None, or a state() dict equal to the current
+        state) it is read from the observation buffer, which must be current (RuntimeError as rollout(linear)); column
+        b puts float(b) in place of that row's remaining_budget column. For any other start_state the buffer does not
+        belong to it, and the call is refused (ValueError) unless every live env of it is at t == 0 with used == 0,
+        streak == 0 and an empty 14-day window: there the held row is day 0's table row with lag 0 and streak 0, which
+        the kernel rebuilds.
+        The call changes nothing: state, observation buffer, statistics and status word stay as they were, and a
+        following rollout() sees the same episodes. ValueError, before anything touches a device, for kind "mlp" (a
+        later addition: its first layer shares the same way, in a kernel of its own), a "lookahead" key,
+        reward_mode="posterior_mean", fixes other than "budget", a max_budget that is not an int in 0..1023,
+        n_steps < 1, an env that needs a reset, and whatever rollout(linear) refuses of the policy."""
+        who = "policy_budget_curve()"
+        kind = policy.get("kind") if isinstance(policy, dict) else None
+        if kind == "mlp":
+            raise ValueError(f"{who} takes kind 'linear' only; the mlp kind is a later addition (its first layer's "
+                             "table-sourced k-steps share the same way, in a kernel of its own)")
+        if kind != "linear":
+            raise ValueError(f"{who} takes a policy dict of kind 'linear', got {kind!r}")
+        if policy.get("lookahead") is not None:
+            raise ValueError(f"{who} does not take a 'lookahead' policy: its kernel does not read the lookahead inputs")
+        if self._pm:
+            raise ValueError(f"{who} needs reward_mode='sampled', not 'posterior_mean'")
+        if self.fixes - {"budget"}:
+            raise ValueError(f"{who} needs faithful observations; fixes {sorted(self.fixes - {'budget'})} change what "
+                             "the observation is")
+        B = self._curve_check(who, max_budget, schedules, packed)
+        steps = self._hs_steps(n_steps, who, strict=True)
+        if self._needs_reset:
+            raise ValueError(f"{who}: the env needs a reset(): there is no state to start from")
+        ct, n, dev = self.ct, self.num_envs, self.device
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _ffi.W2AError(f"{who}: the stream is recording a hipGraph; the call compares the start state with "
+                                "the env's own on the host")
+        gate = _policy.check_allowed_days(policy, n, ct.T, dev, who)
+        lin = _check_learned(self, policy)
+        own = start_state is None
+        if own:
+            st = self._state_packed(_PC_FIELDS)[1]
+        else:
+            st = self._hs_start_state(start_state, _PC_FIELDS)
+            cur = self._state_packed(_PC_FIELDS)[1]
+            own = all(torch.equal(st[k], cur[k]) for k in _PC_FIELDS)
+            if not own:
+                live = (st["finished"] == 0) & (st["t"] < st["n_days"])
+                fresh = (st["t"] == 0) & (st["used"] == 0) & (st["streak"] == 0) & (st["hist14"] == 0)
+                if bool((live & ~fresh).any()):
+                    raise ValueError(f"{who}: start_state is not the env's current state, so the observation buffer does "
+                                     "not hold its agents' rows; such a start is taken only where every live env is at "
+                                     "t == 0 with used == 0 (the held row is then rebuilt from day 0's table row)")
+        if own and not self._obs_current:
+            raise RuntimeError(f"{who} reads the observation buffer, which does not hold the agents' current rows "
+                               "(write_obs=False, a built-in rollout or load_state_dict since the last step()/reset()): "
+                               "call step() or reset() first")
+        lp = _ffi.LinearPolicy()
+        lp.weight, lp.bias = lin.weight_slots.data_ptr(), lin.bias.data_ptr()
+        lp.group = None if lin.group is None else lin.group.data_ptr()
+        lp.n_groups, lp.sample, lp.require_budget, lp.seed = lin.n_groups, int(lin.sample), int(lin.require_budget), lin.seed
+        words = (ct.T + 31) // 32
+        ret = torch.empty((n, B + 1), dtype=torch.float32, device=dev)
+        alerts = torch.empty((n, B + 1), dtype=torch.int32, device=dev)
+        over = torch.empty((n, B + 1), dtype=torch.int32, device=dev)
+        masks = torch.empty((n, B + 1, words), dtype=torch.int32, device=dev) if schedules else None
+        with torch.cuda.device(dev):
+            ws_bytes = self._lib.w2a_policy_curve_workspace_bytes(self._h, steps, B)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            v = _ffi.StateView()
+            for k in _PC_FIELDS:
+                setattr(v, k, st[k].data_ptr())
+            args = (self._h, C.byref(lp), C.byref(v), steps, B, self._obs.data_ptr() if own else None, ret.data_ptr(),
+                    alerts.data_ptr(), over.data_ptr(), None if masks is None else masks.data_ptr(), words,
+                    ws.data_ptr(), ws_bytes, self._stream())
+            if gate is None:
+                _ffi.check(self._lib.w2a_policy_curve_linear(*args), "w2a_policy_curve_linear")
+            else:
+                _ffi.check(self._lib.w2a_policy_curve_linear_gated(*args, gate.data_ptr(), int(gate.shape[1])),
+                           "w2a_policy_curve_linear_gated")
+        self._keep_curve = (st, gate, ws, lin)  # the launch is asynchronous
+        out = self._curve_out(ret, alerts, masks, st, schedules, packed)
+        out["attempts_over_budget"] = over
+        return out
+
     def _curve_check(self, who: str, max_budget, schedules: bool, packed: bool) -> int:
         """max_budget as an int in 0 .. 1023 and the byte cap of the schedules"""
         if isinstance(max_budget, bool) or not isinstance(max_budget, (int, np.integer)) or \
@@ -2365,12 +2470,14 @@ class HeatAlertVecEnv(_VectorEnvBase):
             raise ValueError(f"{who}: some coefficient row has a nonzero slot-27 (alert_2wks of the agent) term; the "
                              "(alerts, streak) DP is exact only without it")
 
-    def _hs_start_state(self, start_state: dict | None) -> dict:
-        """start_state (a state() dict; None: the current state) as the int32 [N] device arrays of _HS_FIELDS"""
+    def _hs_start_state(self, start_state: dict | None, fields=None) -> dict:
+        """start_state (a state() dict; None: the current state) as the int32 [N] device arrays of `fields` (default:
+        _HS_FIELDS)"""
+        fields = _HS_FIELDS if fields is None else fields
         if start_state is None:
-            return self._state_packed(_HS_FIELDS)[1]
+            return self._state_packed(fields)[1]
         n, st = self.num_envs, {}
-        for k in _HS_FIELDS:
+        for k in fields:
             if k not in start_state:
                 raise KeyError(f"start_state lacks {k!r} (pass a state() dict)")
             st[k] = torch.as_tensor(start_state[k], device=self.device).to(torch.int32).contiguous()
@@ -2558,6 +2665,8 @@ _PR_FIELDS = ("t", "used", "streak", "hist14", "budget", "n_days", "county_w", "
 # the start-state fields w2a_hindsight_optimum reads, and how many envs beyond the LDS budget one launch serves
 _HS_FIELDS = ("t", "used", "streak", "budget", "n_days", "county_w", "year_i", "coef_col", "sample", "finished")
 _HS_BIG_ENVS = 64
+# what policy_budget_curve() takes of a start state: the hindsight fields, the 14-day window, the episode number
+_PC_FIELDS = _HS_FIELDS + ("hist14", "episode_no")
 # hindsight_budget_curve(): the largest max_budget w2a_hindsight_curve takes, and the bytes of schedules one call returns
 _CURVE_MAX_BUDGET = 1023
 _CURVE_SCHEDULE_BYTES = 4 << 30
