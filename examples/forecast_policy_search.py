@@ -7,8 +7,13 @@
    iterations; prints the elite mean return of both per iteration.
 2. Behaviour cloning of hindsight_optimum()["alert_days"] (schedules that depend on future weather) with
    imitation_gradient(), with and without the lookahead inputs: the log-likelihood the forecast-aware policy reaches.
+3. With ``--forecast-error E`` (one MAE in the feature's units for every lead, or ``reference`` for the older
+   reference env's profile 2.5, 3.0, .., 7.0, which suits a feature in degrees) the search also runs with
+   ``"error": E`` in the key -- forecasts perturbed by U(-1, 1) * MAE[k] -- and the 2 x 2 table is printed: searched
+   without / with error, each evaluated without / with error. How much of the gain survives realistic forecast error,
+   and does searching under error buy robustness?
 
-    python examples/forecast_policy_search.py [--days 3]           # needs one ROCm GPU
+    python examples/forecast_policy_search.py [--days 3] [--forecast-error 0.1 --error-seed 1]   # needs one ROCm GPU
 """
 import argparse
 import os
@@ -27,9 +32,15 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--groups", type=int, default=128)
 ap.add_argument("--per", type=int, default=2048)
 ap.add_argument("--clone-steps", type=int, default=60)
+ap.add_argument("--forecast-error", default=None, help="a number (one MAE for every lead) or 'reference'")
+ap.add_argument("--error-seed", type=int, default=0)
 args = ap.parse_args()
 D, G, per = args.days, args.groups, args.per
 spec = {"feature": "heat_qi", "days": D}
+noisy = None
+if args.forecast_error is not None:
+    mae = [2.0 + 0.5 * k for k in range(1, D + 1)] if args.forecast_error == "reference" else float(args.forecast_error)
+    noisy = dict(spec, error=mae, error_seed=args.error_seed)
 
 data = synth.make_synth("linear", n_fips=64, years=[2006, 2007, 2008], n_samples=20, seed=0, extra_confounder_fips=6)
 tables = compile_from_synth(data)
@@ -42,7 +53,8 @@ scale_obs = obs0.std(dim=0).clamp_min(0.1).cpu().numpy().astype(np.float64)
 scale_look = env.lookahead_features(spec).std(dim=0).clamp_min(1e-3).cpu().numpy().astype(np.float64)
 
 
-def cem(look: bool, seed=0):
+def cem(look, seed=0):
+    """look: False, or the "lookahead" value to search with. Returns the elite means and the final mean policy."""
     width = k + (D if look else 0)
     scale = np.concatenate([scale_obs, scale_look]) if look else scale_obs
     rng = np.random.default_rng(seed)
@@ -54,18 +66,27 @@ def cem(look: bool, seed=0):
         pol = {"kind": "linear", "weight": (theta[:, :width] / scale).astype(np.float32),
                "bias": theta[:, width].astype(np.float32), "group": group, "require_budget": True}
         if look:
-            pol["lookahead"] = spec
+            pol["lookahead"] = look
         score = env.rollout(pol)["group_mean_return"].cpu().numpy()
         top = np.argsort(score)[-elite:]
         mu, sd = theta[top].mean(axis=0), theta[top].std(axis=0) + 0.05
         hist.append(score[top].mean())
-    return hist
+    return hist, ((mu[:width] / scale).astype(np.float32)[None, :], mu[width:].astype(np.float32))
 
 
-plain, aware = cem(False), cem(True)
+(plain, _), (aware, best_clean) = cem(False), cem(spec)
 print(f"CEM, {G} candidates x {per} envs, elite mean return per iteration (lookahead: {spec})")
 for it, (a, b) in enumerate(zip(plain, aware)):
     print(f"  iter {it:2d}   observation only {a:9.3f}   with lookahead {b:9.3f}")
+
+if noisy is not None:
+    _, best_noisy = cem(noisy)
+    print(f"searched / evaluated with forecast error {noisy['error']} (seed {noisy['error_seed']}): mean return")
+    print(f"  {'':24s} {'evaluated clean':>16s} {'evaluated noisy':>16s}")
+    for name, (w, b) in (("searched without error", best_clean), ("searched with error", best_noisy)):
+        row = [float(env.rollout({"kind": "linear", "weight": w, "bias": b, "require_budget": True,
+                                  "lookahead": la})["return"].mean()) for la in (spec, noisy)]
+        print(f"  {name:24s} {row[0]:16.3f} {row[1]:16.3f}")
 
 # ---- cloning the hindsight optimum: one group, normalised gradient ascent on the mean log-likelihood
 clone = HeatAlertVecEnv(8192, tables=tables, similar_climate_counties=True, autoreset="disabled")

@@ -1191,6 +1191,60 @@ int w2a_lookahead_imitation_gradient_linear(w2a_env *env, const w2a_linear_polic
                                             const w2a_lookahead *lookahead, const uint32_t *allowed_days,
                                             int32_t allowed_words);
 
+/* Forecast error: lookahead inputs as the older reference env forms them with forecast_error > 0 (its default; additions
+ * to ABI 18, nothing above changes). The w2a_forecast_* entry points take a w2a_lookahead block and a w2a_forecast_error
+ * block (host memory, read during the call). For the held row's day r and lead k = 1 .. days,
+ *     f_k = fmaf(U(r, k), mae[k - 1], h(r + k)) - h(r)     one f32 fma, then one f32 subtraction; h(r) itself is exact
+ *     f_k = +0 where r + k >= n_days of that env (no noise)
+ * and where mae[k - 1] == 0 the term is skipped, h(r + k) is taken as it is (the fma would turn a -0 into +0): with
+ * every entry zero the inputs, and so every output, are the bits of the w2a_lookahead_* call, for every finite h.
+ *     U(r, k) = (float)(word >> 8) * 2^-23 - 1.0f       24 bits, exact in f32, in [-1, 1 - 2^-23]
+ *     x       = w2a_mix64(stream + (uint64_t)(8 * r + ((k - 1) >> 1) + 1) * 0x9E3779B97F4A7C15)
+ *     word    = x >> 32 for odd k, (uint32_t)x for even k          (one hash serves the two leads 2j + 1, 2j + 2)
+ *     stream  = rng_stream(seed ^ 0xC3C3C3C33C3C3C3C, env_gid0 + env id, episode number)
+ * with w2a_mix64 / rng_stream the pair of the device reset and of the Bernoulli policies, whose stream uses another
+ * constant: equal seeds still give independent draws. A draw depends on (seed, global env id, episode number, held
+ * day, lead) and on nothing else -- not on the schedule, the call boundaries, the visiting order or the shard. So calls
+ * of k and S - k days equal one of S days, the gradient kernels' passes see the rollout's inputs, and handles that
+ * cover the same global ids draw the same noise.
+ *   mae   mean absolute error per lead in the feature's own units, >= 0 and finite for the first `days` entries (the
+ *         reference's profile for a feature in degrees: 2.5, 3.0, .., 7.0); later entries are not read
+ *   seed  any value
+ * w2a_forecast_rollout_linear / w2a_forecast_rollout_mlp: the arguments of w2a_lookahead_rollout_*_gated with
+ * allowed_days nullable (NULL: no gate) and the block. w2a_forecast_policy_gradient_linear /
+ * w2a_forecast_imitation_gradient_linear: the arguments of their w2a_lookahead_* forms and the block.
+ * w2a_forecast_features writes out = device f32 [num_envs][days], the inputs of the rows the envs hold now (weight is
+ * not read); it changes no state.
+ * W2A_ERR_ARG where the w2a_lookahead_* form refuses (same order), then for a NULL block, then for a negative or
+ * non-finite mae among the first `days`. */
+typedef struct w2a_forecast_error {
+  float mae[W2A_LOOKAHEAD_PAD];
+  uint64_t seed;
+} w2a_forecast_error;
+int w2a_forecast_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                                float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words, float *last_return,
+                                float *ret_snapshot, void *stream, const w2a_lookahead *lookahead,
+                                const uint32_t *allowed_days, int32_t allowed_words, const w2a_forecast_error *error);
+int w2a_forecast_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                             int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                             uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                             void *stream, const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                             int32_t allowed_words, const w2a_forecast_error *error);
+int w2a_forecast_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline,
+                                        int32_t n_steps, const float *obs, float *grad, void *workspace,
+                                        size_t workspace_bytes, void *stream, const w2a_lookahead *lookahead,
+                                        const uint32_t *allowed_days, int32_t allowed_words,
+                                        const w2a_forecast_error *error);
+int w2a_forecast_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                           int32_t mask_words, const float *env_weight, const float *day_weight,
+                                           int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                           float *loglik, int32_t *days, void *stream,
+                                           const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                           int32_t allowed_words, const w2a_forecast_error *error);
+int w2a_forecast_features(w2a_env *env, const w2a_lookahead *lookahead, const w2a_forecast_error *error, float *out,
+                          void *stream);
+
 /* Hindsight values along a GIVEN schedule (additions to ABI 18, nothing above changes): what the DP of
  * w2a_hindsight_optimum says in the states a caller's schedule reaches, not only on the optimum's own path -- the
  * expert labels of DAgger / hindsight relabelling and the share of every day's decision in the regret.

@@ -45,6 +45,8 @@ SYMBOLS = [
     "w2a_lookahead_rollout_linear", "w2a_lookahead_rollout_linear_gated", "w2a_lookahead_rollout_mlp",
     "w2a_lookahead_rollout_mlp_gated", "w2a_lookahead_policy_gradient_linear",
     "w2a_lookahead_imitation_gradient_linear",
+    "w2a_forecast_rollout_linear", "w2a_forecast_rollout_mlp", "w2a_forecast_policy_gradient_linear",
+    "w2a_forecast_imitation_gradient_linear", "w2a_forecast_features",
     "w2a_hindsight_along", "w2a_relabel_imitation_linear", "w2a_relabel_imitation_mlp",
     "w2a_hindsight_curve_workspace_bytes", "w2a_hindsight_curve", "w2a_hindsight_curve_gated",
     "w2a_hindsight_posterior_workspace_bytes", "w2a_hindsight_posterior", "w2a_hindsight_posterior_gated",
@@ -80,6 +82,11 @@ class MlpPolicy(C.Structure):
 class Lookahead(C.Structure):
     """w2a_lookahead: the series table, its stride, D and (linear kind) the lookahead weights [G][12]."""
     _fields_ = [("series", C.c_void_p), ("stride", C.c_int32), ("days", C.c_int32), ("weight", C.c_void_p)]
+
+
+class ForecastError(C.Structure):
+    """w2a_forecast_error: the MAE of every lead (k = 1 first, the first D entries are read) and the error seed."""
+    _fields_ = [("mae", C.c_float * 12), ("seed", C.c_uint64)]
 
 
 MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}  # W2A_MLP_TANH, W2A_MLP_RELU
@@ -324,6 +331,17 @@ def load(build_if_missing: bool = True):
     lib.w2a_lookahead_policy_gradient_linear.argtypes = lib.w2a_policy_gradient_linear.argtypes + look + [vp, i32]
     lib.w2a_lookahead_imitation_gradient_linear.restype = C.c_int
     lib.w2a_lookahead_imitation_gradient_linear.argtypes = lib.w2a_imitation_gradient_linear_weighted.argtypes + look + [vp, i32]
+    ferr = [C.POINTER(ForecastError)]
+    lib.w2a_forecast_rollout_linear.restype = C.c_int
+    lib.w2a_forecast_rollout_linear.argtypes = lib.w2a_lookahead_rollout_linear_gated.argtypes + ferr
+    lib.w2a_forecast_rollout_mlp.restype = C.c_int
+    lib.w2a_forecast_rollout_mlp.argtypes = lib.w2a_lookahead_rollout_mlp_gated.argtypes + ferr
+    lib.w2a_forecast_policy_gradient_linear.restype = C.c_int
+    lib.w2a_forecast_policy_gradient_linear.argtypes = lib.w2a_lookahead_policy_gradient_linear.argtypes + ferr
+    lib.w2a_forecast_imitation_gradient_linear.restype = C.c_int
+    lib.w2a_forecast_imitation_gradient_linear.argtypes = lib.w2a_lookahead_imitation_gradient_linear.argtypes + ferr
+    lib.w2a_forecast_features.restype = C.c_int
+    lib.w2a_forecast_features.argtypes = [vp] + look + ferr + [vp, vp]
     # hindsight values along a schedule: start, n_steps, the schedule, the nullable gate, gain, expert bitmap, regret,
     # the nullable value and loss, the workspace and the stream
     lib.w2a_hindsight_along.restype = C.c_int

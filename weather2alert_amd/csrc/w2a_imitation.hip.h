@@ -89,7 +89,9 @@ __device__ __forceinline__ double im_log_pi(double z, uint32_t a) {
 // from the statements it had before.
 // LABELS (w2a_relabel_imitation_linear): the schedule still forces the env and decides m_s; delta_s and the
 // log-likelihood take a*_s from ia.im.labels. LABELS = false scores the schedule's own bit, as before.
-template <bool GATE, bool LOOK = false, bool LABELS = false>
+// NOISE (w2a_forecast_imitation_gradient_linear; needs LOOK, no LABELS form): the inputs carry the forecast error of
+// la.look.mae, as k_rollout_linear<.., NOISE> forms them.
+template <bool GATE, bool LOOK = false, bool LABELS = false, bool NOISE = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArgs ia) {
   const LinearRolloutArgs &la = ia.l;
   const RolloutArgs &a = la.r;
@@ -124,6 +126,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
   }
   const float *lser = nullptr;
   if constexpr (LOOK) lser = look_series(la.look, cold.x);
+  uint64_t estream = 0;
+  if constexpr (NOISE) estream = look_noise_stream(la.look, (uint64_t)(a.gid0 + e), cold.w);
   double gl[W2A_LOOK_MAX];  // LOOK: the lookahead inputs' columns
 #pragma unroll
   for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = 0.0;
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
     for (int k = 0; k < RO64_SLOTS; ++k)
       if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
     if constexpr (LOOK) {
-      look_inputs(la.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+      look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t > 0 ? t - 1 : 0u, ndays, lf, estream);
       z = look_logit(la.look, lf, lw, z);
     }
     lab = im_label(ia.im, e, t, lab_word, lab_idx);
@@ -199,7 +203,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_imitation_linear(const ImLinearArg
       zp = fma((double)xv[k], (double)wp[k], zp);
     }
     if constexpr (LOOK) {  // xv[] is day t's row
-      look_inputs(la.look, lser, t, ndays, lf);
+      look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t, ndays, lf, estream);
       zp = look_logit(la.look, lf, lw, zp);
     }
     if (active) {

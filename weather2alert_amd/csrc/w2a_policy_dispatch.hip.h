@@ -206,6 +206,21 @@ static void fill_lookahead(const w2a_lookahead *look, LookArgs &lk) {
   lk.series = look->series; lk.stride = look->stride; lk.days = look->days; lk.weight = look->weight;
 }
 
+// the forecast-error block of the w2a_forecast_* entry points: checked after the lookahead block
+static int check_forecast_error(const char *fn, const w2a_lookahead *look, const w2a_forecast_error *err) {
+  if (!err) return fail(W2A_ERR_ARG, "%s: NULL forecast error", fn);
+  for (int k = 0; k < look->days; ++k)
+    if (!isfinite(err->mae[k]) || err->mae[k] < 0.0f)
+      return fail(W2A_ERR_ARG, "%s: forecast error mae must be finite and non-negative", fn);
+  return W2A_OK;
+}
+
+// entries past `days` are never read by the kernels; they are passed as zeros
+static void fill_forecast_error(const w2a_lookahead *look, const w2a_forecast_error *err, LookArgs &lk) {
+  lk.err_seed = err->seed;
+  for (int k = 0; k < W2A_LOOK_PAD; ++k) lk.mae[k] = k < look->days ? err->mae[k] : 0.0f;
+}
+
 // REFUSE_WHILE_CAPTURING with the name at run time: every body's last refusal
 static int refuse_while_capturing(const char *fn, void *stream) {
   if (stream_is_capturing((hipStream_t)stream))
@@ -472,17 +487,20 @@ static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy 
                           int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
                           uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
                           void *stream, const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
-                          int32_t gate_words = 0, bool looking = false, const w2a_lookahead *look = nullptr) {
+                          int32_t gate_words = 0, bool looking = false, const w2a_lookahead *look = nullptr,
+                          bool noisy = false, const w2a_forecast_error *ferr = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_obs(fn, obs));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, (alert_mask || attempt_mask) ? MASK_ROLLOUT : MASK_NONE, mask_words));
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
   if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
+  if (noisy) W2A_CHECK(check_forecast_error(fn, look, ferr));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   LinearRolloutArgs la;
   memset(&la, 0, sizeof(la));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, la));
   if (looking) fill_lookahead(look, la.look);
+  if (noisy) fill_forecast_error(look, ferr, la.look);
   la.r.pol.require_budget = policy->require_budget;
   la.r.pol.seed = policy->seed;
   la.r.order = env->order;
@@ -508,7 +526,17 @@ static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy 
     if (gated) hipLaunchKernelGGL((k_rollout_linear<M, S, false, true, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr); \
     else hipLaunchKernelGGL((k_rollout_linear<M, S, false, false, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr);      \
   } while (0)
-  if (looking) {  // no trajectory: the w2a_lookahead_* exports take none
+#define W2A_LAUNCH_LINEAR_NOISE(M, S)                                                                                     \
+  do {                                                                                                                    \
+    if (gated) hipLaunchKernelGGL((k_rollout_linear<M, S, false, true, true, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr); \
+    else hipLaunchKernelGGL((k_rollout_linear<M, S, false, false, true, true>), dim3(g64), dim3(BLOCK), 0, s, la, tr);      \
+  } while (0)
+  if (noisy) {  // w2a_forecast_rollout_linear
+    if (masks && policy->sample) W2A_LAUNCH_LINEAR_NOISE(true, true);
+    else if (masks) W2A_LAUNCH_LINEAR_NOISE(true, false);
+    else if (policy->sample) W2A_LAUNCH_LINEAR_NOISE(false, true);
+    else W2A_LAUNCH_LINEAR_NOISE(false, false);
+  } else if (looking) {  // no trajectory: the w2a_lookahead_* exports take none
     if (masks && policy->sample) W2A_LAUNCH_LINEAR_LOOK(true, true);
     else if (masks) W2A_LAUNCH_LINEAR_LOOK(true, false);
     else if (policy->sample) W2A_LAUNCH_LINEAR_LOOK(false, true);
@@ -526,6 +554,7 @@ static int rollout_linear(const char *fn, w2a_env *env, const w2a_linear_policy 
   }
 #undef W2A_LAUNCH_LINEAR
 #undef W2A_LAUNCH_LINEAR_LOOK
+#undef W2A_LAUNCH_LINEAR_NOISE
   HIP_TRY(hipGetLastError());
   end_call(env, s);
   return W2A_OK;
@@ -576,11 +605,23 @@ int w2a_lookahead_rollout_linear_gated(w2a_env *env, const w2a_linear_policy *po
                         lookahead);
 }
 
+// allowed_days nullable: NULL runs the ungated NOISE forms
+int w2a_forecast_rollout_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t n_steps, float *obs,
+                                float *ret_out, int32_t *alerts_out, int32_t *attempts_over_budget,
+                                uint32_t *alert_mask, uint32_t *attempt_mask, int32_t mask_words, float *last_return,
+                                float *ret_snapshot, void *stream, const w2a_lookahead *lookahead,
+                                const uint32_t *allowed_days, int32_t allowed_words, const w2a_forecast_error *error) {
+  return rollout_linear("w2a_forecast_rollout_linear", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask,
+                        attempt_mask, mask_words, last_return, ret_snapshot, stream, nullptr, allowed_days != nullptr, allowed_days,
+                        allowed_words, true, lookahead, true, error);
+}
+
 static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
                        int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask, uint32_t *attempt_mask,
                        int32_t mask_words, float *last_return, float *ret_snapshot, void *stream,
                        const w2a_trajectory *traj, bool gated = false, const uint32_t *gate = nullptr,
-                       int32_t gate_words = 0, bool looking = false, const w2a_lookahead *look = nullptr) {
+                       int32_t gate_words = 0, bool looking = false, const w2a_lookahead *look = nullptr,
+                       bool noisy = false, const w2a_forecast_error *ferr = nullptr) {
   W2A_CHECK(check_mlp_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_obs(fn, obs));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, (alert_mask || attempt_mask) ? MASK_ROLLOUT : MASK_NONE, mask_words));
@@ -591,6 +632,7 @@ static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *polic
     if ((int64_t)policy->n_groups * W2A_MLP_LOOKAHEAD_STRIDE((int64_t)policy->width, policy->n_layers) >= (1ll << 31))
       return fail(W2A_ERR_ARG, "%s: n_groups * block size must stay below 2^31 floats", fn);
   }
+  if (noisy) W2A_CHECK(check_forecast_error(fn, look, ferr));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   MlpRolloutArgs ma;
   memset(&ma, 0, sizeof(ma));
@@ -599,6 +641,7 @@ static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *polic
     fill_lookahead(look, ma.look);
     ma.stride = (int32_t)W2A_MLP_LOOKAHEAD_STRIDE((int64_t)policy->width, policy->n_layers);
   }
+  if (noisy) fill_forecast_error(look, ferr, ma.look);
   ma.r.pol.require_budget = policy->require_budget;
   ma.r.pol.seed = policy->seed;
   ma.r.order = policy->order ? mlp_own_order(policy) : env->order;  // the rollout writes state: the handle's order serves too
@@ -614,7 +657,10 @@ static int rollout_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *polic
     // group-major order keeps the kernel's group loop short and the rows are stored directly
     if (policy->n_groups == 1) ma.r.order = nullptr;
   }
-  if (looking)
+  if (noisy)
+    dispatch_mlp_shape(policy->width, policy->n_layers,
+                       [&](auto W, auto L) { launch_rollout_mlp_forecast<W(), L()>(ma, masks, smp, g64, s); });
+  else if (looking)
     dispatch_mlp_shape(policy->width, policy->n_layers,
                        [&](auto W, auto L) { launch_rollout_mlp_lookahead<W(), L()>(ma, masks, smp, g64, s); });
   else
@@ -669,6 +715,17 @@ int w2a_lookahead_rollout_mlp_gated(w2a_env *env, const w2a_mlp_policy *policy, 
                      lookahead);
 }
 
+// allowed_days nullable: NULL runs the ungated NOISE forms
+int w2a_forecast_rollout_mlp(w2a_env *env, const w2a_mlp_policy *policy, int32_t n_steps, float *obs, float *ret_out,
+                             int32_t *alerts_out, int32_t *attempts_over_budget, uint32_t *alert_mask,
+                             uint32_t *attempt_mask, int32_t mask_words, float *last_return, float *ret_snapshot,
+                             void *stream, const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                             int32_t allowed_words, const w2a_forecast_error *error) {
+  return rollout_mlp("w2a_forecast_rollout_mlp", env, policy, n_steps, obs, ret_out, alerts_out, attempts_over_budget, alert_mask,
+                     attempt_mask, mask_words, last_return, ret_snapshot, stream, nullptr, allowed_days != nullptr, allowed_days,
+                     allowed_words, true, lookahead, true, error);
+}
+
 // ---- policy gradients ------------------------------------------------------------------------------------------------
 // As found: these two bodies read the canonical state words (the rollout that follows would make them current itself),
 // change nothing else, and -- unlike the ten others -- do not call end_call.
@@ -684,7 +741,8 @@ static int check_policy_gradient(const char *fn, int32_t baseline, const float *
 static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear_policy *policy, int32_t baseline, int32_t n_steps,
                                   const float *obs, float *grad, void *workspace, size_t workspace_bytes, void *stream,
                                   bool gated, const uint32_t *gate, int32_t gate_words, bool looking = false,
-                                  const w2a_lookahead *look = nullptr) {
+                                  const w2a_lookahead *look = nullptr, bool noisy = false,
+                                  const w2a_forecast_error *ferr = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_MUST_BE_1));
   W2A_CHECK(check_policy_gradient(fn, baseline, obs, grad, workspace));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_NONE, 0));
@@ -692,11 +750,13 @@ static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear
     return fail(W2A_ERR_ARG, "%s: workspace smaller than w2a_policy_gradient_workspace_bytes", fn);
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
   if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
+  if (noisy) W2A_CHECK(check_forecast_error(fn, look, ferr));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   PolicyGradArgs ga;
   memset(&ga, 0, sizeof(ga));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, ga.l));
   if (looking) fill_lookahead(look, ga.l.look);
+  if (noisy) fill_forecast_error(look, ferr, ga.l.look);
   ga.l.r.pol.require_budget = policy->require_budget;
   ga.l.r.pol.seed = policy->seed;
   ga.l.r.order = env->order;
@@ -707,7 +767,9 @@ static int policy_gradient_linear(const char *fn, w2a_env *env, const w2a_linear
   hipStream_t s = (hipStream_t)stream;
   if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
   const unsigned g64 = grid64(env);
-  if (looking && gated) hipLaunchKernelGGL((k_policy_gradient_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
+  if (noisy && gated) hipLaunchKernelGGL((k_policy_gradient_linear<true, true, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
+  else if (noisy) hipLaunchKernelGGL((k_policy_gradient_linear<false, true, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
+  else if (looking && gated) hipLaunchKernelGGL((k_policy_gradient_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
   else if (looking) hipLaunchKernelGGL((k_policy_gradient_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, ga);
   else if (gated) hipLaunchKernelGGL(k_policy_gradient_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ga);
   else hipLaunchKernelGGL(k_policy_gradient_linear<false>, dim3(g64), dim3(BLOCK), 0, s, ga);
@@ -735,6 +797,16 @@ int w2a_lookahead_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *
                                          const uint32_t *allowed_days, int32_t allowed_words) {
   return policy_gradient_linear("w2a_lookahead_policy_gradient_linear", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream,
                                 allowed_days != nullptr, allowed_days, allowed_words, true, lookahead);
+}
+
+// allowed_days nullable: NULL runs the ungated NOISE form
+int w2a_forecast_policy_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, int32_t baseline,
+                                        int32_t n_steps, const float *obs, float *grad, void *workspace,
+                                        size_t workspace_bytes, void *stream, const w2a_lookahead *lookahead,
+                                        const uint32_t *allowed_days, int32_t allowed_words,
+                                        const w2a_forecast_error *error) {
+  return policy_gradient_linear("w2a_forecast_policy_gradient_linear", env, policy, baseline, n_steps, obs, grad, workspace, workspace_bytes, stream,
+                                allowed_days != nullptr, allowed_days, allowed_words, true, lookahead, true, error);
 }
 
 static int policy_gradient_mlp(const char *fn, w2a_env *env, const w2a_mlp_policy *policy, int32_t baseline, int32_t n_steps,
@@ -784,19 +856,22 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
                                      float *grad, float *loglik, int32_t *days, void *stream, bool gated = false,
                                      const uint32_t *gate = nullptr, int32_t gate_words = 0, bool looking = false,
                                      const w2a_lookahead *look = nullptr, bool relabel = false,
-                                     const uint32_t *labels = nullptr) {
+                                     const uint32_t *labels = nullptr, bool noisy = false,
+                                     const w2a_forecast_error *ferr = nullptr) {
   W2A_CHECK(check_linear_policy_struct(fn, policy, n_steps, SAMPLE_0_OR_1));
   W2A_CHECK(check_imitation(fn, alert_mask, obs, grad, loglik, days));
   W2A_CHECK(check_day_weight(fn, day_weight, day_weight_days, n_steps));
   W2A_CHECK(check_handle_common(fn, env, FIXES_CHANGE_OBS, MASK_SCHEDULE, mask_words));
   if (gated) W2A_CHECK(check_gate(fn, env, gate, gate_words));
   if (looking) W2A_CHECK(check_lookahead(fn, env, look, true));
+  if (noisy) W2A_CHECK(check_forecast_error(fn, look, ferr));
   W2A_CHECK(refuse_while_capturing(fn, stream));
   if (relabel && !labels) return fail(W2A_ERR_ARG, "%s: NULL labels (the actions to score along the schedule)", fn);
   ImLinearArgs ia;
   memset(&ia, 0, sizeof(ia));
   W2A_CHECK(fill_linear(fn, env, policy, n_steps, obs, gate, gate_words, ia.l));
   if (looking) fill_lookahead(look, ia.l.look);
+  if (noisy) fill_forecast_error(look, ferr, ia.l.look);
   ia.l.r.pol.require_budget = policy->require_budget;
   ia.l.r.order = env->order;
   fill_imitation(ia.im, alert_mask, mask_words, env_weight, day_weight, loglik, days);
@@ -807,6 +882,8 @@ static int imitation_gradient_linear(const char *fn, w2a_env *env, const w2a_lin
   const unsigned g64 = grid64(env);
   if (relabel && gated) hipLaunchKernelGGL((k_imitation_linear<true, false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
   else if (relabel) hipLaunchKernelGGL((k_imitation_linear<false, false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  else if (noisy && gated) hipLaunchKernelGGL((k_imitation_linear<true, true, false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
+  else if (noisy) hipLaunchKernelGGL((k_imitation_linear<false, true, false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
   else if (looking && gated) hipLaunchKernelGGL((k_imitation_linear<true, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
   else if (looking) hipLaunchKernelGGL((k_imitation_linear<false, true>), dim3(g64), dim3(BLOCK), 0, s, ia);
   else if (gated) hipLaunchKernelGGL(k_imitation_linear<true>, dim3(g64), dim3(BLOCK), 0, s, ia);
@@ -852,6 +929,42 @@ int w2a_lookahead_imitation_gradient_linear(w2a_env *env, const w2a_linear_polic
   return imitation_gradient_linear("w2a_lookahead_imitation_gradient_linear", env, policy, alert_mask, mask_words,
                                    env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
                                    allowed_days != nullptr, allowed_days, allowed_words, true, lookahead);
+}
+
+// day_weight and allowed_days nullable (= 1, = no gate)
+int w2a_forecast_imitation_gradient_linear(w2a_env *env, const w2a_linear_policy *policy, const uint32_t *alert_mask,
+                                           int32_t mask_words, const float *env_weight, const float *day_weight,
+                                           int32_t day_weight_days, int32_t n_steps, const float *obs, float *grad,
+                                           float *loglik, int32_t *days, void *stream,
+                                           const w2a_lookahead *lookahead, const uint32_t *allowed_days,
+                                           int32_t allowed_words, const w2a_forecast_error *error) {
+  return imitation_gradient_linear("w2a_forecast_imitation_gradient_linear", env, policy, alert_mask, mask_words,
+                                   env_weight, day_weight, day_weight_days, n_steps, obs, grad, loglik, days, stream,
+                                   allowed_days != nullptr, allowed_days, allowed_words, true, lookahead, false, nullptr,
+                                   true, error);
+}
+
+// the inputs of the rows the envs hold now, through look_inputs<true> (k_lookahead_features): reads the canonical state
+// words, changes nothing
+int w2a_forecast_features(w2a_env *env, const w2a_lookahead *lookahead, const w2a_forecast_error *error, float *out,
+                          void *stream) {
+  const char *fn = "w2a_forecast_features";
+  if (!env) return fail(W2A_ERR_ARG, "%s: NULL handle", fn);
+  if (!out) return fail(W2A_ERR_ARG, "%s: NULL out", fn);
+  W2A_CHECK(check_lookahead(fn, env, lookahead, false));
+  W2A_CHECK(check_forecast_error(fn, lookahead, error));
+  W2A_CHECK(refuse_while_capturing(fn, stream));
+  LookFeaturesArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.st = env->st; fa.n = env->n; fa.gid0 = env->gid0; fa.out = out;
+  fill_lookahead(lookahead, fa.look);
+  fill_forecast_error(lookahead, error, fa.look);
+  hipStream_t s = (hipStream_t)stream;
+  if (!ensure_canonical(env, s, fn)) return W2A_ERR_STATE;
+  hipLaunchKernelGGL(k_lookahead_features, dim3((unsigned)((env->n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, fa);
+  HIP_TRY(hipGetLastError());
+  end_call(env, s);
+  return W2A_OK;
 }
 
 // labels scored along the schedule that forces the env (DAgger); day_weight and allowed_days nullable (= 1, = no gate)

@@ -32,7 +32,9 @@ struct PolicyGradArgs {
 // LOOK (w2a_lookahead_policy_gradient_linear; GATE when its nullable allowed_days is given): pass 1 continues the logit chain over the lookahead
 // inputs as k_rollout_linear<.., LOOK> does; pass 2 rebuilds them for o_s from the series and keeps D more fp64
 // accumulators. LOOK = false compiles from the statements it had before.
-template <bool GATE, bool LOOK = false>
+// NOISE (w2a_forecast_policy_gradient_linear; needs LOOK): both passes form the inputs with the forecast error of
+// la.look.mae from the env's one stream, so pass 2 sees the inputs pass 1 and the rollout act on.
+template <bool GATE, bool LOOK = false, bool NOISE = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const PolicyGradArgs ga) {
   const LinearRolloutArgs &la = ga.l;
   const RolloutArgs &a = la.r;
@@ -53,6 +55,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
   int32_t n_valid = 0;  // days the env steps in this call
   const float *lser = nullptr;
   if constexpr (LOOK) lser = look_series(la.look, cold.x);
+  uint64_t estream = 0;
+  if constexpr (NOISE) estream = look_noise_stream(la.look, (uint64_t)(a.gid0 + e), cold.w);
   // ---------------------------------------------------------------- pass 1: k_rollout_linear's days
   {
     const uint32_t wrow = W_COL(cold.y) * (uint32_t)a.tb.n_samples + W_SAMPLE(cold.y);
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
       for (int k = 0; k < RO64_SLOTS; ++k)
         if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
       if constexpr (LOOK) {
-        look_inputs(la.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+        look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t > 0 ? t - 1 : 0u, ndays, lf, estream);
         z = look_logit(la.look, lf, lw, z);
       }
     }
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
         zp = fma(xk, (double)wp[k], zp);
       }
       if constexpr (LOOK) {
-        look_inputs(la.look, lser, t, ndays, lf);
+        look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t, ndays, lf, estream);
         zp = look_logit(la.look, lf, lw, zp);
       }
       if (!(xv[30] > 0.5f)) ze = -__builtin_inf();
@@ -172,7 +176,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
     g[31] = c;
     if constexpr (LOOK) {
       float lf[W2A_LOOK_MAX];
-      look_inputs(la.look, lser, t0 > 0 ? t0 - 1 : 0u, ndays, lf);
+      look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t0 > 0 ? t0 - 1 : 0u, ndays, lf, estream);
 #pragma unroll
       for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = c * (double)lf[k];
     }
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_policy_gradient_linear(const Polic
       g[31] += c;
       if constexpr (LOOK) {  // o_s is day t's row
         float lf[W2A_LOOK_MAX];
-        look_inputs(la.look, lser, t, ndays, lf);
+        look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t, ndays, lf, estream);
 #pragma unroll
         for (int k = 0; k < W2A_LOOK_MAX; ++k) gl[k] = fma(c, (double)lf[k], gl[k]);
       }

@@ -136,7 +136,9 @@ __device__ __forceinline__ void traj_store_tile(const Args &pa, const w2a_trajec
 // LOOK (w2a_lookahead_rollout_linear and its _gated form): the logit chain goes on over la.look.days lookahead inputs of
 // the held row's day (w2a_lookahead.hip.h): on entry from the state and the series, then every day next to zp. LOOK =
 // false compiles from the statements it had before; there is no RECORD form.
-template <bool MASKS, bool SAMPLE, bool RECORD, bool GATE, bool LOOK = false>
+// NOISE (w2a_forecast_rollout_linear; needs LOOK): the lookahead inputs carry the forecast error of la.look.mae
+// (w2a_lookahead.hip.h), drawn from a stream of the env's own that is derived once, before the day loop.
+template <bool MASKS, bool SAMPLE, bool RECORD, bool GATE, bool LOOK = false, bool NOISE = false>
 __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRolloutArgs la, const w2a_trajectory tr) {
   const RolloutArgs &a = la.r;
   const int64_t slot64 = (int64_t)logical_block(blockIdx.x, gridDim.x >> 3) * BLOCK + threadIdx.x;
@@ -181,6 +183,8 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
     look_weights(la.look, g, lw);
     lser = look_series(la.look, cold.x);
   }
+  uint64_t estream = 0;
+  if constexpr (NOISE) estream = look_noise_stream(la.look, (uint64_t)(a.gid0 + e), cold.w);
   const uint64_t pstream = SAMPLE ? rng_stream(a.pol.seed ^ 0xA5A5A5A55A5A5A5Aull, (uint64_t)(a.gid0 + e), cold.w) : 0ull;
   const uint32_t obs0 = e * (uint32_t)la.n_obs;  // first element of the env's observation row (host: n * n_obs < 2^31)
   if (RECORD && valid) traj_copy_row(la, tr, 0, e, obs0);  // slab 0: the row every env holds on entry
@@ -204,7 +208,7 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
     for (int k = 0; k < RO64_SLOTS; ++k)
       if (la.slot_obs[k] >= 0) z = fma((double)la.obs[obs0 + la.slot_obs[k]], (double)wp[k], z);
     if constexpr (LOOK) {  // the held row is day max(t - 1, 0)'s: its lookahead inputs are rebuilt, never carried
-      look_inputs(la.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+      look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t > 0 ? t - 1 : 0u, ndays, lf, estream);
       z = look_logit(la.look, lf, lw, z);
     }
   }
@@ -252,7 +256,7 @@ __global__ __launch_bounds__(BLOCK, 3) void k_rollout_linear(const LinearRollout
       zp = fma(xk, (double)wp[k], zp);
     }
     if constexpr (LOOK) {  // xv[] is day t's row: tomorrow's decision looks ahead from day t
-      look_inputs(la.look, lser, t, ndays, lf);
+      look_inputs<NOISE>(la.look, look_series_of<NOISE>(la.look, lser, cold.x), t, ndays, lf, estream);
       zp = look_logit(la.look, lf, lw, zp);
     }
     if (!(xv[30] > 0.5f)) ze = -__builtin_inf();

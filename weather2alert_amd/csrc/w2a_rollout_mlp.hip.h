@@ -186,7 +186,9 @@ __device__ __forceinline__ float mlp_logit_groups(const MlpRolloutArgs &ma, int3
 // LOOK (w2a_lookahead_rollout_mlp and its _gated form): every lane also puts the lookahead inputs of the row it holds
 // (w2a_lookahead.hip.h) into a second LDS region next to xs, and the first layer runs on over them. LOOK = false
 // compiles from the statements it had before; there is no RECORD form.
-template <int WIDTH, int LAYERS, bool MASKS, bool RECORD, bool GATE, bool LOOK = false>
+// NOISE (w2a_forecast_rollout_mlp; needs LOOK): the lookahead inputs carry the forecast error of ma.look.mae, as in
+// k_rollout_linear.
+template <int WIDTH, int LAYERS, bool MASKS, bool RECORD, bool GATE, bool LOOK = false, bool NOISE = false>
 __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs ma, const int32_t sample,
                                                           const w2a_trajectory tr) {
   __shared__ __attribute__((aligned(16))) float s_x[MLP_WAVES][64 * MLP_XS];
@@ -247,13 +249,15 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
     xlrow = xl + (threadIdx.x & 63) * W2A_LOOK_PAD;
     lser = look_series(ma.look, cold.x);
   }
+  uint64_t estream = 0;
+  if constexpr (NOISE) estream = look_noise_stream(ma.look, (uint64_t)(a.gid0 + e), cold.w);
   // first day: the logit of the observation row the agent holds (zeros for lanes with no live env)
 #pragma unroll
   for (int k = 0; k < ROWF; ++k)
     xrow[k] = (k < RO64_SLOTS && ma.slot_obs[k] >= 0 && active) ? ma.obs[obs0 + ma.slot_obs[k]] : 0.0f;
   if constexpr (LOOK) {  // the held row is day max(t - 1, 0)'s: its lookahead inputs are rebuilt, never carried
     float lf[W2A_LOOK_MAX];
-    look_inputs(ma.look, lser, t > 0 ? t - 1 : 0u, ndays, lf);
+    look_inputs<NOISE>(ma.look, look_series_of<NOISE>(ma.look, lser, cold.x), t > 0 ? t - 1 : 0u, ndays, lf, estream);
 #pragma unroll
     for (int k = 0; k < W2A_LOOK_PAD; ++k) xlrow[k] = (k < W2A_LOOK_MAX && active) ? lf[k < W2A_LOOK_MAX ? k : 0] : 0.0f;
   }
@@ -315,7 +319,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_rollout_mlp(const MlpRolloutArgs m
     }
     if constexpr (LOOK) {  // xv[] is day t's row: tomorrow's decision looks ahead from day t
       float lf[W2A_LOOK_MAX];
-      look_inputs(ma.look, lser, t, ndays, lf);
+      look_inputs<NOISE>(ma.look, look_series_of<NOISE>(ma.look, lser, cold.x), t, ndays, lf, estream);
 #pragma unroll
       for (int k = 0; k < W2A_LOOK_PAD; ++k) xlrow[k] = (k < W2A_LOOK_MAX && active) ? lf[k < W2A_LOOK_MAX ? k : 0] : 0.0f;
     }
@@ -410,6 +414,17 @@ static void launch_rollout_mlp_lookahead(const MlpRolloutArgs &ma, bool masks, i
   else if (ma.gate) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
   else if (masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false, false, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
   else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false, false, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+}
+
+// the 24 NOISE instantiations (w2a_forecast_rollout_mlp, allowed_days nullable): no trajectory
+template <int WIDTH, int LAYERS>
+static void launch_rollout_mlp_forecast(const MlpRolloutArgs &ma, bool masks, int32_t sample, unsigned grid, hipStream_t s) {
+  w2a_trajectory tr;
+  memset(&tr, 0, sizeof(tr));
+  if (ma.gate && masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false, true, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else if (ma.gate) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false, true, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else if (masks) hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, true, false, false, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
+  else hipLaunchKernelGGL((k_rollout_mlp<WIDTH, LAYERS, false, false, false, true, true>), dim3(grid), dim3(BLOCK), 0, s, ma, sample, tr);
 }
 
 #endif  // W2A_ROLLOUT_MLP_HIP_H

@@ -12,6 +12,7 @@ fallback -- constructing an env without a ROCm device or without libw2a.so raise
 from __future__ import annotations
 
 import ctypes as C
+import types
 from typing import Literal
 
 import numpy as np
@@ -989,13 +990,24 @@ class HeatAlertVecEnv(_VectorEnvBase):
         "days": D}`` (a policy's "lookahead" value): f_k = h(r + k) - h(r), k = 1..D, with h the series of
         lookahead_table(feature) for the env's (county, year), r = max(t - 1, 0) the day of the row step() returned last
         (Q6), and 0 where r + k >= n_days of the env. What the kernels of a lookahead policy form themselves: a torch
-        policy driven through step() acts on ``cat(obs, env.lookahead_features(spec))``."""
+        policy driven through step() acts on ``cat(obs, env.lookahead_features(spec))``. A spec with ``"error"``
+        (policy.check_lookahead) gives the noisy inputs, formed by the device function the rollout kernels use
+        (w2a_forecast_features): the same values whenever and however often it is asked."""
         if self._needs_reset:
             raise RuntimeError("call reset() before lookahead_features()")
         feature, D = _policy.check_lookahead({"lookahead": spec}, "lookahead_features()", self.ct.feature_names,
                                              self.ct.obs_slot, self.ct.n_obs, self.fixes,
                                              self.ct.slot_of.get("alerts_2wks", -1))
         tab = self.lookahead_table(feature)
+        fe = _policy.check_forecast_error({"lookahead": spec}, "lookahead_features()")
+        if fe is not None:
+            pol = types.SimpleNamespace(look_feature=feature, look_days=D, look_error=fe[0], look_error_seed=fe[1])
+            look, ferr = self._lookahead_struct(pol), self._forecast_error_struct(pol)
+            out = torch.empty((self.num_envs, D), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                _ffi.check(self._lib.w2a_forecast_features(self._h, C.byref(look), C.byref(ferr), out.data_ptr(),
+                                                           self._stream()), "w2a_forecast_features")
+            return out
         st = self._state_packed(("t", "n_days", "county_w", "year_i"))[1]
         row = (st["county_w"].long() * self.ct.Y + st["year_i"].long())[:, None]
         r = (st["t"].long() - 1).clamp_(min=0)[:, None]
@@ -1011,6 +1023,17 @@ class HeatAlertVecEnv(_VectorEnvBase):
         lk.series, lk.stride, lk.days = tab.data_ptr(), int(tab.shape[1]), pol.look_days
         lk.weight = pol.look_weight.data_ptr() if getattr(pol, "look_weight", None) is not None else None
         return lk
+
+    @staticmethod
+    def _forecast_error_struct(pol):
+        """The w2a_forecast_error block of a checked lookahead policy with "error", None without the key."""
+        if getattr(pol, "look_error", None) is None:
+            return None
+        fe = _ffi.ForecastError()
+        for k, v in enumerate(pol.look_error):
+            fe.mae[k] = v
+        fe.seed = pol.look_error_seed
+        return fe
 
     def _rollout_linear(self, lin, n_steps, alert_mask, record=False, posterior_returns=False, hindsight=False,
                         policy_gradient=None, gate=None) -> dict:
@@ -1073,6 +1096,7 @@ class HeatAlertVecEnv(_VectorEnvBase):
         steps = int(n_steps) if n_steps is not None else ct.T
         # a lookahead policy (rollout() has refused record=True): the w2a_lookahead_* entry points
         look = self._lookahead_struct(keep) if getattr(keep, "look_days", 0) else None
+        ferr = self._forecast_error_struct(keep)  # with "error": the w2a_forecast_* entry points
         out = {"return": torch.empty(n, dtype=torch.float32, device=dev),
                "alerts": torch.empty(n, dtype=torch.int32, device=dev),
                "attempts_over_budget": torch.empty(n, dtype=torch.int32, device=dev)}
@@ -1130,15 +1154,25 @@ class HeatAlertVecEnv(_VectorEnvBase):
                 pg_args = (self._h, C.byref(lp), _ffi.PG_BASELINES[policy_gradient], steps, self._obs.data_ptr(),
                            out["_policy_gradient_env"].data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
                 if look is not None:
-                    _ffi.check(self._lib.w2a_lookahead_policy_gradient_linear(
+                    fn = "w2a_lookahead_policy_gradient_linear" if ferr is None else "w2a_forecast_policy_gradient_linear"
+                    _ffi.check(getattr(self._lib, fn)(
                         *pg_args, C.byref(look), None if gate is None else gate.data_ptr(),
-                        0 if gate is None else int(gate.shape[1])), "w2a_lookahead_policy_gradient_linear")
+                        0 if gate is None else int(gate.shape[1]), *(() if ferr is None else (C.byref(ferr),))), fn)
                 elif gate is None:
                     _ffi.check(self._lib.w2a_policy_gradient_linear(*pg_args), "w2a_policy_gradient_linear")
                 else:
                     _ffi.check(self._lib.w2a_policy_gradient_linear_gated(*pg_args, gate.data_ptr(), int(gate.shape[1])),
                                "w2a_policy_gradient_linear_gated")
-            if look is not None:
+            if ferr is not None:
+                fn = "w2a_forecast_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_forecast_rollout_linear"
+                _ffi.check(getattr(self._lib, fn)(
+                    self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
+                    out["alerts"].data_ptr(), out["attempts_over_budget"].data_ptr(),
+                    None if mask is None else mask.data_ptr(), None if amask is None else amask.data_ptr(), words,
+                    self._fr_ptr, None if snap is None else snap.data_ptr(), self._stream(), C.byref(look),
+                    None if gate is None else gate.data_ptr(), 0 if gate is None else int(gate.shape[1]),
+                    C.byref(ferr)), fn)
+            elif look is not None:
                 fn = "w2a_lookahead_rollout_mlp" if isinstance(lp, _ffi.MlpPolicy) else "w2a_lookahead_rollout_linear"
                 args = (self._h, C.byref(lp), steps, self._obs.data_ptr(), out["return"].data_ptr(),
                         out["alerts"].data_ptr(), out["attempts_over_budget"].data_ptr(),
@@ -1333,13 +1367,15 @@ class HeatAlertVecEnv(_VectorEnvBase):
                         self._stream(), None if gate is None else gate.data_ptr(),
                         0 if gate is None else int(gate.shape[1])), "w2a_relabel_imitation_linear")
                 elif pol.look_days:
-                    look = self._lookahead_struct(pol)
-                    _ffi.check(self._lib.w2a_lookahead_imitation_gradient_linear(
+                    look, ferr = self._lookahead_struct(pol), self._forecast_error_struct(pol)
+                    fn = "w2a_lookahead_imitation_gradient_linear" if ferr is None else \
+                        "w2a_forecast_imitation_gradient_linear"
+                    _ffi.check(getattr(self._lib, fn)(
                         self._h, C.byref(lp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),
                         0 if dw is None else int(dw.shape[0]), steps, self._obs.data_ptr(), rows.data_ptr(),
                         out["log_likelihood"].data_ptr(), out["days"].data_ptr(), self._stream(), C.byref(look),
-                        None if gate is None else gate.data_ptr(), 0 if gate is None else int(gate.shape[1])),
-                        "w2a_lookahead_imitation_gradient_linear")
+                        None if gate is None else gate.data_ptr(), 0 if gate is None else int(gate.shape[1]),
+                        *(() if ferr is None else (C.byref(ferr),))), fn)
                 elif gate is not None:
                     _ffi.check(self._lib.w2a_imitation_gradient_linear_gated(
                         self._h, C.byref(lp), mask.data_ptr(), words, wp, None if dw is None else dw.data_ptr(),

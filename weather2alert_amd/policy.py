@@ -45,6 +45,8 @@ class LinearPolicyArgs:
     look_feature: str | None = None          # "lookahead": the feature's name, None without the key
     look_days: int = 0                       # D
     look_weight: torch.Tensor | None = None  # f32 [G, LOOKAHEAD_PAD], k = 1 first, zero past D
+    look_error: tuple | None = None          # "error": the MAE row e_1..e_D as f32 values, None without the key
+    look_error_seed: int = 0                 # "error_seed"
 
 
 def check_lookahead(policy: dict, who: str, feature_names=None, obs_slot=None, n_obs: int | None = None, fixes=(),
@@ -54,12 +56,22 @@ def check_lookahead(policy: dict, who: str, feature_names=None, obs_slot=None, n
     observation columns: h the f32 table value of `feature` along the env's episode, r the day of the row the agent
     holds, 0 past the env's last day. ValueError for another structure, a D that is not an int in 1..10, a feature that
     is no observation column and -- the rule of alert_gate() -- one that is not table-sourced (run-time slots 24..27, and
-    alerts_2wks under the "alert_2wks" fix). The name is checked when `feature_names` is given."""
+    alerts_2wks under the "alert_2wks" fix). The name is checked when `feature_names` is given.
+
+    Two optional keys add forecast error (the older reference env's ``forecast_error > 0``; check_forecast_error
+    returns them, this function's result does not change): ``"error"``, one finite non-negative MAE for every lead or
+    a sequence of exactly D of them e_1..e_D in the feature's own units, and ``"error_seed"``, an int in 0..2**63 - 1
+    (default 0; ValueError without "error"). Then, for the held row's day r,
+    f_k = fmaf(U(r, k), e_k, h(r + k)) - h(r) in f32, with h(r) exact, +0 past the env's last day, h(r + k) taken as it
+    is where e_k == 0, and U uniform in [-1, 1) from a counter-based stream of (error_seed, global env id, episode
+    number, held day, lead) alone (include/w2a.h: w2a_forecast_error). ValueError for a bool, str or None value, a
+    negative, NaN or inf entry and a sequence of another length; every other key stays refused."""
     if not isinstance(policy, dict) or policy.get("lookahead") is None:
         return None
     la = policy["lookahead"]
-    if not isinstance(la, dict) or set(la) != {"feature", "days"}:
-        raise ValueError(f"{who}: 'lookahead' must be {{'feature': name, 'days': D}}, got {la!r}")
+    if not isinstance(la, dict) or not {"feature", "days"} <= set(la) <= {"feature", "days", "error", "error_seed"}:
+        raise ValueError(f"{who}: 'lookahead' must be {{'feature': name, 'days': D}} with the optional keys 'error' and "
+                         f"'error_seed', got {la!r}")
     feature, D = la["feature"], la["days"]
     if not isinstance(feature, str):
         raise ValueError(f"{who}: lookahead feature must be a column name, got {feature!r}")
@@ -75,7 +87,53 @@ def check_lookahead(policy: dict, who: str, feature_names=None, obs_slot=None, n
             if 24 <= slot <= 27 or ("alert_2wks" in set(fixes) and slot == slot_alerts_2wks):
                 raise ValueError(f"{who}: lookahead feature {feature!r} is not table-sourced (lookahead reads "
                                  "table-sourced columns only)")
+    _forecast_error(la, int(D), who)
     return feature, int(D)
+
+
+def _forecast_error(la: dict, D: int, who: str):
+    """None, or (the MAE row as D Python floats holding f32 values, the seed) of a checked-so-far lookahead dict."""
+    if "error" not in la:
+        if "error_seed" in la:
+            raise ValueError(f"{who}: lookahead 'error_seed' needs 'error'")
+        return None
+    err = la["error"]
+    if err is None or isinstance(err, (bool, np.bool_, str, bytes, dict)):
+        raise ValueError(f"{who}: lookahead error must be a number or a sequence of D numbers, got {err!r}")
+    if isinstance(err, (int, float, np.integer, np.floating)):
+        row = [err] * D
+    else:
+        try:
+            row = list(err.tolist() if hasattr(err, "tolist") else err)
+        except TypeError:
+            raise ValueError(f"{who}: lookahead error must be a number or a sequence of D numbers, got {err!r}") from None
+        if len(row) != D:
+            raise ValueError(f"{who}: lookahead error must have exactly days={D} entries, got {len(row)}")
+    out = []
+    for v in row:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{who}: lookahead error entries must be numbers, got {v!r}")
+        with np.errstate(over="ignore"):
+            try:
+                f = float(np.float32(v))
+            except OverflowError:
+                f = float("inf")
+        if not np.isfinite(f) or f < 0:  # the kernels compute on the f32 values
+            raise ValueError(f"{who}: lookahead error entries must be finite and non-negative (as float32), got {v!r}")
+        out.append(f)
+    seed = la.get("error_seed", 0)
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2**63:
+        raise ValueError(f"{who}: lookahead error_seed must be an int in 0..2**63 - 1, got {seed!r}")
+    return tuple(out), int(seed)
+
+
+def check_forecast_error(policy: dict, who: str):
+    """None for a policy without ``"lookahead"`` or without its ``"error"`` key, else (e_1..e_D as f32 values, seed):
+    what check_lookahead checks of the two optional keys, returned."""
+    look = check_lookahead(policy, who)
+    if look is None:
+        return None
+    return _forecast_error(policy["lookahead"], look[1], who)
 
 
 def slot_map(obs_slot, n_obs: int) -> np.ndarray:
@@ -159,6 +217,9 @@ def check_linear_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, devic
     if look is not None:
         args.look_feature, args.look_days = look
         args.look_weight = torch.nn.functional.pad(w[:, n_obs:], (0, LOOKAHEAD_PAD - D)).contiguous()
+        fe = _forecast_error(policy["lookahead"], D, "linear policy")
+        if fe is not None:
+            args.look_error, args.look_error_seed = fe
     return args
 
 
@@ -464,6 +525,8 @@ class MlpPolicyArgs:
     group_major: bool = False    # `order` is group_order(group), built here (no "order" key in the policy)
     look_feature: str | None = None  # "lookahead": the feature's name, None without the key
     look_days: int = 0               # D: params then has mlp_lookahead_stride floats per block
+    look_error: tuple | None = None  # "error": the MAE row e_1..e_D as f32 values, None without the key
+    look_error_seed: int = 0         # "error_seed"
 
 
 def _real(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -918,9 +981,11 @@ def check_mlp_policy(policy: dict, n_obs: int, num_envs: int, obs_slot, device, 
     if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool):
         raise ValueError("mlp policy: 'seed' must be an int")
     shapes = [tuple(np.shape(W)) for W, _ in policy["layers"]]
+    fe = None if look is None else _forecast_error(policy["lookahead"], D, "mlp policy")
     return MlpPolicyArgs(P.to(device).contiguous(), g, order, G, nl, width, act, bool(sample), int(seed) & (2**64 - 1),
                          bool(rb), tuple(int(sh[-2]) for sh in shapes[:-1]), int(shapes[-1][-2]), group_major,
-                         None if look is None else look[0], D)
+                         None if look is None else look[0], D, None if fe is None else fe[0],
+                         0 if fe is None else fe[1])
 
 
 def mlp_from_module(module: torch.nn.Module, group=None) -> dict:
